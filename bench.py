@@ -2,6 +2,8 @@
 """Headline benchmark of the KASportsFormer hot path on MI355X.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR   # + what the last timed step computed, as DIR/<name>.npy
+    python bench.py --full                # + forward-only rates, parity / profile quotes, kernel rooflines, other configs, fp32 mode, CPU baseline
     python bench.py --gpus N ...          # starts N rank processes itself (one per GPU, RCCL), relays rank 0's line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...   # or under a launcher
 
@@ -9,7 +11,8 @@ A "step" is one full training pass of the path over one batch already resident i
 3-term loss, backward, (N>1: bucketed RCCL all-reduce of the flat gradient, overlapped with backward),
 fused AdamW.  Workload (BASELINE.json configs[1]): SportsPose-GT 27-frame clips, bf16 compute, batch 256
 per GPU, the shipped 26-layer model, synthetic inputs, reference default init under seed 114514.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline needs; every other measurement or
+check runs after the timed steps and only with --full.
 """
 import argparse
 import ctypes as C
@@ -270,14 +273,37 @@ def parity_summary():
 
 
 FLOP_PER_CLIP_FWD = {27: 27.44e9, 81: 85.28e9}
+DUMP_MAX_ELEMS = 3 << 20             # per dumped array; larger ones are replaced by a fixed sample (4 arrays x 12 MB stay under 64 MB)
+
+
+def dump_outputs(d, model, pred, parts):
+    """Writes what the timed path handed its caller in the last timed step, as float32 DIR/<name>.npy: `pred` (the model's output) and, for a
+    training step, `loss_terms` ([total, mpjpe, n_mpjpe, velocity]), `params` (the live flat parameters after the optimizer step), `grad` (the
+    step's flat gradient) and `buffers` (BatchNorm running statistics).  An array of more than DUMP_MAX_ELEMS entries is replaced by the same
+    seeded sample of its flattened entries in every run (the 29.4 M parameters would be 117 MB)."""
+    import numpy as np
+    arrays = {"pred": pred}
+    if parts is not None:
+        arrays.update(loss_terms=parts, params=model._flat[:model.n_live], grad=model.flat_grad[:model.n_live], buffers=model._flat_buffers)
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0)).sort()[0]
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(d, name + ".npy"), t.float().cpu().numpy())
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1, help="number of ranks (one process per GPU).  Without a launcher's WORLD_SIZE in the environment "
                     "and N > 1, this process starts the N ranks itself and relays rank 0's line")
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and quote everything beyond the headline: forward-only rates, "
+                    "the committed parity / profile figures, kernel rooflines, the other BASELINE configs, fp32 mode, the CPU baseline (the --no-* options "
+                    "below switch single legs off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--batch", type=int, default=BATCH_PER_GPU, help="clips per GPU (weak scaling: the default)")
     ap.add_argument("--frames", type=int, default=T, help="clip length (27: configs[1]; 81: configs[3])")
     ap.add_argument("--global-batch", type=int, default=0, help="STRONG scaling: one global batch of this many clips split over the ranks (BASELINE configs[2] is "
@@ -291,7 +317,10 @@ def parse_args(argv=None):
     ap.add_argument("--grad-dtype", choices=("fp32", "bf16"), default="fp32", help="wire format of the gradient all-reduce (bf16: 58.7 MB per step instead of 117.4)")
     ap.add_argument("--force-dp", action="store_true", help="testing: take the data-parallel code path (stage-sliced backward, RCCL all-reduce) with one rank")
     ap.add_argument("--launch-only", action="store_true", help="testing: the ranks rendezvous, all-reduce one number and leave (gloo without GPUs); no model")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args, argv):
@@ -418,8 +447,7 @@ def extra_config_legs(log):
             legs[name] = {"error": repr(e)}
         torch.cuda.empty_cache()
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--force-dp", "--global-batch", "32", "--det-conf", "--steps", "20", "--warmup", "5",
-           "--no-cpu-baseline", "--no-fp32", "--no-kernel-roofline", "--no-extra-configs"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--force-dp", "--global-batch", "32", "--det-conf", "--steps", "20", "--warmup", "5"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     try:
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, timeout=300)
@@ -482,16 +510,17 @@ def main():
 
     def train_step():
         opt.zero_grad()
-        loss, parts = K.loss3(model(x), y)
+        pred = model(x)
+        loss, parts = K.loss3(pred, y)
         loss.backward()
         if dp is not None:
             dp.finish_gradients()
         opt.step()
-        return parts
+        return parts, pred.detach()
 
     def eval_step():                         # configs[4]: inference only, no flip, no communication
         with torch.no_grad():
-            return model(x)
+            return None, model(x)
 
     if args.eval_only:
         model.eval()
@@ -516,14 +545,14 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        parts = step()
+        parts, pred = step()
     torch.cuda.synchronize()
     dt_own = time.perf_counter() - t0        # this rank's own K steps (reported per rank); the headline clock stops after the barrier below
     fence()
     dt = time.perf_counter() - t0
     # a step that produced NaN / inf is not a measurement (checked after the clock has stopped: .item() synchronises)
     if args.eval_only:
-        if not bool(torch.isfinite(parts).all()):
+        if not bool(torch.isfinite(pred).all()):
             raise RuntimeError("bench: non-finite predictions after the timed passes")
     elif not all(math.isfinite(float(v)) for v in parts) or not bool(torch.isfinite(model._flat[:model.n_live]).all()):
         raise RuntimeError(f"bench: non-finite loss terms or parameters after the timed steps: {[float(v) for v in parts]}")
@@ -537,31 +566,35 @@ def main():
         per_rank = [args.batch * args.steps / float(t.item()) for t in own]
     loss_val = None if args.eval_only else float(parts[0].item())
     log(f"timed {args.steps} steps in {dt:.3f} s")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, pred, parts)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
     # BASELINE's metric is "train+eval": the forward-only rate of the same model and batch (evaluation mode, with and without flip-TTA) is
-    # reported next to the headline; it is NOT part of `value` and runs after the timed region.
-    model.eval()
-    with torch.no_grad():
-        for _ in range(2):
-            model(x)
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(5):
-            model(x)
-        fence()
-        dt_eval = (time.perf_counter() - t0) / 5
-        K.predict_flip_tta(model, x)
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(3):
+    # reported next to the headline (--full); it is NOT part of `value` and runs after the timed region.
+    if args.full:
+        model.eval()
+        with torch.no_grad():
+            for _ in range(2):
+                model(x)
+            fence()
+            t0 = time.perf_counter()
+            for _ in range(5):
+                model(x)
+            fence()
+            dt_eval = (time.perf_counter() - t0) / 5
             K.predict_flip_tta(model, x)
-        fence()
-        dt_tta = (time.perf_counter() - t0) / 3
-    if world > 1:
-        te = torch.tensor([dt_eval, dt_tta], device="cuda", dtype=torch.float64)
-        dist.all_reduce(te, op=dist.ReduceOp.MAX)
-        dt_eval, dt_tta = float(te[0]), float(te[1])
-    model.train()
+            fence()
+            t0 = time.perf_counter()
+            for _ in range(3):
+                K.predict_flip_tta(model, x)
+            fence()
+            dt_tta = (time.perf_counter() - t0) / 3
+        if world > 1:
+            te = torch.tensor([dt_eval, dt_tta], device="cuda", dtype=torch.float64)
+            dist.all_reduce(te, op=dist.ReduceOp.MAX)
+            dt_eval, dt_tta = float(te[0]), float(te[1])
+        model.train()
 
     if rank == 0:
         clips = args.batch * world * args.steps
@@ -581,12 +614,13 @@ def main():
                        **({"gradient_allreduce": "bf16 on the wire, fp32 master gradient"} if (dp is not None and args.grad_dtype == "bf16") else {})},
             "per_rank_clips_per_sec": per_rank,
             "final_loss": loss_val,
-            "eval": {"clips_per_sec": args.batch * world / dt_eval, "clips_per_sec_flip_tta": args.batch * world / dt_tta,
-                     "note": "forward only, same model and batch per GPU, evaluation mode; not part of value"},
-            "parity": parity_summary(),
             "model_mfma_frac": value / world * flop_per_clip / (PEAK_BF16_TFLOPS * 1e12),
         }
-        if not args.no_kernel_roofline:
+        if args.full:
+            out["eval"] = {"clips_per_sec": args.batch * world / dt_eval, "clips_per_sec_flip_tta": args.batch * world / dt_tta,
+                           "note": "forward only, same model and batch per GPU, evaluation mode; not part of value"}
+            out["parity"] = parity_summary()
+        if args.full and not args.no_kernel_roofline:
             ks = kernel_rooflines(args.batch * Tn * 17)
             log("kernel rooflines done")
             dom = max(ks, key=lambda k: ks[k]["seconds"])
@@ -632,8 +666,8 @@ def main():
                 out["step_hbm_GB"] = json.load(open(STEP_TRAFFIC_FILE))["hbm_GB_per_step"]
                 out["step_hbm_GB_source"] = "committed file profiles/" + os.path.basename(STEP_TRAFFIC_FILE)
             out["kernels"] = {k: {"ms": v["seconds"] * 1e3, "tflops": v["achieved_tflops"]} for k, v in ks.items()}
-        if world == 1:
-            del model, opt, x, y
+        if args.full and world == 1:
+            del model, opt, x, y, pred
             torch.cuda.empty_cache()
             if headline and not args.force_dp and not args.no_extra_configs:
                 out["configs"] = extra_config_legs(log)
@@ -642,9 +676,10 @@ def main():
                 log("fp32 parity-mode leg done")
             if not args.no_cpu_baseline and not args.eval_only and Tn == T:
                 out["cpu_baseline"] = cpu_baseline()
-        out["profile_stale"] = bool(STALE)       # a quoted committed file was measured on other sources than this library's: its figures are omitted above
-        if STALE:
-            out["profile_stale_files"] = sorted(STALE)
+        if args.full:
+            out["profile_stale"] = bool(STALE)       # a quoted committed file was measured on other sources than this library's: its figures are omitted above
+            if STALE:
+                out["profile_stale_files"] = sorted(STALE)
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if world > 1 or args.force_dp:

@@ -45,3 +45,9 @@ def test_the_launcher_process_never_imports_torch():
     e = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     r = subprocess.run([sys.executable, "-c", code], env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=240)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
+
+
+def test_steps_below_one_are_refused():
+    r = _run(["--steps", "0"])
+    assert r.returncode == 2 and b"--steps must be at least 1" in r.stderr
+    assert not r.stdout.decode().strip()

@@ -71,8 +71,8 @@ timeout -k 10 200 python tools/bench_configs.py train27 2>/dev/null | grep '^{' 
 KASF_SINGLE_STREAM=1 timeout -k 10 200 python tools/bench_configs.py train27 2>/dev/null | grep '^{' | sed 's/"config": "train/"config": "KASF_SINGLE_STREAM=1 train/' >> $O/r6_configs.jsonl
 need $O/r6_configs.jsonl
 say "strong-scaling bench lines at the per-rank shapes of BASELINE configs[2] (one global batch of 256 over 8 / 4 ranks), data-parallel path, one rank"
-timeout -k 10 300 python bench.py --force-dp --global-batch 32 --det-conf --steps 20 --warmup 5 --no-cpu-baseline --no-fp32 --no-kernel-roofline > $O/r6_bench_strong_b32.json 2> $O/bench32.err; need $O/r6_bench_strong_b32.json
-timeout -k 10 300 python bench.py --force-dp --global-batch 64 --det-conf --steps 20 --warmup 5 --no-cpu-baseline --no-fp32 --no-kernel-roofline > $O/r6_bench_strong_b64.json 2> $O/bench64.err; need $O/r6_bench_strong_b64.json
+timeout -k 10 300 python bench.py --full --force-dp --global-batch 32 --det-conf --steps 20 --warmup 5 --no-cpu-baseline --no-fp32 --no-kernel-roofline > $O/r6_bench_strong_b32.json 2> $O/bench32.err; need $O/r6_bench_strong_b32.json
+timeout -k 10 300 python bench.py --full --force-dp --global-batch 64 --det-conf --steps 20 --warmup 5 --no-cpu-baseline --no-fp32 --no-kernel-roofline > $O/r6_bench_strong_b64.json 2> $O/bench64.err; need $O/r6_bench_strong_b64.json
 say "26-layer parity samples (tests/test_gpu_model.py writes gpurun_out/r6_parity_26layers_{fp32,bf16}.json; the bench line's parity object is read from them)"
 timeout -k 10 600 python -m pytest tests/test_gpu_model.py -x -q -m gpu -k "full_depth_26" > $O/parity26.log 2>&1 || { tail -5 $O/parity26.log; echo "refresh_profiles_r6: the 26-layer parity test failed"; exit 4; }
 need gpurun_out/r6_parity_26layers_bf16.json
@@ -86,7 +86,7 @@ python - <<'PY'
 import json, os, shutil
 shutil.copy("gpurun_out/r6/r6_STAMP.json", "profiles/r6_STAMP.json")
 PY
-timeout -k 10 600 python bench.py > $O/r6_bench_b256.json 2> $O/bench.err; need $O/r6_bench_b256.json
+timeout -k 10 600 python bench.py --full > $O/r6_bench_b256.json 2> $O/bench.err; need $O/r6_bench_b256.json
 rm -rf $O/prof27 $O/prof27f $O/prof27sf $O/prof81 $O/prof32 $O/prof27s $O/prof81s $O/prof32s $O/profe $O/pmc_f $O/pmc_w $O/profm $R/gpurun_out/pmcs_f $R/gpurun_out/pmcs_w
 stamp_all
 say done; ls $O
