@@ -21,6 +21,9 @@
  *   kasf_joint_flip        <- joint_flip                            utils/utilities.py:128-135
  *   kasf_tta_merge         <- flip-TTA average + root zeroing        train_and_evaluate_sp.py:46-55
  *   kasf_eval_metrics      <- de-normalise + MPJPE/JPE/accel/P-MPJPE train_and_evaluate_sp.py:57-93, utils/error_calc.py:5-48
+ *   kasf_lift_window_count <- turn_into_clips (number of clips)     demo/demo.py:132-156
+ *   kasf_lift_windows      <- turn_into_clips + normalize_screen_coordinates + flip_data  demo/demo.py:132-156,222-227, demo/lib/utils.py:5-20
+ *   kasf_lift_stitch       <- flip-TTA average + root zeroing + downsample of the tail clip  demo/demo.py:229-236
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
  */
 #ifndef KASF_H_
@@ -158,6 +161,30 @@ int kasf_tta_merge(const float* pred, const float* pred_of_flipped, float* out, 
 #define KASF_EVAL_COLS 22
 int kasf_eval_metrics(const float* pred, const float* label_scaled, const float* factor, const float* res, const int32_t* action, int32_t batch,
                       int32_t n_frames, int32_t n_actions, float* mpjpe, float* p_mpjpe, float* accel, float* jpe, double* action_sums, void* stream);
+
+/* ---- lifting a 2-D keypoint track to 3-D poses (demo/demo.py:194-254, lift_3d_pose): track [P][n][17][3] fp32 = pixel x, y, confidence ----
+ * The window plan: W windows of T frames (T in [1, 256], stride in [1, T]).
+ *   stride == T (the demo): windows start at 0, T, 2T, ...; a last window of L < T frames (and the one window of a track with n < T) is resampled
+ *     to T frames through resample[T] = demo.py:132-136's resample(L, T), computed on the host (float64 linspace, floor, clip).  n = k * T gives
+ *     k full windows (turn_into_clips, demo.py:138-156, raises UnboundLocalError there).
+ *   stride < T (not in the demo): n <= T as above; otherwise windows start at 0, stride, 2 * stride, ... while start + T < n, plus one at n - T,
+ *     all full, and each frame's output is the mean over the windows that cover it (summed in ascending window order, then divided).
+ * kasf_lift_window_count returns W (0 for n = 0), or a negative error code with kasf_last_error() set; it needs no device. */
+int64_t kasf_lift_window_count(int64_t n, int32_t T, int32_t stride);
+/* x_out [(1 + flip) * persons * W][T][17][3]: clip (h * persons + p) * W + w is window w of person p, h = 1 the mirrored copy (the stacking of
+ * predict_flip_tta).  Each frame is normalised as normalize_screen_coordinates (demo/lib/utils.py:16-20): fp32 x / width * 2, then an fp64
+ * subtraction of [1, height / width], stored as fp32; the confidence passes through.  The mirrored copy applies flip_data (demo/lib/utils.py:5-13:
+ * x negated, left joints [1,2,3,14,15,16] swapped with right [4,5,6,11,12,13]) to a copy: the track is never written (demo.py:227 flips its
+ * input in place, so both of its forwards see the mirrored clip).  resample [T] (device) is required when the plan has a resampled window, else
+ * ignored (may be NULL). */
+int kasf_lift_windows(const float* track, int32_t persons, int64_t n, float width, float height, int32_t T, int32_t stride, const int32_t* resample,
+                      int32_t flip, float* x_out, void* stream);
+/* out [persons][n][17][3] from the model's output pred [(1 + flip) * persons * W][T][17][3]: per window (pred + joint_flip(pred of the mirrored
+ * copy)) / 2 (flip = 0: pred alone), root joint zeroed -- kasf_tta_merge's arithmetic, demo.py:229-235 -- and scattered back to the track: frame
+ * start + j of the resampled window reads position first_pos[j], the first t with resample[t] == j (demo.py:146-153's downsample,
+ * np.unique(r, return_index=True)[1]).  first_pos [L] (device) is required when the plan has a resampled window, else ignored (may be NULL). */
+int kasf_lift_stitch(const float* pred, int32_t flip, int32_t persons, int64_t n, int32_t T, int32_t stride, const int32_t* first_pos, float* out,
+                     void* stream);
 
 /* debugging / tests: locate a named activation inside the workspace (see kasf_ws_name()) */
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags);

@@ -14,6 +14,8 @@ Public surface mirrors the reference's interface for this path:
   checkpoint_save, checkpoint_load      utils/utilities.py:110-118, train_and_evaluate_sp.py:171-176,285-301
   slice_source, split_clips,            data/reader/sp_reader.py:25-169,205-249, data/reader/wp_reader.py:25-135,159-199 (offline clip slicing)
   mysplit_clips, resample
+  lift_track, window_plan               demo/demo.py:132-156,194-254, demo/lib/utils.py:5-20 (2-D track -> 3-D poses; also
+                                        `python -m kasportsformer_amd.lift`)
 """
 from .model import (KASportsFormer, load_model, set_single_stream, is_single_stream, set_deterministic, is_deterministic, set_fused_attention_backward,
                     is_fused_attention_backward)
@@ -27,8 +29,10 @@ from .schedule import warmup_lr, apply_warmup, ReduceLROnPlateau
 from .evaluate import joint_flip, predict_flip_tta, clip_metrics, Evaluator, evaluate_one_epoch
 from .synthetic import synthetic_clips, synthetic_test_extras, teacher_labels, teacher_clips
 from .slicing import slice_source, split_clips, mysplit_clips, resample
+from .lift import lift_track, window_plan
 
 __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_stream", "set_deterministic", "is_deterministic", "set_fused_attention_backward", "is_fused_attention_backward", "loss3", "FusedAdamW", "DataParallel", "joint_flip", "predict_flip_tta", "clip_metrics", "Evaluator",
            "evaluate_one_epoch", "PackedClips", "DeviceClipLoader", "pack_clip_directory", "read_clip_file", "shard_indices",
            "checkpoint_save", "checkpoint_load", "strip_module_prefix", "adamw_state_dict", "load_adamw_state_dict", "warmup_lr", "apply_warmup", "ReduceLROnPlateau", "train_one_epoch",
-           "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample"]
+           "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample",
+           "lift_track", "window_plan"]

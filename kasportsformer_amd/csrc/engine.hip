@@ -625,7 +625,7 @@ void kasf_set_fused_attn_bwd(int32_t on) { g_fused_attn_bwd.store(on < 0 ? -1 : 
 int32_t kasf_get_fused_attn_bwd(void) { return fused_attn_bwd_mask(); }
 void kasf_set_deterministic(int32_t on) { kasf_set_single_stream(on); }
 int32_t kasf_get_deterministic(void) { return kasf_get_single_stream(); }
-int kasf_version(void) { return 8; }
+int kasf_version(void) { return 9; }
 
 int kasf_model_create(const kasf_config* cfg, kasf_model** out) {
     if (cfg == nullptr || out == nullptr) return kasf_set_error(2, "null argument");
@@ -1004,6 +1004,43 @@ int kasf_eval_metrics(const float* pred, const float* label_scaled, const float*
     kasf_launch_eval_metrics((hipStream_t)stream, pred, label_scaled, factor, res, action, batch, n_frames, n_actions, mpjpe, p_mpjpe, accel, jpe, action_sums);
     HIPCHK(hipGetLastError());
     return g_err.empty() ? 0 : 3;
+}
+
+static const char* lift_plan_error(int64_t n, int32_t T, int32_t stride) {
+    if (T < 1 || T > 256) return "lift: T must be in [1, 256]";
+    if (stride < 1 || stride > T) return "lift: stride must be in [1, T]";
+    if (n < 0) return "lift: n must be >= 0";
+    return nullptr;
+}
+// the plan has a resampled window: the track is shorter than T, or the demo's windows (stride == T) leave a short tail
+static bool lift_plan_needs_table(int64_t n, int32_t T, int32_t stride) { return n > 0 && (n < T || (stride == T && n % T != 0)); }
+
+int64_t kasf_lift_window_count(int64_t n, int32_t T, int32_t stride) {
+    if (const char* e = lift_plan_error(n, T, stride)) return -(int64_t)kasf_set_error(2, e);
+    return kasf_lift_window_count_of(n, T, stride);
+}
+int kasf_lift_windows(const float* track, int32_t persons, int64_t n, float width, float height, int32_t T, int32_t stride, const int32_t* resample,
+                      int32_t flip, float* x_out, void* stream) {
+    if (const char* e = lift_plan_error(n, T, stride)) return kasf_set_error(2, e);
+    if (persons < 0) return kasf_set_error(2, "lift: persons must be >= 0");
+    if (!(width > 0.0f) || !(height > 0.0f)) return kasf_set_error(2, "lift: width and height must be positive");
+    if (persons == 0 || n == 0) return 0;
+    if (!track || !x_out) return kasf_set_error(2, "null pointer argument");
+    if (resample == nullptr && lift_plan_needs_table(n, T, stride)) return kasf_set_error(2, "lift: this plan has a resampled window and needs the resample table");
+    kasf_launch_lift_windows((hipStream_t)stream, track, persons, n, width, height, T, stride, resample, flip ? 1 : 0, x_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int kasf_lift_stitch(const float* pred, int32_t flip, int32_t persons, int64_t n, int32_t T, int32_t stride, const int32_t* first_pos, float* out,
+                     void* stream) {
+    if (const char* e = lift_plan_error(n, T, stride)) return kasf_set_error(2, e);
+    if (persons < 0) return kasf_set_error(2, "lift: persons must be >= 0");
+    if (persons == 0 || n == 0) return 0;
+    if (!pred || !out) return kasf_set_error(2, "null pointer argument");
+    if (first_pos == nullptr && lift_plan_needs_table(n, T, stride)) return kasf_set_error(2, "lift: this plan has a resampled window and needs first_pos");
+    kasf_launch_lift_stitch((hipStream_t)stream, pred, flip ? 1 : 0, persons, n, T, stride, first_pos, out);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 #define OP_DT_CHECK(dt) \

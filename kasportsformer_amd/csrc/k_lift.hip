@@ -1,0 +1,113 @@
+// Lifting a 2-D keypoint track to 3-D (demo/demo.py:194-254, lift_3d_pose): cut the track into T-frame windows, normalise and mirror them
+// (demo/lib/utils.py:5-20), and, after the model's forward, merge the flip-TTA pair and put every window's frames back on the track.
+// Both kernels move 51 floats per frame: HBM-bound, one fp32 element per thread, consecutive threads on consecutive output floats.
+//
+// Window plan (kasportsformer_amd/lift.py window_plan, kasf.h): W windows of T frames over an n-frame track.
+//   stride == T (the demo's turn_into_clips, demo.py:138-156): windows start at 0, T, 2T, ...; a last window of L < T frames is resampled to
+//     T frames through the host's table resample[T] (demo.py:132-136), and on the way back frame j of it reads position first_pos[j].
+//   stride < T, n > T: windows start at 0, s, 2s, ... while start + T < n, plus one at n - T; all full; a frame's output is the mean over the
+//     windows that cover it, summed in ascending window order.
+//   n <= T (either mode): one window of L = n frames, resampled when n < T.
+#include "kernels.h"
+
+namespace {
+
+// utils/utilities.py:128-135 / demo/lib/utils.py:5-13: destination joint j takes source joint c_lift_flip_src[j]; left [1,2,3,14,15,16] <-> right [4,5,6,11,12,13]
+__constant__ int c_lift_flip_src[17] = {0, 4, 5, 6, 1, 2, 3, 7, 8, 9, 10, 14, 15, 16, 11, 12, 13};
+
+// First frame of window w (of W) on the track.
+__device__ inline int64_t lift_start(int64_t w, int64_t W, int64_t n, int T, int stride) {
+    return (stride < T && n > T && w == W - 1) ? n - T : w * stride;
+}
+
+// x [(1+flip) * P * W, T, 17, 3]: clip (h * P + p) * W + w is window w of person p, mirrored when h == 1.
+// x / w * 2 in fp32, then the fp64 subtraction of [1, h / w], stored as fp32 (normalize_screen_coordinates, demo/lib/utils.py:16-20); confidence unchanged.
+__global__ __launch_bounds__(256) void k_lift_windows(const float* __restrict__ track, int64_t n, int64_t W, int T, int stride, const int* __restrict__ resample,
+                                                      float width, double shift_y, int64_t clips_per_half, int64_t total, float* __restrict__ x) {
+    const int64_t clip_floats = (int64_t)T * 51;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t clip = i / clip_floats, r = i - clip * clip_floats;
+        const int t = (int)(r / 51), q = (int)(r - (int64_t)t * 51), j = q / 3, c = q - 3 * j;
+        const bool mirrored = clip >= clips_per_half;
+        const int64_t pw = mirrored ? clip - clips_per_half : clip;
+        const int64_t p = pw / W, w = pw - p * W;
+        const int64_t start = lift_start(w, W, n, T, stride);
+        const int64_t L = n - start < T ? n - start : T;
+        int64_t f = t;
+        if (L < T) {                                   // the resampled window: table entries are clamped into it, a bad table never reads outside the track
+            const int64_t rt = resample[t];
+            f = rt < 0 ? 0 : (rt >= L ? L - 1 : rt);
+        }
+        const int js = mirrored ? c_lift_flip_src[j] : j;
+        float v = track[(p * n + start + f) * 51 + 3 * js + c];
+        if (c < 2) {
+            const float scaled = v / width * 2.0f;
+            v = (float)((double)scaled - (c == 0 ? 1.0 : shift_y));
+            if (mirrored && c == 0) v = -v;
+        }
+        x[i] = v;
+    }
+}
+
+// out [P, n, 17, 3] from pred [(1+flip) * P * W, T, 17, 3]: per covering window (p + joint_flip(p_f)) / 2 with the root zeroed (kasf_tta_merge,
+// train_and_evaluate_sp.py:46-55 / demo.py:229-235), summed over the covering windows in ascending order and divided by their number.
+__global__ __launch_bounds__(256) void k_lift_stitch(const float* __restrict__ pred, int flip, int64_t n, int64_t W, int T, int stride,
+                                                     const int* __restrict__ first_pos, int64_t clips_per_half, int64_t total, float* __restrict__ out) {
+    const int64_t clip_floats = (int64_t)T * 51;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / 51;
+        const int q = (int)(i - row * 51), j = q / 3, c = q - 3 * j;
+        const int64_t p = row / n, f = row - p * n;
+        if (j == 0) {
+            out[i] = 0.0f;
+            continue;
+        }
+        // windows covering frame f: the regular ones (start w * stride) in [w_lo, w_hi], then, in overlap mode, the last one (start n - T) when it reaches f
+        const bool tail = stride < T && n > T;
+        const int64_t w_lo = f < T ? 0 : (f - T) / stride + 1, last_regular = tail ? W - 2 : W - 1;
+        const int64_t w_hi = f / stride < last_regular ? f / stride : last_regular;
+        float acc = 0.0f;
+        int cnt = 0;
+        for (int64_t w = w_lo; w <= w_hi + (tail && f >= n - T ? 1 : 0); ++w) {
+            const int64_t start = w > w_hi ? n - T : w * stride;
+            const int64_t L = n - start < T ? n - start : T;
+            int64_t t = f - start;
+            if (L < T) {
+                const int64_t ft = first_pos[t];
+                t = ft < 0 ? 0 : (ft >= T ? T - 1 : ft);
+            }
+            const int64_t o = (p * W + (w > w_hi ? W - 1 : w)) * clip_floats + t * 51;
+            float v = pred[o + q];
+            if (flip) {
+                const float fv = pred[clips_per_half * clip_floats + o + 3 * c_lift_flip_src[j] + c];
+                v = (v + (c == 0 ? -fv : fv)) / 2;
+            }
+            acc += v;
+            ++cnt;
+        }
+        out[i] = acc / (float)cnt;
+    }
+}
+
+inline unsigned grid_for(int64_t n) {
+    int64_t g = (n + 255) / 256;
+    return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+}
+
+}  // namespace
+
+void kasf_launch_lift_windows(hipStream_t s, const float* track, int P, int64_t n, float width, float height, int T, int stride, const int* resample, int flip,
+                              float* x) {
+    const int64_t W = kasf_lift_window_count_of(n, T, stride);
+    const int64_t per_half = (int64_t)P * W, total = (flip ? 2 : 1) * per_half * T * 51;
+    if (total <= 0) return;
+    hipLaunchKernelGGL(k_lift_windows, dim3(grid_for(total)), dim3(256), 0, s, track, n, W, T, stride, resample, width, (double)height / (double)width,
+                       per_half, total, x);
+}
+
+void kasf_launch_lift_stitch(hipStream_t s, const float* pred, int flip, int P, int64_t n, int T, int stride, const int* first_pos, float* out) {
+    const int64_t W = kasf_lift_window_count_of(n, T, stride);
+    const int64_t total = (int64_t)P * n * 51;
+    if (total <= 0 || W <= 0) return;
+    hipLaunchKernelGGL(k_lift_stitch, dim3(grid_for(total)), dim3(256), 0, s, pred, flip, n, W, T, stride, first_pos, (int64_t)P * W, total, out);
+}
