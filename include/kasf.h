@@ -24,6 +24,7 @@
  *   kasf_lift_window_count <- turn_into_clips (number of clips)     demo/demo.py:132-156
  *   kasf_lift_windows      <- turn_into_clips + normalize_screen_coordinates + flip_data  demo/demo.py:132-156,222-227, demo/lib/utils.py:5-20
  *   kasf_lift_stitch       <- flip-TTA average + root zeroing + downsample of the tail clip  demo/demo.py:229-236
+ *   kasf_lift_ragged_plan, kasf_lift_windows_ragged, kasf_lift_stitch_ragged <- the same three over many tracks of different lengths in one batch
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
  */
 #ifndef KASF_H_
@@ -185,6 +186,30 @@ int kasf_lift_windows(const float* track, int32_t persons, int64_t n, float widt
  * np.unique(r, return_index=True)[1]).  first_pos [L] (device) is required when the plan has a resampled window, else ignored (may be NULL). */
 int kasf_lift_stitch(const float* pred, int32_t flip, int32_t persons, int64_t n, int32_t T, int32_t stride, const int32_t* first_pos, float* out,
                      void* stream);
+
+/* ---- many tracks of different lengths in one call (ABI 10; one track per tracked person, each its own length) ----
+ * Packed layout: the tracks back to back in packed [frames][17][3] fp32; track p is rows offsets[p] .. offsets[p + 1] - 1, offsets [tracks + 1]
+ * int64 with offsets[0] = 0 and offsets[tracks] = frames.  Each track is cut by its own plan (the rule above with its own n; one T and one stride
+ * for the call), and win_first [tracks + 1] int64 is the prefix sum of the per-track window counts: track p owns windows win_first[p] ..
+ * win_first[p + 1] - 1, win_first[tracks] = windows.
+ * kasf_lift_ragged_plan fills win_first from the track lengths (host arrays; it needs no device) and returns windows, or a negative error code with
+ * kasf_last_error() set (bad T or stride, tracks < 0, a negative length), in which case nothing is written. */
+int64_t kasf_lift_ragged_plan(const int64_t* lengths, int32_t tracks, int32_t T, int32_t stride, int64_t* win_first);
+/* x_out [(1 + flip) * windows][T][17][3]: clip h * windows + win_first[p] + w is window w of track p, h = 1 the mirrored copy (equal lengths: the
+ * clip order of kasf_lift_windows, (h * persons + p) * W + w).  Track p is normalised with its own width[p] and height[p] (device fp32 [tracks],
+ * positive), bit for bit what kasf_lift_windows writes for that track alone.  resample [tracks][T] int32 (device): row p is the track's resample
+ * table when its plan has a resampled window and is not read otherwise. */
+int kasf_lift_windows_ragged(const float* packed, const int64_t* offsets, const int64_t* win_first, int32_t tracks, int64_t frames, int64_t windows,
+                             const float* width, const float* height, int32_t T, int32_t stride, const int32_t* resample, int32_t flip, float* x_out,
+                             void* stream);
+/* out [frames][17][3] from the model's output pred [(1 + flip) * windows][T][17][3] in the clip order above: kasf_lift_stitch's arithmetic per
+ * track.  first_pos [tracks][T] int32 (device): row p holds the track's first_pos in its first L entries when its plan has a resampled window
+ * and is not read otherwise.
+ * Both entries: offsets, win_first, width, height and the tables are device arrays that are only read, and required whenever windows > 0;
+ * tracks, frames and windows are the host's copies of the sizes (error 2 when they cannot belong to one plan).  Every index formed from a device
+ * table is clamped into the arrays those sizes describe: an inconsistent table gives wrong poses, never an access outside the arrays. */
+int kasf_lift_stitch_ragged(const float* pred, int32_t flip, const int64_t* offsets, const int64_t* win_first, int32_t tracks, int64_t frames,
+                            int64_t windows, int32_t T, int32_t stride, const int32_t* first_pos, float* out, void* stream);
 
 /* debugging / tests: locate a named activation inside the workspace (see kasf_ws_name()) */
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags);

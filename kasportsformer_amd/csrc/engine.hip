@@ -625,7 +625,7 @@ void kasf_set_fused_attn_bwd(int32_t on) { g_fused_attn_bwd.store(on < 0 ? -1 : 
 int32_t kasf_get_fused_attn_bwd(void) { return fused_attn_bwd_mask(); }
 void kasf_set_deterministic(int32_t on) { kasf_set_single_stream(on); }
 int32_t kasf_get_deterministic(void) { return kasf_get_single_stream(); }
-int kasf_version(void) { return 9; }
+int kasf_version(void) { return 10; }
 
 int kasf_model_create(const kasf_config* cfg, kasf_model** out) {
     if (cfg == nullptr || out == nullptr) return kasf_set_error(2, "null argument");
@@ -1039,6 +1039,50 @@ int kasf_lift_stitch(const float* pred, int32_t flip, int32_t persons, int64_t n
     if (!pred || !out) return kasf_set_error(2, "null pointer argument");
     if (first_pos == nullptr && lift_plan_needs_table(n, T, stride)) return kasf_set_error(2, "lift: this plan has a resampled window and needs first_pos");
     kasf_launch_lift_stitch((hipStream_t)stream, pred, flip ? 1 : 0, persons, n, T, stride, first_pos, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int64_t kasf_lift_ragged_plan(const int64_t* lengths, int32_t tracks, int32_t T, int32_t stride, int64_t* win_first) {
+    if (const char* e = lift_plan_error(0, T, stride)) return -(int64_t)kasf_set_error(2, e);
+    if (tracks < 0) return -(int64_t)kasf_set_error(2, "lift: tracks must be >= 0");
+    if (!win_first || (tracks > 0 && !lengths)) return -(int64_t)kasf_set_error(2, "null pointer argument");
+    int64_t total = 0;
+    for (int32_t p = 0; p < tracks; ++p) {                 // validate everything before writing anything
+        if (lengths[p] < 0) return -(int64_t)kasf_set_error(2, "lift: track lengths must be >= 0");
+        const int64_t w = kasf_lift_window_count_of(lengths[p], T, stride);
+        if (total > INT64_MAX - w) return -(int64_t)kasf_set_error(2, "lift: too many windows");
+        total += w;
+    }
+    win_first[0] = 0;
+    for (int32_t p = 0; p < tracks; ++p) win_first[p + 1] = win_first[p] + kasf_lift_window_count_of(lengths[p], T, stride);
+    return total;
+}
+// the host's sizes of the packed arrays: every window has a frame, every frame a track, and no track has more windows than frames
+static const char* lift_ragged_error(int32_t tracks, int64_t frames, int64_t windows, int32_t T, int32_t stride) {
+    if (const char* e = lift_plan_error(0, T, stride)) return e;
+    if (tracks < 0 || frames < 0 || windows < 0) return "lift: tracks, frames and windows must be >= 0";
+    if ((frames == 0) != (windows == 0) || windows > frames || (tracks == 0 && frames > 0))
+        return "lift: tracks, frames and windows do not belong to one plan";
+    return nullptr;
+}
+int kasf_lift_windows_ragged(const float* packed, const int64_t* offsets, const int64_t* win_first, int32_t tracks, int64_t frames, int64_t windows,
+                             const float* width, const float* height, int32_t T, int32_t stride, const int32_t* resample, int32_t flip, float* x_out,
+                             void* stream) {
+    if (const char* e = lift_ragged_error(tracks, frames, windows, T, stride)) return kasf_set_error(2, e);
+    if (windows == 0) return 0;
+    if (!packed || !offsets || !win_first || !width || !height || !resample || !x_out) return kasf_set_error(2, "null pointer argument");
+    kasf_launch_lift_windows_ragged((hipStream_t)stream, packed, frames, offsets, win_first, tracks, windows, width, height, T, stride, resample,
+                                    flip ? 1 : 0, x_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int kasf_lift_stitch_ragged(const float* pred, int32_t flip, const int64_t* offsets, const int64_t* win_first, int32_t tracks, int64_t frames,
+                            int64_t windows, int32_t T, int32_t stride, const int32_t* first_pos, float* out, void* stream) {
+    if (const char* e = lift_ragged_error(tracks, frames, windows, T, stride)) return kasf_set_error(2, e);
+    if (frames == 0) return 0;
+    if (!pred || !offsets || !win_first || !first_pos || !out) return kasf_set_error(2, "null pointer argument");
+    kasf_launch_lift_stitch_ragged((hipStream_t)stream, pred, flip ? 1 : 0, windows, offsets, win_first, tracks, frames, T, stride, first_pos, out);
     HIPCHK(hipGetLastError());
     return 0;
 }

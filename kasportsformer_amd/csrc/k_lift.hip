@@ -89,6 +89,96 @@ __global__ __launch_bounds__(256) void k_lift_stitch(const float* __restrict__ p
     }
 }
 
+// ---- many tracks of different lengths in one launch (kasf.h, kasf_lift_*_ragged) ----
+// Tracks packed back to back: track p is rows [offsets[p], offsets[p + 1]) of [frames, 17, 3] and owns windows [win_first[p], win_first[p + 1]) of the
+// call, cut by its own plan (n = its length, W = its window count).  The two kernels are k_lift_windows / k_lift_stitch with (n, W) taken per track.
+// Every index formed from a device table is clamped into the arrays the host sized (frames, windows, tracks): an inconsistent table gives wrong values,
+// never an access outside track, pred or the tables.
+
+// The p in [0, P) with sorted[p] <= key < sorted[p + 1] (sorted: P + 1 non-decreasing entries); any table content gives some p in [0, P).
+__device__ inline int lift_track_of(const int64_t* __restrict__ sorted, int P, int64_t key) {
+    int lo = 0, hi = P - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (sorted[mid] <= key) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__device__ inline int64_t lift_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// x [(1+flip) * windows, T, 17, 3]: clip h * windows + win_first[p] + w is window w of track p, mirrored when h == 1; track p normalised with width[p], height[p].
+__global__ __launch_bounds__(256) void k_lift_windows_ragged(const float* __restrict__ track, int64_t frames, const int64_t* __restrict__ offsets,
+                                                             const int64_t* __restrict__ win_first, int P, int64_t windows, const float* __restrict__ width,
+                                                             const float* __restrict__ height, int T, int stride, const int* __restrict__ resample,
+                                                             int64_t total, float* __restrict__ x) {
+    const int64_t clip_floats = (int64_t)T * 51;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t clip = i / clip_floats, r = i - clip * clip_floats;
+        const int t = (int)(r / 51), q = (int)(r - (int64_t)t * 51), j = q / 3, c = q - 3 * j;
+        const bool mirrored = clip >= windows;
+        const int64_t g = mirrored ? clip - windows : clip;
+        const int p = lift_track_of(win_first, P, g);
+        const int64_t base = offsets[p], n = offsets[p + 1] - base, W = win_first[p + 1] - win_first[p], w = g - win_first[p];
+        const int64_t start = lift_start(w, W, n, T, stride);
+        const int64_t L = n - start < T ? n - start : T;
+        int64_t f = t;
+        if (L < T) {
+            const int64_t rt = resample[(int64_t)p * T + t];
+            f = rt < 0 ? 0 : (rt >= L ? L - 1 : rt);
+        }
+        const int js = mirrored ? c_lift_flip_src[j] : j;
+        float v = track[lift_clamp(base + start + f, 0, frames - 1) * 51 + 3 * js + c];
+        if (c < 2) {
+            const float wp = width[p];
+            const float scaled = v / wp * 2.0f;
+            v = (float)((double)scaled - (c == 0 ? 1.0 : (double)height[p] / (double)wp));
+            if (mirrored && c == 0) v = -v;
+        }
+        x[i] = v;
+    }
+}
+
+// out [frames, 17, 3] from pred [(1+flip) * windows, T, 17, 3] in the clip order above: k_lift_stitch's loop over the windows of the frame's track.
+__global__ __launch_bounds__(256) void k_lift_stitch_ragged(const float* __restrict__ pred, int flip, int64_t windows, const int64_t* __restrict__ offsets,
+                                                            const int64_t* __restrict__ win_first, int P, int T, int stride, const int* __restrict__ first_pos,
+                                                            int64_t total, float* __restrict__ out) {
+    const int64_t clip_floats = (int64_t)T * 51;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / 51;
+        const int q = (int)(i - row * 51), j = q / 3, c = q - 3 * j;
+        if (j == 0) {
+            out[i] = 0.0f;
+            continue;
+        }
+        const int p = lift_track_of(offsets, P, row);
+        const int64_t n = offsets[p + 1] - offsets[p], f = row - offsets[p], wb = win_first[p], W = win_first[p + 1] - wb;
+        const bool tail = stride < T && n > T;
+        const int64_t w_lo = f < T ? 0 : (f - T) / stride + 1, last_regular = tail ? W - 2 : W - 1;
+        const int64_t w_hi = f / stride < last_regular ? f / stride : last_regular;
+        float acc = 0.0f;
+        int cnt = 0;
+        for (int64_t w = w_lo; w <= w_hi + (tail && f >= n - T ? 1 : 0); ++w) {
+            const int64_t start = w > w_hi ? n - T : w * stride;
+            const int64_t L = n - start < T ? n - start : T;
+            int64_t t = lift_clamp(f - start, 0, T - 1);
+            if (L < T) {
+                const int64_t ft = first_pos[(int64_t)p * T + t];
+                t = ft < 0 ? 0 : (ft >= T ? T - 1 : ft);
+            }
+            const int64_t o = lift_clamp(wb + (w > w_hi ? W - 1 : w), 0, windows - 1) * clip_floats + t * 51;
+            float v = pred[o + q];
+            if (flip) {
+                const float fv = pred[windows * clip_floats + o + 3 * c_lift_flip_src[j] + c];
+                v = (v + (c == 0 ? -fv : fv)) / 2;
+            }
+            acc += v;
+            ++cnt;
+        }
+        out[i] = acc / (float)cnt;
+    }
+}
+
 inline unsigned grid_for(int64_t n) {
     int64_t g = (n + 255) / 256;
     return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
@@ -110,4 +200,19 @@ void kasf_launch_lift_stitch(hipStream_t s, const float* pred, int flip, int P, 
     const int64_t total = (int64_t)P * n * 51;
     if (total <= 0 || W <= 0) return;
     hipLaunchKernelGGL(k_lift_stitch, dim3(grid_for(total)), dim3(256), 0, s, pred, flip, n, W, T, stride, first_pos, (int64_t)P * W, total, out);
+}
+
+void kasf_launch_lift_windows_ragged(hipStream_t s, const float* track, int64_t frames, const int64_t* offsets, const int64_t* win_first, int P,
+                                     int64_t windows, const float* width, const float* height, int T, int stride, const int* resample, int flip, float* x) {
+    const int64_t total = (flip ? 2 : 1) * windows * T * 51;
+    if (total <= 0 || P <= 0 || frames <= 0) return;
+    hipLaunchKernelGGL(k_lift_windows_ragged, dim3(grid_for(total)), dim3(256), 0, s, track, frames, offsets, win_first, P, windows, width, height, T, stride,
+                       resample, total, x);
+}
+
+void kasf_launch_lift_stitch_ragged(hipStream_t s, const float* pred, int flip, int64_t windows, const int64_t* offsets, const int64_t* win_first, int P,
+                                    int64_t frames, int T, int stride, const int* first_pos, float* out) {
+    const int64_t total = frames * 51;
+    if (total <= 0 || P <= 0 || windows <= 0) return;
+    hipLaunchKernelGGL(k_lift_stitch_ragged, dim3(grid_for(total)), dim3(256), 0, s, pred, flip, windows, offsets, win_first, P, T, stride, first_pos, total, out);
 }

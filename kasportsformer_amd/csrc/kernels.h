@@ -175,6 +175,11 @@ inline int64_t kasf_lift_window_count_of(int64_t n, int T, int stride) {
 void kasf_launch_lift_windows(hipStream_t s, const float* track, int P, int64_t n, float width, float height, int T, int stride, const int* resample, int flip,
                               float* x);
 void kasf_launch_lift_stitch(hipStream_t s, const float* pred, int flip, int P, int64_t n, int T, int stride, const int* first_pos, float* out);
+// P tracks packed back to back: track p = rows [offsets[p], offsets[p+1]) of [frames,17,3], windows [win_first[p], win_first[p+1]) of the call
+void kasf_launch_lift_windows_ragged(hipStream_t s, const float* track, int64_t frames, const int64_t* offsets, const int64_t* win_first, int P,
+                                     int64_t windows, const float* width, const float* height, int T, int stride, const int* resample, int flip, float* x);
+void kasf_launch_lift_stitch_ragged(hipStream_t s, const float* pred, int flip, int64_t windows, const int64_t* offsets, const int64_t* win_first, int P,
+                                    int64_t frames, int T, int stride, const int* first_pos, float* out);
 
 // ---- k_gemm2.hip (bf16, persistent, register-resident weights) ----
 // bf16 partial tiles a fused data + weight gradient launch left: out[e] += sum over z < nparts of part[z][e], e < elems (elems a multiple of 128)

@@ -1,6 +1,7 @@
 """Lifting a 2-D keypoint track to 3-D poses on the GPU: the demo's stage 2 (demo/demo.py:194-254, ``lift_3d_pose``) without the detectors.
 
     poses = lift_track(model, keypoints, width, height)          # keypoints [N,17,3] or [P,N,17,3] pixels + confidence -> [..., 17, 3]
+    poses = lift_tracks(model, [kp_0, kp_1, ...], width, height) # tracks [N_i,17,3] of different lengths -> a list of [N_i,17,3], one batch
 
 The demo cuts the track into T-frame clips (``turn_into_clips`` / ``resample``, demo.py:132-156), normalises them
 (``normalize_screen_coordinates``, demo/lib/utils.py:16-20), runs two forwards per clip (plain and ``flip_data``-mirrored), averages the
@@ -10,6 +11,9 @@ puts the frames back on the track (``kasf_lift_stitch``).  Two demo bugs are not
 (demo.py:227: both forwards see the mirrored clip), and ``turn_into_clips`` raises ``UnboundLocalError`` when N > T and N % T == 0.
 
 ``stride < T`` selects overlapping windows (not in the demo): each frame is the mean over the windows that cover it.
+
+``lift_tracks`` takes tracks of different lengths (one per tracked player): each is cut by its own plan, the windows of all of them go through
+the forward together (``kasf_lift_windows_ragged`` / ``kasf_lift_stitch_ragged``), and each track gets what ``lift_track`` gives it alone.
 
     python -m kasportsformer_amd.lift --config X.yaml --checkpoint best.pth --keypoints keypoints2d.pkl --width 1280 --height 720 --out poses3d.npy
 """
@@ -60,32 +64,56 @@ def window_plan(n: int, T: int, stride: int | None = None):
     return starts, lengths, resample, first_pos
 
 
+def ragged_plan(lengths, T: int, stride: int | None = None):
+    """The window plans of many tracks, ``window_plan`` track by track: ``(win_first [P+1] int64, resample [P,T] int32, first_pos [P,T] int32)``.
+    Track p owns windows ``win_first[p] .. win_first[p+1] - 1`` of the call; rows p of ``resample`` / ``first_pos`` hold its tables (``first_pos``
+    in the first L entries) when its plan has a resampled window, and zeros, which the kernels never read, otherwise."""
+    window_plan(0, T, stride)                               # refuses a bad T or stride even without tracks
+    lengths = [int(n) for n in lengths]
+    win_first = np.zeros(len(lengths) + 1, np.int64)
+    resample = np.zeros((len(lengths), T), np.int32)
+    first_pos = np.zeros((len(lengths), T), np.int32)
+    plans = {}
+    for p, n in enumerate(lengths):
+        if n not in plans:
+            plans[n] = window_plan(n, T, stride)
+        starts, _, r, fp = plans[n]
+        win_first[p + 1] = win_first[p] + len(starts)
+        if r is not None:
+            resample[p], first_pos[p, :len(fp)] = r, fp
+    return win_first, resample, first_pos
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _model_device(model) -> torch.device:
+def _model_device(model, who: str = "lift_track") -> torch.device:
     dev = model._flat.device
     if dev.type != "cuda":
-        raise RuntimeError("lift_track: the model must be on the GPU (model.cuda()); kasportsformer_amd has no CPU path")
+        raise RuntimeError(f"{who}: the model must be on the GPU (model.cuda()); kasportsformer_amd has no CPU path")
     return dev
 
 
-def _track(keypoints, device) -> torch.Tensor:
+def _as_tensor(keypoints, device, who: str) -> torch.Tensor:
+    """float32 keypoints as a tensor on the host or on ``device``, not moved (a numpy array is shared, not copied)."""
     if isinstance(keypoints, np.ndarray):
         if keypoints.dtype != np.float32:
-            raise TypeError(f"lift_track: keypoints must be float32, got {keypoints.dtype}")
-        kp = torch.from_numpy(np.ascontiguousarray(keypoints))
-    elif isinstance(keypoints, torch.Tensor):
+            raise TypeError(f"{who}: keypoints must be float32, got {keypoints.dtype}")
+        return torch.from_numpy(np.ascontiguousarray(keypoints))
+    if isinstance(keypoints, torch.Tensor):
         if keypoints.dtype != torch.float32:
-            raise TypeError(f"lift_track: keypoints must be float32, got {keypoints.dtype}")
+            raise TypeError(f"{who}: keypoints must be float32, got {keypoints.dtype}")
         if keypoints.is_cuda and keypoints.device != device:
-            raise RuntimeError(f"lift_track: keypoints are on {keypoints.device}, the model on {device}")
+            raise RuntimeError(f"{who}: keypoints are on {keypoints.device}, the model on {device}")
         if not keypoints.is_cuda and keypoints.device.type != "cpu":
-            raise RuntimeError(f"lift_track: keypoints on unsupported device {keypoints.device}")
-        kp = keypoints.detach()
-    else:
-        raise TypeError(f"lift_track: keypoints must be a numpy array or a torch tensor, got {type(keypoints).__name__}")
+            raise RuntimeError(f"{who}: keypoints on unsupported device {keypoints.device}")
+        return keypoints.detach()
+    raise TypeError(f"{who}: keypoints must be a numpy array or a torch tensor, got {type(keypoints).__name__}")
+
+
+def _track(keypoints, device) -> torch.Tensor:
+    kp = _as_tensor(keypoints, device, "lift_track")
     if kp.dim() not in (3, 4) or tuple(kp.shape[-2:]) != (17, 3):
         raise ValueError(f"lift_track: expected keypoints [N,17,3] or [P,N,17,3], got {tuple(kp.shape)}")
     return kp.to(device).contiguous()            # a copy when it comes from the host; on the device the kernels only read it
@@ -145,6 +173,120 @@ def lift_track(model, keypoints, width, height, *, stride=None, flip: bool = Tru
     return poses.view(lead + (17, 3))
 
 
+def _per_track(value, P: int, name: str) -> np.ndarray:
+    """``width`` / ``height``: one value for every track or one per track -> float32 [P] (what the C entry points receive)."""
+    v = np.asarray(value.detach().cpu() if isinstance(value, torch.Tensor) else value, dtype=np.float64)
+    if v.ndim == 0:
+        v = np.full(P, v)
+    elif v.shape != (P,):
+        raise ValueError(f"lift_tracks: {name} must be one value or one per track ({P}), got shape {v.shape}")
+    v = v.astype(np.float32)
+    if not np.all(v > 0):
+        raise ValueError("lift_tracks: width and height must be positive")
+    return v
+
+
+_TORCH_DTYPE = {np.dtype(np.int64): torch.int64, np.dtype(np.int32): torch.int32, np.dtype(np.float32): torch.float32}
+
+
+def _upload(device, *arrays):
+    """Small host arrays in one host-to-device copy: a device tensor per array (views of one buffer at 8-byte aligned offsets)."""
+    at = np.cumsum([0] + [(a.nbytes + 7) // 8 * 8 for a in arrays])
+    buf = np.zeros(int(at[-1]), np.uint8)
+    for a, o in zip(arrays, at):
+        buf[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    dev = torch.from_numpy(buf).to(device)
+    return [dev[o:o + a.nbytes].view(_TORCH_DTYPE[a.dtype]).view(a.shape) for a, o in zip(arrays, at)]
+
+
+def _forward_windows(model, x, windows: int, halves: int, max_windows: int) -> torch.Tensor:
+    """The eval-mode forward of stacked windows x [halves * windows, T, 17, 3] (plain half, then mirrored): one batch, or chunks of at most
+    ``max_windows`` windows in window order with both halves of a chunk in one forward; ``model.training`` is restored."""
+    was_training = model.training
+    model.eval()
+    try:
+        if windows <= max_windows:
+            return model(x)
+        pred = torch.empty_like(x)
+        for a in range(0, windows, max_windows):
+            b = min(a + max_windows, windows)
+            idx = [slice(h * windows + a, h * windows + b) for h in range(halves)]
+            out = model(torch.cat([x[i] for i in idx]) if halves == 2 else x[idx[0]])
+            for h, i in enumerate(idx):
+                pred[i].copy_(out[h * (b - a):(h + 1) * (b - a)])
+        return pred
+    finally:
+        model.train(was_training)
+
+
+def lift_tracks(model, tracks, width, height, *, stride=None, flip: bool = True, max_windows: int = 1024, offsets=None):
+    """3-D poses of many 2-D keypoint tracks of different lengths in one batched lift: ``tracks`` a sequence of [N_i,17,3] float32 arrays
+    (numpy or torch, CPU or on the model's GPU, any N_i >= 0, never modified) -> a list of CUDA fp32 [N_i,17,3] tensors, views of one packed
+    result.  With ``offsets`` (integers [P+1]: 0, non-decreasing, ending at the packed length), ``tracks`` is one packed [sum N_i,17,3] array,
+    track i its rows offsets[i] .. offsets[i+1] - 1, and the result is one packed tensor too.  ``width`` / ``height``: one value, or one per
+    track (cameras of different resolutions).
+
+    Each track is cut by its own plan (``window_plan``; ``stride`` as in ``lift_track``), and the windows of all tracks run through the forward
+    together: one stacked batch, or chunks of at most ``max_windows`` windows in track order (a chunk may split a track).  Track i's poses are
+    ``lift_track(model, tracks[i], ...)``'s -- bit for bit in fp32, where an eval forward computes every clip alone.  Eval mode without
+    autograd; ``model.training`` is restored afterwards.  Bad shapes, dtypes, devices, strides and resolution counts raise before any kernel runs."""
+    device = _model_device(model, "lift_tracks")
+    T = int(model.n_frames)
+    stride = T if stride is None else int(stride)
+    if not 1 <= stride <= T:
+        raise ValueError(f"lift_tracks: stride must be in [1, T={T}], got {stride}")
+    if int(max_windows) < 1:
+        raise ValueError("lift_tracks: max_windows must be >= 1")
+    if offsets is None:
+        parts = [_as_tensor(a, device, "lift_tracks") for a in tracks]
+        for a in parts:
+            if a.dim() != 3 or tuple(a.shape[1:]) != (17, 3):
+                raise ValueError(f"lift_tracks: expected tracks of [N,17,3], got {tuple(a.shape)}")
+        off = np.cumsum([0] + [a.shape[0] for a in parts], dtype=np.int64)
+    else:
+        packed = _as_tensor(tracks, device, "lift_tracks")
+        if packed.dim() != 3 or tuple(packed.shape[1:]) != (17, 3):
+            raise ValueError(f"lift_tracks: expected packed tracks [sum N_i,17,3], got {tuple(packed.shape)}")
+        off = np.asarray(offsets.detach().cpu() if isinstance(offsets, torch.Tensor) else offsets)
+        if (off.ndim != 1 or off.size < 1 or off.dtype.kind not in "iu" or off[0] != 0 or np.any(np.diff(off) < 0)
+                or off[-1] != packed.shape[0]):
+            raise ValueError(f"lift_tracks: offsets must be integers [P+1] from 0 up to the packed length {packed.shape[0]}, non-decreasing")
+        off = off.astype(np.int64)
+    P = len(off) - 1
+    w32, h32 = _per_track(width, P, "width"), _per_track(height, P, "height")
+    lengths = np.diff(off)
+    win_first, resample, first_pos = ragged_plan(lengths, T, stride)
+    frames, windows = int(off[-1]), int(win_first[-1])
+    lib = _lib.load()
+    c_first = np.empty(P + 1, np.int64)
+    if (lib.kasf_lift_ragged_plan(lengths.ctypes.data, P, T, stride, c_first.ctypes.data) != windows
+            or not np.array_equal(c_first, win_first)):
+        raise _lib.KasfError("lift_tracks: the library's window plan disagrees with ragged_plan (stale build?)")
+    if offsets is None:
+        if P == 0:
+            return []
+        if any(a.is_cuda for a in parts):
+            packed = torch.cat([a.to(device) for a in parts])
+        else:
+            packed = torch.cat(parts).to(device)                  # packed on the host, one upload
+    else:
+        packed = packed.to(device).contiguous()
+    poses = torch.empty((frames, 17, 3), dtype=torch.float32, device=device)
+    if windows > 0:
+        off_d, wf_d, w_d, h_d, r_d, fp_d = _upload(device, off, win_first, w32, h32, resample, first_pos)
+        halves = 2 if flip else 1
+        with torch.no_grad():
+            x = torch.empty((halves * windows, T, 17, 3), dtype=torch.float32, device=device)
+            _lib.check(lib.kasf_lift_windows_ragged(packed.data_ptr(), off_d.data_ptr(), wf_d.data_ptr(), P, frames, windows, w_d.data_ptr(),
+                                                    h_d.data_ptr(), T, stride, r_d.data_ptr(), int(flip), x.data_ptr(), _stream()))
+            pred = _forward_windows(model, x, windows, halves, int(max_windows))
+            _lib.check(lib.kasf_lift_stitch_ragged(pred.data_ptr(), int(flip), off_d.data_ptr(), wf_d.data_ptr(), P, frames, windows, T, stride,
+                                                   fp_d.data_ptr(), poses.data_ptr(), _stream()))
+    if offsets is not None:
+        return poses
+    return [poses[a:b] for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
+
+
 class _KeypointUnpickler(pickle.Unpickler):
     """``keypoints2d.pkl`` (the demo's ``detect_2d_pose`` output) holds one numpy array: only the globals an ndarray pickle names may be loaded
     (numpy 1.x and 2.x module paths, protocols 2-5).  Any other global -- a numpy function included -- is refused before it can be called."""
@@ -161,30 +303,43 @@ class _KeypointUnpickler(pickle.Unpickler):
         raise pickle.UnpicklingError(f"keypoint file references {module}.{name}: only the globals of a numpy array pickle are allowed")
 
 
-def load_keypoints(path: str) -> np.ndarray:
-    """[P,N,17,3] (or [N,17,3]) float32 keypoints from a ``.npy`` file (no pickles) or a ``.pkl`` file of numpy arrays only."""
+def _numeric(kp, what) -> np.ndarray:
+    if not isinstance(kp, np.ndarray) or kp.dtype.hasobject:
+        raise TypeError(f"{what}: expected a numeric numpy array, got {type(kp).__name__} {getattr(kp, 'dtype', '')}")
+    return np.ascontiguousarray(kp, dtype=np.float32)
+
+
+def load_keypoints(path: str):
+    """[P,N,17,3] (or [N,17,3]) float32 keypoints from a ``.npy`` file (no pickles) or a ``.pkl`` file of numpy arrays only.  Tracks of
+    different lengths -- a ``.npz`` (its arrays in file order; no pickles) or a ``.pkl`` holding a list or tuple of arrays (lists and tuples
+    are pickle opcodes, not globals: the unpickler admits nothing new) -- come back as a list of float32 arrays."""
     if str(path).endswith(".npy"):
         kp = np.load(path, allow_pickle=False)
+    elif str(path).endswith(".npz"):
+        with np.load(path, allow_pickle=False) as z:
+            return [_numeric(z[k], f"{path}:{k}") for k in z.files]
     else:
         with open(path, "rb") as f:
             kp = _KeypointUnpickler(io.BytesIO(f.read())).load()
-    if not isinstance(kp, np.ndarray) or kp.dtype.hasobject:
-        raise TypeError(f"{path}: expected a numeric numpy array, got {type(kp).__name__} {getattr(kp, 'dtype', '')}")
-    return np.ascontiguousarray(kp, dtype=np.float32)
+        if isinstance(kp, (list, tuple)):
+            return [_numeric(a, path) for a in kp]
+    return _numeric(kp, path)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m kasportsformer_amd.lift", description="Lift a 2-D keypoint track to 3-D poses (demo.py stage 2).")
     ap.add_argument("--config", required=True, help="model yaml (configs/*.yaml)")
     ap.add_argument("--checkpoint", required=True, help="checkpoint written by checkpoint_save or the reference's training script")
-    ap.add_argument("--keypoints", required=True, help="keypoints2d.pkl ([P,N,17,3], the demo's detect_2d_pose output) or .npy")
+    ap.add_argument("--keypoints", required=True, help="keypoints2d.pkl ([P,N,17,3], the demo's detect_2d_pose output) or .npy; tracks of different "
+                                                       "lengths: an .npz of [N_i,17,3] arrays (file order) or a .pkl of a list of them")
     ap.add_argument("--width", type=float, required=True, help="frame width in pixels")
     ap.add_argument("--height", type=float, required=True, help="frame height in pixels")
     ap.add_argument("--stride", type=int, default=None, help="window stride (default: T, the demo's clips; < T: overlapping windows averaged)")
     ap.add_argument("--no-flip", action="store_true", help="skip the flip-TTA pair")
     ap.add_argument("--compute-dtype", choices=("bf16", "fp32"), default=None, help="default: the yaml's compute_dtype, else bf16")
     ap.add_argument("--max-windows", type=int, default=1024)
-    ap.add_argument("--out", required=True, help="output .npy of [P,N,17,3] (or [N,17,3]) float32 poses")
+    ap.add_argument("--out", required=True, help="output .npy of [P,N,17,3] (or [N,17,3]) float32 poses; tracks of different lengths: an .npz "
+                                                 "of track_0 ... track_{P-1}")
     args = ap.parse_args(argv)
 
     import yaml
@@ -197,6 +352,11 @@ def main(argv=None):
     model = load_model(cfg).cuda()
     checkpoint_load(args.checkpoint, model)
     keypoints = load_keypoints(args.keypoints)
+    if isinstance(keypoints, list):
+        poses = lift_tracks(model, keypoints, args.width, args.height, stride=args.stride, flip=not args.no_flip, max_windows=args.max_windows)
+        np.savez(args.out, **{f"track_{i}": p.cpu().numpy() for i, p in enumerate(poses)})
+        print(f"lifted {len(keypoints)} tracks ({sum(len(k) for k in keypoints)} frames) -> {args.out}")
+        return
     poses = lift_track(model, keypoints, args.width, args.height, stride=args.stride, flip=not args.no_flip, max_windows=args.max_windows)
     np.save(args.out, poses.cpu().numpy())
     print(f"lifted {keypoints.shape} -> {tuple(poses.shape)}: {args.out}")
