@@ -25,6 +25,8 @@
  *   kasf_lift_windows      <- turn_into_clips + normalize_screen_coordinates + flip_data  demo/demo.py:132-156,222-227, demo/lib/utils.py:5-20
  *   kasf_lift_stitch       <- flip-TTA average + root zeroing + downsample of the tail clip  demo/demo.py:229-236
  *   kasf_lift_ragged_plan, kasf_lift_windows_ragged, kasf_lift_stitch_ragged <- the same three over many tracks of different lengths in one batch
+ *   kasf_stream_tables, kasf_stream_push, kasf_stream_windows, kasf_stream_emit <- the same lift one frame at a time: per-player history on the device,
+ *                             its last T frames (fewer: the demo's one resampled clip) lifted every tick            demo/demo.py:132-156,222-236
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
  */
 #ifndef KASF_H_
@@ -210,6 +212,36 @@ int kasf_lift_windows_ragged(const float* packed, const int64_t* offsets, const 
  * table is clamped into the arrays those sizes describe: an inconsistent table gives wrong poses, never an access outside the arrays. */
 int kasf_lift_stitch_ragged(const float* pred, int32_t flip, const int64_t* offsets, const int64_t* win_first, int32_t tracks, int64_t frames,
                             int64_t windows, int32_t T, int32_t stride, const int32_t* first_pos, float* out, void* stream);
+
+/* ---- one new frame per tick (ABI 11): the online form of the lift, per-player history that stays on the device ----
+ * A slot holds one player's recent frames: ring [S][T][17][3] fp32 raw pixel keypoints (frame number c of a slot at ring position c % T) and count [S]
+ * int64, the frames pushed since the slot's reset (a reset is zeroing the count entry; the ring needs no clearing).  A slot's current window is its last
+ * L = min(count, T) frames; a window of L < T frames is lifted as the demo lifts a track shorter than one clip (turn_into_clips, demo/demo.py:138-156: the
+ * one clip resampled to T frames), a full one as one clip.  The plans of all L are two host-built tables [T + 1][T] int32, so nothing is planned per tick:
+ * kasf_stream_tables fills row n (1 <= n < T) of resample_tab with demo.py:132-136's resample(n, T) -- clamp(floor((double)t * ((double)n / (double)T)),
+ * 0, n - 1), which is np.linspace(0, n, T, endpoint=False) floored and clipped -- and of first_pos_tab, in its first n entries (zeros after), with the first t of
+ * every frame (demo.py:146-153's downsample, np.unique(r, return_index=True)[1]); row T is the identity 0 .. T - 1 in both, row 0 is zeros.  Host arrays, no
+ * device needed; error 2 (T outside [1, 256], a null pointer) writes nothing. */
+int kasf_stream_tables(int32_t T, int32_t* resample_tab, int32_t* first_pos_tab);
+/* The three device entries share K (slots of this call), S (slots of the state), T and slots [K] int32 (device): distinct ids in [0, S), or NULL for
+ * "slot i for row i", which needs K == S.  Error 2: T outside [1, 256], K or S negative, K > S, NULL slots with 0 < K < S, a required pointer that is
+ * null.  K = 0 does nothing.  ring, count, width, height and the tables are device arrays; only kasf_stream_push writes ring and count.  Every index formed
+ * from a device array (slot id, count, table entry) is clamped into the arrays S and T describe, and a count below 1 is read as 1: an inconsistent state
+ * gives wrong poses, never an access outside the arrays.
+ * kasf_stream_push stores row i of frames [K][17][3] at ring[slot][count[slot] % T], then count[slot] += 1. */
+int kasf_stream_push(const float* frames, const int32_t* slots, int32_t K, int32_t S, int32_t T, float* ring, int64_t* count, void* stream);
+/* x_out [(1 + flip) * K][T][17][3]: clip h * K + i is the current window of slot i of the call, h = 1 the mirrored copy (the stacking of
+ * predict_flip_tta).  Clip frame t of a slot with count k is ring position (k - L + resample_tab[L][t]) % T, normalised with the slot's width[slot] and
+ * height[slot] (device fp32 [S], positive) and mirrored bit for bit as kasf_lift_windows_ragged does it (normalize_screen_coordinates and flip_data,
+ * demo/lib/utils.py:5-20; demo.py:222-227). */
+int kasf_stream_windows(const float* ring, const int64_t* count, const int32_t* slots, int32_t K, int32_t S, int32_t T, const float* width,
+                        const float* height, const int32_t* resample_tab, int32_t flip, float* x_out, void* stream);
+/* out [K][n_out][17][3] from the model's output pred [(1 + flip) * K][T][17][3] in the clip order above: row r of slot i is window frame
+ * j = clamp(L - 1 - back + r, 0, L - 1), read at clip position first_pos_tab[L][j] and merged as kasf_lift_stitch merges a frame of one window
+ * ((pred + joint_flip(pred of the mirrored copy)) / 2, flip = 0: pred alone; root joint zeroed; demo.py:229-236).  back in [0, T - 1], n_out in [0, T]
+ * (0 does nothing).  back = D, n_out = 1 is the pose D frames behind the newest one; back = D - 1, n_out = D the D newest frames at the end of a track. */
+int kasf_stream_emit(const float* pred, int32_t flip, const int64_t* count, const int32_t* slots, int32_t K, int32_t S, int32_t T,
+                     const int32_t* first_pos_tab, int32_t back, int32_t n_out, float* out, void* stream);
 
 /* debugging / tests: locate a named activation inside the workspace (see kasf_ws_name()) */
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags);

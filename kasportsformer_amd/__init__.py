@@ -17,6 +17,8 @@ Public surface mirrors the reference's interface for this path:
   lift_track, window_plan               demo/demo.py:132-156,194-254, demo/lib/utils.py:5-20 (2-D track -> 3-D poses; also
                                         `python -m kasportsformer_amd.lift`)
   lift_tracks                           the same over many tracks of different lengths in one batched call
+  StreamLifter                          the same one frame at a time: per-player history on the device, one pose per player per tick
+                                        (`python -m kasportsformer_amd.lift --online`)
 """
 from .model import (KASportsFormer, load_model, set_single_stream, is_single_stream, set_deterministic, is_deterministic, set_fused_attention_backward,
                     is_fused_attention_backward)
@@ -31,9 +33,10 @@ from .evaluate import joint_flip, predict_flip_tta, clip_metrics, Evaluator, eva
 from .synthetic import synthetic_clips, synthetic_test_extras, teacher_labels, teacher_clips
 from .slicing import slice_source, split_clips, mysplit_clips, resample
 from .lift import lift_track, lift_tracks, window_plan
+from .stream import StreamLifter
 
 __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_stream", "set_deterministic", "is_deterministic", "set_fused_attention_backward", "is_fused_attention_backward", "loss3", "FusedAdamW", "DataParallel", "joint_flip", "predict_flip_tta", "clip_metrics", "Evaluator",
            "evaluate_one_epoch", "PackedClips", "DeviceClipLoader", "pack_clip_directory", "read_clip_file", "shard_indices",
            "checkpoint_save", "checkpoint_load", "strip_module_prefix", "adamw_state_dict", "load_adamw_state_dict", "warmup_lr", "apply_warmup", "ReduceLROnPlateau", "train_one_epoch",
            "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample",
-           "lift_track", "lift_tracks", "window_plan"]
+           "lift_track", "lift_tracks", "window_plan", "StreamLifter"]

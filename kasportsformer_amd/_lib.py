@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("KASF_LIB") or os.path.join(_HERE, "libkasf_hip.so")
 DTYPE_F32, DTYPE_BF16 = 0, 1
 FLAG_TRAIN, FLAG_RETURN_REP, FLAG_KEEP = 1, 2, 4
 EVAL_COLS = 22
-ABI_VERSION = 10         # kasf_version() of the library these prototypes describe (a stale in-tree .so is refused)
+ABI_VERSION = 11        # kasf_version() of the library these prototypes describe (a stale in-tree .so is refused)
 
 
 class KasfConfig(C.Structure):
@@ -72,6 +72,10 @@ SIGNATURES = {
     "kasf_lift_ragged_plan": (_i64, [_vp, _i32, _i32, _i32, _vp]),
     "kasf_lift_windows_ragged": (_i32, [_vp, _vp, _vp, _i32, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp]),
     "kasf_lift_stitch_ragged": (_i32, [_vp, _i32, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "kasf_stream_tables": (_i32, [_i32, _vp, _vp]),
+    "kasf_stream_push": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "kasf_stream_windows": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "kasf_stream_emit": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
     "kasf_ws_entries": (_i32, [_vp, _i32, _i32]),
     "kasf_ws_entry": (_i32, [_vp, _i32, _i32, _i32, C.c_char_p, _i32, _pi64, _pi64, _pi32]),
     "kasf_op_linear": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),

@@ -625,7 +625,7 @@ void kasf_set_fused_attn_bwd(int32_t on) { g_fused_attn_bwd.store(on < 0 ? -1 : 
 int32_t kasf_get_fused_attn_bwd(void) { return fused_attn_bwd_mask(); }
 void kasf_set_deterministic(int32_t on) { kasf_set_single_stream(on); }
 int32_t kasf_get_deterministic(void) { return kasf_get_single_stream(); }
-int kasf_version(void) { return 10; }
+int kasf_version(void) { return 11; }
 
 int kasf_model_create(const kasf_config* cfg, kasf_model** out) {
     if (cfg == nullptr || out == nullptr) return kasf_set_error(2, "null argument");
@@ -1083,6 +1083,57 @@ int kasf_lift_stitch_ragged(const float* pred, int32_t flip, const int64_t* offs
     if (frames == 0) return 0;
     if (!pred || !offsets || !win_first || !first_pos || !out) return kasf_set_error(2, "null pointer argument");
     kasf_launch_lift_stitch_ragged((hipStream_t)stream, pred, flip ? 1 : 0, windows, offsets, win_first, tracks, frames, T, stride, first_pos, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- one new frame per tick (kasf.h, kasf_stream_*) ----
+int kasf_stream_tables(int32_t T, int32_t* resample_tab, int32_t* first_pos_tab) {
+    if (T < 1 || T > 256) return kasf_set_error(2, "stream: T must be in [1, 256]");
+    if (!resample_tab || !first_pos_tab) return kasf_set_error(2, "null pointer argument");
+    for (int64_t i = 0; i < (int64_t)(T + 1) * T; ++i) resample_tab[i] = first_pos_tab[i] = 0;
+    for (int32_t n = 1; n <= T; ++n) {
+        int32_t* r = resample_tab + (int64_t)n * T;
+        int32_t* fp = first_pos_tab + (int64_t)n * T;
+        for (int32_t t = 0; t < T; ++t) {                  // demo.py:132-136: np.linspace(0, n, T, endpoint=False) is t * (n / T) in float64; floor; clip
+            const int64_t v = (int64_t)floor((double)t * ((double)n / (double)T));
+            r[t] = (int32_t)(v < 0 ? 0 : (v > n - 1 ? n - 1 : v));
+        }
+        for (int32_t t = T - 1; t >= 0; --t) fp[r[t]] = t;  // the first t of every frame (demo.py:146-153, np.unique(r, return_index=True)[1])
+    }
+    return 0;
+}
+static const char* stream_error(const void* slots, int32_t K, int32_t S, int32_t T) {
+    if (T < 1 || T > 256) return "stream: T must be in [1, 256]";
+    if (S < 0 || K < 0 || K > S) return "stream: need 0 <= K <= S";
+    if (slots == nullptr && K != 0 && K != S) return "stream: without slot ids the call covers every slot (K == S)";
+    return nullptr;
+}
+int kasf_stream_push(const float* frames, const int32_t* slots, int32_t K, int32_t S, int32_t T, float* ring, int64_t* count, void* stream) {
+    if (const char* e = stream_error(slots, K, S, T)) return kasf_set_error(2, e);
+    if (K == 0) return 0;
+    if (!frames || !ring || !count) return kasf_set_error(2, "null pointer argument");
+    kasf_launch_stream_push((hipStream_t)stream, frames, slots, K, S, T, ring, count);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int kasf_stream_windows(const float* ring, const int64_t* count, const int32_t* slots, int32_t K, int32_t S, int32_t T, const float* width,
+                        const float* height, const int32_t* resample_tab, int32_t flip, float* x_out, void* stream) {
+    if (const char* e = stream_error(slots, K, S, T)) return kasf_set_error(2, e);
+    if (K == 0) return 0;
+    if (!ring || !count || !width || !height || !resample_tab || !x_out) return kasf_set_error(2, "null pointer argument");
+    kasf_launch_stream_windows((hipStream_t)stream, ring, count, slots, K, S, T, width, height, resample_tab, flip ? 1 : 0, x_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int kasf_stream_emit(const float* pred, int32_t flip, const int64_t* count, const int32_t* slots, int32_t K, int32_t S, int32_t T,
+                     const int32_t* first_pos_tab, int32_t back, int32_t n_out, float* out, void* stream) {
+    if (const char* e = stream_error(slots, K, S, T)) return kasf_set_error(2, e);
+    if (back < 0 || back > T - 1) return kasf_set_error(2, "stream: back must be in [0, T - 1]");
+    if (n_out < 0 || n_out > T) return kasf_set_error(2, "stream: n_out must be in [0, T]");
+    if (K == 0 || n_out == 0) return 0;
+    if (!pred || !count || !first_pos_tab || !out) return kasf_set_error(2, "null pointer argument");
+    kasf_launch_stream_emit((hipStream_t)stream, pred, flip ? 1 : 0, count, slots, K, S, T, first_pos_tab, back, n_out, out);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -1,6 +1,7 @@
 // Lifting a 2-D keypoint track to 3-D (demo/demo.py:194-254, lift_3d_pose): cut the track into T-frame windows, normalise and mirror them
 // (demo/lib/utils.py:5-20), and, after the model's forward, merge the flip-TTA pair and put every window's frames back on the track.
-// Both kernels move 51 floats per frame: HBM-bound, one fp32 element per thread, consecutive threads on consecutive output floats.
+// Every kernel here moves 51 floats per frame: HBM-bound, one fp32 element per thread, consecutive threads on consecutive output floats.
+// Three forms: one track layout for all persons, many tracks of different lengths packed back to back, and one new frame per tick (k_stream_*).
 //
 // Window plan (kasportsformer_amd/lift.py window_plan, kasf.h): W windows of T frames over an n-frame track.
 //   stride == T (the demo's turn_into_clips, demo.py:138-156): windows start at 0, T, 2T, ...; a last window of L < T frames is resampled to
@@ -179,6 +180,81 @@ __global__ __launch_bounds__(256) void k_lift_stitch_ragged(const float* __restr
     }
 }
 
+// ---- one new frame per tick (kasf.h, kasf_stream_*): per-slot history that stays on the device ----
+// A slot is one tracked player: ring [S, T, 17, 3] holds the raw pixel keypoints of its last T frames (frame number c at position c % T), count [S] the
+// frames pushed since its reset.  Its current window is the last L = min(count, T) frames; a window of L < T frames is the demo's one resampled clip of an
+// L-frame track.  resample_tab / first_pos_tab [T + 1][T] hold window_plan(L, T)'s tables in row L (row T: the identity), so no plan is made per tick.
+// slots [K] names the slots of a call (NULL: slot i for row i).  As above, every index formed from a device array (slot id, count, table entry) is clamped
+// into the arrays the host sized; a count below 1 is read as 1 (below 0 as 0 where a frame is stored), so no % T sees a negative number.
+
+__device__ inline int64_t stream_slot(const int* __restrict__ slots, int64_t i, int S) { return slots ? lift_clamp(slots[i], 0, S - 1) : lift_clamp(i, 0, S - 1); }
+
+// One workgroup per pushed slot: row i of frames [K, 17, 3] goes to ring[slot][count[slot] % T], then count[slot] += 1.  Every thread reads the count before
+// the barrier, one thread stores the new one after it.  The slots of a call are distinct (the host checks), so no other workgroup touches this slot.
+__global__ __launch_bounds__(256) void k_stream_push(const float* __restrict__ frames, const int* __restrict__ slots, int K, int S, int T,
+                                                     float* __restrict__ ring, int64_t* __restrict__ count) {
+    for (int64_t i = blockIdx.x; i < K; i += gridDim.x) {
+        const int64_t slot = stream_slot(slots, i, S);
+        int64_t k = count[slot];
+        __syncthreads();
+        if (k < 0) k = 0;
+        if (threadIdx.x < 51) ring[(slot * T + k % T) * 51 + threadIdx.x] = frames[i * 51 + threadIdx.x];
+        if (threadIdx.x == 0) count[slot] = k + 1;
+    }
+}
+
+// x [(1+flip) * K, T, 17, 3]: clip h * K + i is the current window of slot i of the call, mirrored when h == 1; k_lift_windows_ragged's arithmetic with the
+// slot's width and height.  Clip frame t is window frame resample_tab[L][t], i.e. ring position (k - L + that) % T.
+__global__ __launch_bounds__(256) void k_stream_windows(const float* __restrict__ ring, const int64_t* __restrict__ count, const int* __restrict__ slots,
+                                                        int64_t K, int S, int T, const float* __restrict__ width, const float* __restrict__ height,
+                                                        const int* __restrict__ resample_tab, int64_t total, float* __restrict__ x) {
+    const int64_t clip_floats = (int64_t)T * 51;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t clip = i / clip_floats, r = i - clip * clip_floats;
+        const int t = (int)(r / 51), q = (int)(r - (int64_t)t * 51), j = q / 3, c = q - 3 * j;
+        const bool mirrored = clip >= K;
+        const int64_t slot = stream_slot(slots, mirrored ? clip - K : clip, S);
+        const int64_t kc = count[slot], k = kc < 1 ? 1 : kc, L = k < T ? k : T;
+        const int64_t f = lift_clamp(resample_tab[L * T + t], 0, L - 1);
+        const int js = mirrored ? c_lift_flip_src[j] : j;
+        float v = ring[(slot * T + (k - L + f) % T) * 51 + 3 * js + c];
+        if (c < 2) {
+            const float wp = width[slot];
+            const float scaled = v / wp * 2.0f;
+            v = (float)((double)scaled - (c == 0 ? 1.0 : (double)height[slot] / (double)wp));
+            if (mirrored && c == 0) v = -v;
+        }
+        x[i] = v;
+    }
+}
+
+// out [K, n_out, 17, 3] from pred [(1+flip) * K, T, 17, 3] in the clip order above: row r of slot i is window frame clamp(L - 1 - back + r, 0, L - 1), read at
+// clip position first_pos_tab[L][that] and merged as k_lift_stitch merges a frame that one window covers.
+__global__ __launch_bounds__(256) void k_stream_emit(const float* __restrict__ pred, int flip, const int64_t* __restrict__ count, const int* __restrict__ slots,
+                                                     int64_t K, int S, int T, const int* __restrict__ first_pos_tab, int back, int n_out, int64_t total,
+                                                     float* __restrict__ out) {
+    const int64_t clip_floats = (int64_t)T * 51;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / 51;
+        const int q = (int)(i - row * 51), j = q / 3, c = q - 3 * j;
+        if (j == 0) {
+            out[i] = 0.0f;
+            continue;
+        }
+        const int64_t g = row / n_out, r = row - g * n_out;
+        const int64_t kc = count[stream_slot(slots, g, S)], k = kc < 1 ? 1 : kc, L = k < T ? k : T;
+        const int64_t jw = lift_clamp(L - 1 - back + r, 0, L - 1);
+        const int64_t t = lift_clamp(first_pos_tab[L * T + jw], 0, T - 1);
+        const int64_t o = g * clip_floats + t * 51;
+        float v = pred[o + q];
+        if (flip) {
+            const float fv = pred[K * clip_floats + o + 3 * c_lift_flip_src[j] + c];
+            v = (v + (c == 0 ? -fv : fv)) / 2;
+        }
+        out[i] = 0.0f + v;                             // k_lift_stitch's sum over the one covering window, divided by 1
+    }
+}
+
 inline unsigned grid_for(int64_t n) {
     int64_t g = (n + 255) / 256;
     return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
@@ -215,4 +291,23 @@ void kasf_launch_lift_stitch_ragged(hipStream_t s, const float* pred, int flip, 
     const int64_t total = frames * 51;
     if (total <= 0 || P <= 0 || windows <= 0) return;
     hipLaunchKernelGGL(k_lift_stitch_ragged, dim3(grid_for(total)), dim3(256), 0, s, pred, flip, windows, offsets, win_first, P, T, stride, first_pos, total, out);
+}
+
+void kasf_launch_stream_push(hipStream_t s, const float* frames, const int* slots, int K, int S, int T, float* ring, int64_t* count) {
+    if (K <= 0 || S <= 0) return;
+    hipLaunchKernelGGL(k_stream_push, dim3(K > 4096 ? 4096 : K), dim3(256), 0, s, frames, slots, K, S, T, ring, count);
+}
+
+void kasf_launch_stream_windows(hipStream_t s, const float* ring, const int64_t* count, const int* slots, int K, int S, int T, const float* width,
+                                const float* height, const int* resample_tab, int flip, float* x) {
+    const int64_t total = (flip ? 2 : 1) * (int64_t)K * T * 51;
+    if (total <= 0 || S <= 0) return;
+    hipLaunchKernelGGL(k_stream_windows, dim3(grid_for(total)), dim3(256), 0, s, ring, count, slots, (int64_t)K, S, T, width, height, resample_tab, total, x);
+}
+
+void kasf_launch_stream_emit(hipStream_t s, const float* pred, int flip, const int64_t* count, const int* slots, int K, int S, int T, const int* first_pos_tab,
+                             int back, int n_out, float* out) {
+    const int64_t total = (int64_t)K * n_out * 51;
+    if (total <= 0 || S <= 0) return;
+    hipLaunchKernelGGL(k_stream_emit, dim3(grid_for(total)), dim3(256), 0, s, pred, flip, count, slots, (int64_t)K, S, T, first_pos_tab, back, n_out, total, out);
 }

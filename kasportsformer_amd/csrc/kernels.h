@@ -180,6 +180,12 @@ void kasf_launch_lift_windows_ragged(hipStream_t s, const float* track, int64_t 
                                      int64_t windows, const float* width, const float* height, int T, int stride, const int* resample, int flip, float* x);
 void kasf_launch_lift_stitch_ragged(hipStream_t s, const float* pred, int flip, int64_t windows, const int64_t* offsets, const int64_t* win_first, int P,
                                     int64_t frames, int T, int stride, const int* first_pos, float* out);
+// one new frame per tick: S slots of ring [S,T,17,3] / count [S], K of them named by slots [K] (NULL: slot i for row i); tables [T+1][T] (kasf.h, kasf_stream_*)
+void kasf_launch_stream_push(hipStream_t s, const float* frames, const int* slots, int K, int S, int T, float* ring, int64_t* count);
+void kasf_launch_stream_windows(hipStream_t s, const float* ring, const int64_t* count, const int* slots, int K, int S, int T, const float* width,
+                                const float* height, const int* resample_tab, int flip, float* x);
+void kasf_launch_stream_emit(hipStream_t s, const float* pred, int flip, const int64_t* count, const int* slots, int K, int S, int T, const int* first_pos_tab,
+                             int back, int n_out, float* out);
 
 // ---- k_gemm2.hip (bf16, persistent, register-resident weights) ----
 // bf16 partial tiles a fused data + weight gradient launch left: out[e] += sum over z < nparts of part[z][e], e < elems (elems a multiple of 128)

@@ -16,6 +16,8 @@ puts the frames back on the track (``kasf_lift_stitch``).  Two demo bugs are not
 the forward together (``kasf_lift_windows_ragged`` / ``kasf_lift_stitch_ragged``), and each track gets what ``lift_track`` gives it alone.
 
     python -m kasportsformer_amd.lift --config X.yaml --checkpoint best.pth --keypoints keypoints2d.pkl --width 1280 --height 720 --out poses3d.npy
+
+``--online [--lag D]`` replays the file tick by tick through ``kasportsformer_amd.stream.StreamLifter`` (the lift of live streams) instead.
 """
 from __future__ import annotations
 
@@ -338,9 +340,16 @@ def main(argv=None):
     ap.add_argument("--no-flip", action="store_true", help="skip the flip-TTA pair")
     ap.add_argument("--compute-dtype", choices=("bf16", "fp32"), default=None, help="default: the yaml's compute_dtype, else bf16")
     ap.add_argument("--max-windows", type=int, default=1024)
+    ap.add_argument("--online", action="store_true", help="replay the track(s) tick by tick through StreamLifter (kasportsformer_amd.stream): frame f "
+                                                          "from the sliding window of the T frames up to f + LAG; not with --stride")
+    ap.add_argument("--lag", type=int, default=0, help="--online: frames of look-ahead, in [0, T - 1] (default 0: every pose from the frames up to its own)")
     ap.add_argument("--out", required=True, help="output .npy of [P,N,17,3] (or [N,17,3]) float32 poses; tracks of different lengths: an .npz "
                                                  "of track_0 ... track_{P-1}")
     args = ap.parse_args(argv)
+    if args.online and args.stride is not None:
+        ap.error("--online lifts the sliding window of every tick: it takes no --stride")
+    if args.lag and not args.online:
+        ap.error("--lag belongs to --online")
 
     import yaml
     from .checkpoint import checkpoint_load
@@ -352,6 +361,17 @@ def main(argv=None):
     model = load_model(cfg).cuda()
     checkpoint_load(args.checkpoint, model)
     keypoints = load_keypoints(args.keypoints)
+    if args.online:
+        from .stream import StreamLifter
+        lifter = StreamLifter(model, args.width, args.height, slots=1, flip=not args.no_flip, lag=args.lag)
+        if isinstance(keypoints, list):
+            np.savez(args.out, **{f"track_{i}": lifter.replay(k).cpu().numpy() for i, k in enumerate(keypoints)})
+            print(f"replayed {len(keypoints)} tracks ({sum(len(k) for k in keypoints)} frames) tick by tick, lag {args.lag} -> {args.out}")
+            return
+        poses = lifter.replay(keypoints)
+        np.save(args.out, poses.cpu().numpy())
+        print(f"replayed {keypoints.shape} tick by tick, lag {args.lag} -> {tuple(poses.shape)}: {args.out}")
+        return
     if isinstance(keypoints, list):
         poses = lift_tracks(model, keypoints, args.width, args.height, stride=args.stride, flip=not args.no_flip, max_windows=args.max_windows)
         np.savez(args.out, **{f"track_{i}": p.cpu().numpy() for i, p in enumerate(poses)})
