@@ -27,6 +27,8 @@
  *   kasf_lift_ragged_plan, kasf_lift_windows_ragged, kasf_lift_stitch_ragged <- the same three over many tracks of different lengths in one batch
  *   kasf_stream_tables, kasf_stream_push, kasf_stream_windows, kasf_stream_emit <- the same lift one frame at a time: per-player history on the device,
  *                             its last T frames (fewer: the demo's one resampled clip) lifted every tick            demo/demo.py:132-156,222-236
+ *   kasf_coco_h36m         <- h36m_coco_format / coco_h36m (COCO-17 detector keypoints -> H36M-17)  demo/lib/preprocess.py:10-69, demo/demo.py:75-78
+ *   kasf_pose_world        <- camera_to_world / qrot, feet on the floor, unit scale                demo/lib/utils.py:55-73, demo/demo.py:242-248
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
  */
 #ifndef KASF_H_
@@ -242,6 +244,23 @@ int kasf_stream_windows(const float* ring, const int64_t* count, const int32_t* 
  * (0 does nothing).  back = D, n_out = 1 is the pose D frames behind the newest one; back = D - 1, n_out = D the D newest frames at the end of a track. */
 int kasf_stream_emit(const float* pred, int32_t flip, const int64_t* count, const int32_t* slots, int32_t K, int32_t S, int32_t T,
                      const int32_t* first_pos_tab, int32_t back, int32_t n_out, float* out, void* stream);
+
+/* ---- the two ends of the lift that the demo does on the host (new symbols of ABI 11; frames of [17][3] fp32 on the device) ----
+ * kasf_coco_h36m: coco [frames][17][3] = pixel x, pixel y, score in COCO joint order (what YOLO-pose, RTMPose, ViTPose and the demo's HRNet emit) ->
+ * h36m [frames][17][3] in the Human3.6M order the model was trained on.  Coordinates as coco_h36m (demo/lib/preprocess.py:10-37, the file the demo
+ * imports: spine factor 2), statement by statement in fp32 -- the neck correction reads the copied nose, the spine x correction the pelvis and the thorax
+ * before the thorax y correction -- and scores as h36m_coco_format (preprocess.py:58-62): bit for bit the reference's values.  Shapes are kept: a frame
+ * of zeros gives a frame of zeros (the reference drops a whole person whose coordinates sum to exactly zero; its valid_frames and the unused
+ * revise_kpts are not reproduced).  coco and h36m must not overlap.  frames = 0 does nothing; error 2 for frames < 0, or a null pointer with frames > 0
+ * (no device needed to refuse). */
+int kasf_coco_h36m(const float* coco, int64_t frames, float* h36m, void* stream);
+/* kasf_pose_world: poses [frames][17][3] camera space (the lift's output) -> out [frames][17][3]: every joint v becomes v + 2 (q0 (q x v) + q x (q x v)) + t
+ * with q = quat4[1..3], in fp32 and in qrot's operation order (demo/lib/utils.py:55-73); with `floor` the frame's smallest z is then subtracted from
+ * its z column (demo.py:246), and with `unit` all 51 values are then divided by their largest (demo.py:247-248; a frame whose largest value is 0 gets
+ * the reference's division by zero, unguarded).  quat4 (w, x, y, z) and trans3 are HOST pointers to 4 and 3 floats, read during the call and passed by
+ * value into the launch; trans3 = NULL means zero (the demo's t = 0).  poses and out must not overlap.  frames = 0 does nothing; error 2 for
+ * frames < 0, or a null poses / quat4 / out with frames > 0 (no device needed to refuse). */
+int kasf_pose_world(const float* poses, int64_t frames, const float* quat4, const float* trans3, int32_t floor, int32_t unit, float* out, void* stream);
 
 /* debugging / tests: locate a named activation inside the workspace (see kasf_ws_name()) */
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags);

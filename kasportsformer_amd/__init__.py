@@ -19,6 +19,9 @@ Public surface mirrors the reference's interface for this path:
   lift_tracks                           the same over many tracks of different lengths in one batched call
   StreamLifter                          the same one frame at a time: per-player history on the device, one pose per player per tick
                                         (`python -m kasportsformer_amd.lift --online`)
+  coco_to_h36m                          demo/lib/preprocess.py:10-69, demo/demo.py:75-78 (COCO-17 detector keypoints -> the H36M-17 layout, on the
+                                        device; `layout="coco"` on the three lifts, `--layout coco`)
+  poses_to_world, DEMO_CAMERA_ROTATION  demo/lib/utils.py:55-73, demo/demo.py:242-248 (camera space -> world space, floor, unit scale; `--world`)
 """
 from .model import (KASportsFormer, load_model, set_single_stream, is_single_stream, set_deterministic, is_deterministic, set_fused_attention_backward,
                     is_fused_attention_backward)
@@ -34,9 +37,10 @@ from .synthetic import synthetic_clips, synthetic_test_extras, teacher_labels, t
 from .slicing import slice_source, split_clips, mysplit_clips, resample
 from .lift import lift_track, lift_tracks, window_plan
 from .stream import StreamLifter
+from .pose import coco_to_h36m, poses_to_world, DEMO_CAMERA_ROTATION
 
 __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_stream", "set_deterministic", "is_deterministic", "set_fused_attention_backward", "is_fused_attention_backward", "loss3", "FusedAdamW", "DataParallel", "joint_flip", "predict_flip_tta", "clip_metrics", "Evaluator",
            "evaluate_one_epoch", "PackedClips", "DeviceClipLoader", "pack_clip_directory", "read_clip_file", "shard_indices",
            "checkpoint_save", "checkpoint_load", "strip_module_prefix", "adamw_state_dict", "load_adamw_state_dict", "warmup_lr", "apply_warmup", "ReduceLROnPlateau", "train_one_epoch",
            "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample",
-           "lift_track", "lift_tracks", "window_plan", "StreamLifter"]
+           "lift_track", "lift_tracks", "window_plan", "StreamLifter", "coco_to_h36m", "poses_to_world", "DEMO_CAMERA_ROTATION"]

@@ -76,6 +76,8 @@ SIGNATURES = {
     "kasf_stream_push": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "kasf_stream_windows": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "kasf_stream_emit": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "kasf_coco_h36m": (_i32, [_vp, _i64, _vp, _vp]),
+    "kasf_pose_world": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "kasf_ws_entries": (_i32, [_vp, _i32, _i32]),
     "kasf_ws_entry": (_i32, [_vp, _i32, _i32, _i32, C.c_char_p, _i32, _pi64, _pi64, _pi32]),
     "kasf_op_linear": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),

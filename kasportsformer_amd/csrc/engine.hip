@@ -1138,6 +1138,25 @@ int kasf_stream_emit(const float* pred, int32_t flip, const int64_t* count, cons
     return 0;
 }
 
+// ---- the two ends of the lift (kasf.h, kasf_coco_h36m / kasf_pose_world) ----
+int kasf_coco_h36m(const float* coco, int64_t frames, float* h36m, void* stream) {
+    if (frames < 0) return kasf_set_error(2, "coco_h36m: frames must be >= 0");
+    if (frames == 0) return 0;
+    if (!coco || !h36m) return kasf_set_error(2, "null pointer argument");
+    kasf_launch_coco_h36m((hipStream_t)stream, coco, frames, h36m);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int kasf_pose_world(const float* poses, int64_t frames, const float* quat4, const float* trans3, int32_t floor, int32_t unit, float* out, void* stream) {
+    if (frames < 0) return kasf_set_error(2, "pose_world: frames must be >= 0");
+    if (frames == 0) return 0;
+    if (!poses || !quat4 || !out) return kasf_set_error(2, "null pointer argument");
+    const float zero[3] = {0.0f, 0.0f, 0.0f};
+    kasf_launch_pose_world((hipStream_t)stream, poses, frames, quat4, trans3 ? trans3 : zero, floor ? 1 : 0, unit ? 1 : 0, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 #define OP_DT_CHECK(dt) \
     if ((dt) != KASF_F32 && (dt) != KASF_BF16) return kasf_set_error(3, "bad dtype")
 

@@ -2,6 +2,8 @@
 // (demo/lib/utils.py:5-20), and, after the model's forward, merge the flip-TTA pair and put every window's frames back on the track.
 // Every kernel here moves 51 floats per frame: HBM-bound, one fp32 element per thread, consecutive threads on consecutive output floats.
 // Three forms: one track layout for all persons, many tracks of different lengths packed back to back, and one new frame per tick (k_stream_*).
+// The tracks are in the H36M-17 joint layout; COCO-17 detector keypoints are converted in front of these kernels, and the poses they give are taken to
+// world space behind them, by k_pose.hip (kasf_coco_h36m / kasf_pose_world).
 //
 // Window plan (kasportsformer_amd/lift.py window_plan, kasf.h): W windows of T frames over an n-frame track.
 //   stride == T (the demo's turn_into_clips, demo.py:138-156): windows start at 0, T, 2T, ...; a last window of L < T frames is resampled to

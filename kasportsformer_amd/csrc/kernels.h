@@ -187,6 +187,11 @@ void kasf_launch_stream_windows(hipStream_t s, const float* ring, const int64_t*
 void kasf_launch_stream_emit(hipStream_t s, const float* pred, int flip, const int64_t* count, const int* slots, int K, int S, int T, const int* first_pos_tab,
                              int back, int n_out, float* out);
 
+// ---- k_pose.hip: the two ends of the lift (kasf.h, kasf_coco_h36m / kasf_pose_world); frames of [17,3] fp32, src and dst distinct arrays ----
+void kasf_launch_coco_h36m(hipStream_t s, const float* coco, int64_t frames, float* h36m);
+// q [4], t [3]: host arrays, passed by value into the launch
+void kasf_launch_pose_world(hipStream_t s, const float* poses, int64_t frames, const float* q, const float* t, int floor, int unit, float* out);
+
 // ---- k_gemm2.hip (bf16, persistent, register-resident weights) ----
 // bf16 partial tiles a fused data + weight gradient launch left: out[e] += sum over z < nparts of part[z][e], e < elems (elems a multiple of 128)
 // ---- persistent launches narrower than the chip (round 4) ----

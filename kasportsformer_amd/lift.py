@@ -18,6 +18,9 @@ the forward together (``kasf_lift_windows_ragged`` / ``kasf_lift_stitch_ragged``
     python -m kasportsformer_amd.lift --config X.yaml --checkpoint best.pth --keypoints keypoints2d.pkl --width 1280 --height 720 --out poses3d.npy
 
 ``--online [--lag D]`` replays the file tick by tick through ``kasportsformer_amd.stream.StreamLifter`` (the lift of live streams) instead.
+
+``layout="coco"`` (``--layout coco``) takes the keypoints as a COCO-17 detector writes them and converts them on the device first
+(``kasportsformer_amd.pose.coco_to_h36m``); ``--world [--world-floor] [--world-unit]`` sends the poses through ``poses_to_world`` before they are written.
 """
 from __future__ import annotations
 
@@ -30,6 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .pose import check_layout, convert_frames, poses_to_world
 
 
 def demo_resample(n_frames: int, target_frame: int) -> np.ndarray:
@@ -121,12 +125,14 @@ def _track(keypoints, device) -> torch.Tensor:
     return kp.to(device).contiguous()            # a copy when it comes from the host; on the device the kernels only read it
 
 
-def lift_track(model, keypoints, width, height, *, stride=None, flip: bool = True, max_windows: int = 1024) -> torch.Tensor:
+def lift_track(model, keypoints, width, height, *, stride=None, flip: bool = True, max_windows: int = 1024, layout: str = "h36m") -> torch.Tensor:
     """3-D poses of a 2-D keypoint track: ``keypoints`` [N,17,3] or [P,N,17,3] float32 (pixel x, y, confidence; numpy or torch, CPU or
     GPU, never modified) -> CUDA fp32 [N,17,3] / [P,N,17,3] in the model's output space with the root joint at zero (the demo's
     ``output_3D`` before ``camera_to_world``).  T is ``model.n_frames``; ``stride`` defaults to T (the demo's clips).  The forward runs in
     eval mode without autograd, the plain and mirrored views of each window in one stacked batch, at most ``max_windows`` windows
-    (2 * ``max_windows`` clips with ``flip``) per call; ``model.training`` is restored afterwards."""
+    (2 * ``max_windows`` clips with ``flip``) per call; ``model.training`` is restored afterwards.  ``layout="coco"``: the keypoints are COCO-17
+    (pixel x, y, score) and go through ``coco_to_h36m`` on the device first; any other value but "h36m" raises ``ValueError``."""
+    coco = check_layout(layout, "lift_track")
     device = _model_device(model)
     kp = _track(keypoints, device)
     lead = tuple(kp.shape[:-2])
@@ -151,6 +157,8 @@ def lift_track(model, keypoints, width, height, *, stride=None, flip: bool = Tru
     fp_dev = torch.from_numpy(first_pos).to(device) if first_pos is not None else None
     halves, PW = (2 if flip else 1), P * W
     with torch.no_grad():
+        if coco:
+            kp4 = convert_frames(kp4)
         x = torch.empty((halves * PW, T, 17, 3), dtype=torch.float32, device=device)
         _lib.check(lib.kasf_lift_windows(kp4.data_ptr(), P, n, float(width), float(height), T, stride,
                                          r_dev.data_ptr() if r_dev is not None else None, int(flip), x.data_ptr(), _stream()))
@@ -221,7 +229,7 @@ def _forward_windows(model, x, windows: int, halves: int, max_windows: int) -> t
         model.train(was_training)
 
 
-def lift_tracks(model, tracks, width, height, *, stride=None, flip: bool = True, max_windows: int = 1024, offsets=None):
+def lift_tracks(model, tracks, width, height, *, stride=None, flip: bool = True, max_windows: int = 1024, offsets=None, layout: str = "h36m"):
     """3-D poses of many 2-D keypoint tracks of different lengths in one batched lift: ``tracks`` a sequence of [N_i,17,3] float32 arrays
     (numpy or torch, CPU or on the model's GPU, any N_i >= 0, never modified) -> a list of CUDA fp32 [N_i,17,3] tensors, views of one packed
     result.  With ``offsets`` (integers [P+1]: 0, non-decreasing, ending at the packed length), ``tracks`` is one packed [sum N_i,17,3] array,
@@ -231,7 +239,9 @@ def lift_tracks(model, tracks, width, height, *, stride=None, flip: bool = True,
     Each track is cut by its own plan (``window_plan``; ``stride`` as in ``lift_track``), and the windows of all tracks run through the forward
     together: one stacked batch, or chunks of at most ``max_windows`` windows in track order (a chunk may split a track).  Track i's poses are
     ``lift_track(model, tracks[i], ...)``'s -- bit for bit in fp32, where an eval forward computes every clip alone.  Eval mode without
-    autograd; ``model.training`` is restored afterwards.  Bad shapes, dtypes, devices, strides and resolution counts raise before any kernel runs."""
+    autograd; ``model.training`` is restored afterwards.  ``layout="coco"``: the tracks are COCO-17 keypoints, converted on the device (one launch over
+    the packed frames) before they are cut.  Bad shapes, dtypes, devices, strides, layouts and resolution counts raise before any kernel runs."""
+    coco = check_layout(layout, "lift_tracks")
     device = _model_device(model, "lift_tracks")
     T = int(model.n_frames)
     stride = T if stride is None else int(stride)
@@ -278,6 +288,8 @@ def lift_tracks(model, tracks, width, height, *, stride=None, flip: bool = True,
         off_d, wf_d, w_d, h_d, r_d, fp_d = _upload(device, off, win_first, w32, h32, resample, first_pos)
         halves = 2 if flip else 1
         with torch.no_grad():
+            if coco:
+                packed = convert_frames(packed)
             x = torch.empty((halves * windows, T, 17, 3), dtype=torch.float32, device=device)
             _lib.check(lib.kasf_lift_windows_ragged(packed.data_ptr(), off_d.data_ptr(), wf_d.data_ptr(), P, frames, windows, w_d.data_ptr(),
                                                     h_d.data_ptr(), T, stride, r_d.data_ptr(), int(flip), x.data_ptr(), _stream()))
@@ -328,7 +340,8 @@ def load_keypoints(path: str):
     return _numeric(kp, path)
 
 
-def main(argv=None):
+def _parse(argv=None):
+    """The command line of ``python -m kasportsformer_amd.lift`` (no device needed)."""
     ap = argparse.ArgumentParser(prog="python -m kasportsformer_amd.lift", description="Lift a 2-D keypoint track to 3-D poses (demo.py stage 2).")
     ap.add_argument("--config", required=True, help="model yaml (configs/*.yaml)")
     ap.add_argument("--checkpoint", required=True, help="checkpoint written by checkpoint_save or the reference's training script")
@@ -343,6 +356,11 @@ def main(argv=None):
     ap.add_argument("--online", action="store_true", help="replay the track(s) tick by tick through StreamLifter (kasportsformer_amd.stream): frame f "
                                                           "from the sliding window of the T frames up to f + LAG; not with --stride")
     ap.add_argument("--lag", type=int, default=0, help="--online: frames of look-ahead, in [0, T - 1] (default 0: every pose from the frames up to its own)")
+    ap.add_argument("--layout", choices=("h36m", "coco"), default="h36m", help="joint layout of the keypoints: h36m (default; the demo's keypoints2d.pkl) or "
+                                                                               "coco (COCO-17 x, y, score as a detector writes them: converted on the device)")
+    ap.add_argument("--world", action="store_true", help="write world-space poses: the demo's camera_to_world rotation (demo.py:243-245)")
+    ap.add_argument("--world-floor", action="store_true", help="--world: put each frame's lowest joint at z = 0 (demo.py:246)")
+    ap.add_argument("--world-unit", action="store_true", help="--world: divide each frame by its largest value (demo.py:247-248), after --world-floor")
     ap.add_argument("--out", required=True, help="output .npy of [P,N,17,3] (or [N,17,3]) float32 poses; tracks of different lengths: an .npz "
                                                  "of track_0 ... track_{P-1}")
     args = ap.parse_args(argv)
@@ -350,6 +368,13 @@ def main(argv=None):
         ap.error("--online lifts the sliding window of every tick: it takes no --stride")
     if args.lag and not args.online:
         ap.error("--lag belongs to --online")
+    if (args.world_floor or args.world_unit) and not args.world:
+        ap.error("--world-floor and --world-unit belong to --world")
+    return args
+
+
+def main(argv=None):
+    args = _parse(argv)
 
     import yaml
     from .checkpoint import checkpoint_load
@@ -361,23 +386,29 @@ def main(argv=None):
     model = load_model(cfg).cuda()
     checkpoint_load(args.checkpoint, model)
     keypoints = load_keypoints(args.keypoints)
+
+    def final(poses):
+        return poses_to_world(poses, floor=args.world_floor, unit=args.world_unit) if args.world else poses
+
     if args.online:
         from .stream import StreamLifter
-        lifter = StreamLifter(model, args.width, args.height, slots=1, flip=not args.no_flip, lag=args.lag)
+        lifter = StreamLifter(model, args.width, args.height, slots=1, flip=not args.no_flip, lag=args.lag, layout=args.layout)
         if isinstance(keypoints, list):
-            np.savez(args.out, **{f"track_{i}": lifter.replay(k).cpu().numpy() for i, k in enumerate(keypoints)})
+            np.savez(args.out, **{f"track_{i}": final(lifter.replay(k)).cpu().numpy() for i, k in enumerate(keypoints)})
             print(f"replayed {len(keypoints)} tracks ({sum(len(k) for k in keypoints)} frames) tick by tick, lag {args.lag} -> {args.out}")
             return
-        poses = lifter.replay(keypoints)
+        poses = final(lifter.replay(keypoints))
         np.save(args.out, poses.cpu().numpy())
         print(f"replayed {keypoints.shape} tick by tick, lag {args.lag} -> {tuple(poses.shape)}: {args.out}")
         return
     if isinstance(keypoints, list):
-        poses = lift_tracks(model, keypoints, args.width, args.height, stride=args.stride, flip=not args.no_flip, max_windows=args.max_windows)
-        np.savez(args.out, **{f"track_{i}": p.cpu().numpy() for i, p in enumerate(poses)})
+        poses = lift_tracks(model, keypoints, args.width, args.height, stride=args.stride, flip=not args.no_flip, max_windows=args.max_windows,
+                            layout=args.layout)
+        np.savez(args.out, **{f"track_{i}": final(p).cpu().numpy() for i, p in enumerate(poses)})
         print(f"lifted {len(keypoints)} tracks ({sum(len(k) for k in keypoints)} frames) -> {args.out}")
         return
-    poses = lift_track(model, keypoints, args.width, args.height, stride=args.stride, flip=not args.no_flip, max_windows=args.max_windows)
+    poses = final(lift_track(model, keypoints, args.width, args.height, stride=args.stride, flip=not args.no_flip, max_windows=args.max_windows,
+                             layout=args.layout))
     np.save(args.out, poses.cpu().numpy())
     print(f"lifted {keypoints.shape} -> {tuple(poses.shape)}: {args.out}")
 

@@ -1,6 +1,6 @@
 """Lifting live keypoint streams frame by frame: the online form of ``lift_track`` / ``lift_tracks`` (demo/demo.py:194-254, ``lift_3d_pose``).
 
-    lifter = StreamLifter(model, width, height, slots=32, flip=True, lag=0)      # width / height: one value or one per slot
+    lifter = StreamLifter(model, width, height, slots=32, flip=True, lag=0)      # width / height: one value or one per slot; layout="coco": COCO-17 frames in
     poses = lifter.push(kp)                     # kp [slots,17,3] fp32 pixels + confidence, one new frame for every slot -> CUDA fp32 [slots,17,3]
     poses = lifter.push(kp, slots=[3, 7, 8])    # kp [3,17,3]: only these slots got a frame this tick -> [3,17,3]
     rest = lifter.tail(slots=[3])               # [1,lag,17,3]: the frames push has not emitted yet, at the end of a track
@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .pose import check_layout, convert_frames
 from .lift import _as_tensor, _forward_windows, _model_device, _stream, _upload, window_plan
 
 
@@ -52,9 +53,12 @@ def _per_slot(value, S: int, name: str) -> np.ndarray:
 
 class StreamLifter:
     """Per-player lifting state on the model's device; see the module docstring.  ``counts`` (host int64 [slots]) mirrors the device's frame counts and is
-    what validates calls: every refusal is raised before any kernel runs and leaves the state as it was.  Inputs are never modified."""
+    what validates calls: every refusal is raised before any kernel runs and leaves the state as it was.  Inputs are never modified.
+    ``layout="coco"``: every frame pushed (``replay``'s tracks included) is COCO-17 pixel x, y, score and goes through ``coco_to_h36m`` on the device
+    before it is stored, one more launch per tick: the ring holds H36M frames, and the window and emit kernels see nothing new."""
 
-    def __init__(self, model, width, height, slots: int = 32, flip: bool = True, lag: int = 0, _tables=None):
+    def __init__(self, model, width, height, slots: int = 32, flip: bool = True, lag: int = 0, layout: str = "h36m", _tables=None):
+        self.layout, self._coco = layout, check_layout(layout, "StreamLifter")
         self.device = _model_device(model, "StreamLifter")
         self.model, self.flip = model, bool(flip)
         self.T = T = int(model.n_frames)
@@ -132,6 +136,8 @@ class StreamLifter:
         frames = kp.to(self.device).contiguous()               # a copy when it comes from the host; on the device the kernel only reads it
         ids_d = torch.from_numpy(ids).to(self.device) if ids is not None else None
         with torch.no_grad():
+            if self._coco:
+                frames = convert_frames(frames)
             _lib.check(self._lib.kasf_stream_push(frames.data_ptr(), ids_d.data_ptr() if ids_d is not None else None, K, self.slots, self.T,
                                                   self._ring.data_ptr(), self._count.data_ptr(), _stream()))
             if ids is None:
@@ -185,7 +191,7 @@ class StreamLifter:
             if P > 0:
                 _per_slot(width, P, "width"), _per_slot(height, P, "height")
             return out.view(lead + (17, 3))
-        temp = StreamLifter(self.model, width, height, slots=P, flip=self.flip, lag=lag, _tables=self._tables)
+        temp = StreamLifter(self.model, width, height, slots=P, flip=self.flip, lag=lag, layout=self.layout, _tables=self._tables)
         ticks = kp4.to(self.device).transpose(0, 1).contiguous()   # [N,P,17,3]: one upload, every tick reads its frame in place
         for f in range(N):
             pose = temp.push(ticks[f])
