@@ -30,6 +30,7 @@
  *   kasf_coco_h36m         <- h36m_coco_format / coco_h36m (COCO-17 detector keypoints -> H36M-17)  demo/lib/preprocess.py:10-69, demo/demo.py:75-78
  *   kasf_pose_world        <- camera_to_world / qrot, feet on the floor, unit scale                demo/lib/utils.py:55-73, demo/demo.py:242-248
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
+ *   kasf_op_gcn_fwd, kasf_op_gcn_bwd <- GCN.forward between its U | V Linear and the residual, and autograd of it   model/modules/graph.py:19-134, KASportsFormer.py:109
  */
 #ifndef KASF_H_
 #define KASF_H_
@@ -320,6 +321,38 @@ int kasf_op_attention_bwd_heads(int32_t dtype, const void* q, int64_t ldq, const
 int kasf_op_attention_bwd_fused_do(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* g_mid, const void* wproj_t_scaled,
                                    void* dq, int64_t lddq, void* dk, void* dv, int64_t lddkv, int32_t batch, int32_t n_frames, int32_t mode, int32_t form,
                                    const void* o_saved, const float* lse, void* stream);
+/* ---- the GCN mixer on its own (ABI 12; modules/graph.py:19-134 between the U | V Linear and the residual of KASportsFormer.py:109) ----
+ * M = batch * n_frames * 17 tokens in [batch][frame][joint] order.  mode 0 = spatial (fixed skeleton adjacency, BatchNorm channel = joint, 17 nodes), 1 = temporal
+ * (per (clip, joint) track: S = xn xn^T, every frame whose similarity reaches the neighbour_num-th largest of its row is a neighbour -- ties are all kept, so a row's
+ * degree may exceed neighbour_num --, BatchNorm channel = frame, n_frames nodes).  Both entries run the engine's own launches with the engine's own
+ * count = batch * n_frames * 128 (spatial) or batch * 17 * 128 (temporal) values per node.
+ *   y    = D^-1/2 A D^-1/2 . V + U          uv [M,256] = U | V of xn, bias included (kasf_op_linear with N = 256)
+ *   out  = x_in + ls1 * relu(xn + BN(y))    xn [M,128] = LN(x_in), as kasf_op_linear's xn_out leaves it
+ * training != 0: BatchNorm on the batch mean and biased variance of y AS STORED (rounded to the model dtype), and run_mean / run_var become (1 - momentum) * old +
+ * momentum * (mean, unbiased variance); training == 0: BatchNorm on run_mean / run_var, which are not written.  mask [batch * 17][n_frames][MW] uint32 receives the
+ * temporal adjacency (bit c of word c >> 5 of row r = "frame c is a neighbour of frame r"; MW = 3 up to 96 frames, ceil(n_frames / 32) beyond; NULL in spatial mode).
+ * coef [256][8] fp32 receives per node: scale, shift, mean, rstd (4 more floats of scratch).
+ * stats / bstats: ONE statistics buffer each, KASF_GCN_STAT_WORDS int64 words, zeroed by the entry itself (hipMemsetAsync on `stream`, as kasf_forward does) and
+ * left readable.  Layout [4 slots][512 statistics][5 words]: statistic 2 n of node n is the sum of y (bstats: of r), statistic 2 n + 1 the sum of y^2 (bstats: of
+ * r . (y - mean) . rstd).  Words 0..3 are SIGNED counts of units 2^(-110 + 52 k) of one fixed-point number (a negative partial adds two's-complement pieces, each
+ * word keeps 12 bits of head room for carries), so a statistic's value is EXACTLY sum_slots sum_{k<4} word[k] 2^(-110 + 52 k): each workgroup adds its fp32 partial
+ * sum to slot (workgroup index mod 4) with 64-bit integer atomics, bits below 2^-110 floored toward -inf (at most once per workgroup; grids of at most 1,024
+ * workgroups).  Word 4 is the poison flag: non-zero once a partial was non-finite or >= 2^97 in magnitude; readers then take the statistic as NaN.
+ * RANGE: the variance is E[y^2] - mean^2 from those two sums, and each workgroup's partial of either is an fp32 sum, so a node whose |mean| / std = rho loses about
+ * (1 + rho^2) 2^-22 of its variance relative to a two-pass (torch.nn.BatchNorm1d) evaluation: rho = 8 is held to the 1e-4 / 3e-2 parity bars, rho = 64 to those
+ * bars plus twice that sensitivity (tests/test_gpu_gcn.py).  Default-initialised and trained-from-default weights sit at rho < 1 (U and V have zero-mean weights
+ * and see LayerNorm'd rows).
+ * Error 2, before any device is touched: n_frames outside [4, 256], neighbour_num outside [1, 4], mode not 0 / 1, batch < 1 or batch * n_frames * 17 * 16 >= 2^31,
+ * a required pointer that is null. */
+#define KASF_GCN_STAT_WORDS (4 * 512 * 5)
+int kasf_op_gcn_fwd(int32_t dtype, const void* x_in, const void* xn, const void* uv, const float* bn_w, const float* bn_b, float* run_mean, float* run_var,
+                    const float* ls1, void* y, uint32_t* mask, void* stats, float* coef, void* out, int32_t batch, int32_t n_frames, int32_t mode,
+                    int32_t neighbour_num, int32_t training, float momentum, void* stream);
+/* Gradients of the above for g [M,128] = d/d(out): r [M,128] = ls1 . g where the ReLU passed (the direct d/d(xn) term, and d/d(BN(y))), duv [M,256] = dU | dV (the
+ * adjacency carries no gradient); dls1 [128], d_bn_w and d_bn_b [nodes] are ACCUMULATED into.  xn, y, coef and mask as kasf_op_gcn_fwd left them; training as there
+ * (0: mean and variance are constants, duv has no batch-mean terms). */
+int kasf_op_gcn_bwd(int32_t dtype, const void* g, const void* xn, const void* y, const float* coef, const uint32_t* mask, const float* ls1, void* r, void* duv,
+                    float* dls1, float* d_bn_w, float* d_bn_b, void* bstats, int32_t batch, int32_t n_frames, int32_t mode, int32_t training, void* stream);
 /* fp32 <-> model dtype */
 int kasf_op_cast(int32_t dtype, const void* src, void* dst, int64_t n, int32_t to_f32, void* stream);
 

@@ -15,7 +15,8 @@ LIB_PATH = os.environ.get("KASF_LIB") or os.path.join(_HERE, "libkasf_hip.so")
 DTYPE_F32, DTYPE_BF16 = 0, 1
 FLAG_TRAIN, FLAG_RETURN_REP, FLAG_KEEP = 1, 2, 4
 EVAL_COLS = 22
-ABI_VERSION = 11        # kasf_version() of the library these prototypes describe (a stale in-tree .so is refused)
+GCN_STAT_WORDS = 4 * 512 * 5     # KASF_GCN_STAT_WORDS: int64 words of one BatchNorm statistics buffer of kasf_op_gcn_fwd / kasf_op_gcn_bwd
+ABI_VERSION = 12        # kasf_version() of the library these prototypes describe (a stale in-tree .so is refused)
 
 
 class KasfConfig(C.Structure):
@@ -91,6 +92,8 @@ SIGNATURES = {
     "kasf_op_attention_fwd_heads": (_i32, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp]),
     "kasf_op_attention_bwd_heads": (_i32, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "kasf_op_attention_bwd_fused_do": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "kasf_op_gcn_fwd": (_i32, [_i32] + [_vp] * 13 + [_i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "kasf_op_gcn_bwd": (_i32, [_i32] + [_vp] * 12 + [_i32, _i32, _i32, _i32, _vp]),
     "kasf_op_cast": (_i32, [_i32, _vp, _vp, _i64, _i32, _vp]),
 }
 _EXTRA = {}

@@ -625,7 +625,7 @@ void kasf_set_fused_attn_bwd(int32_t on) { g_fused_attn_bwd.store(on < 0 ? -1 : 
 int32_t kasf_get_fused_attn_bwd(void) { return fused_attn_bwd_mask(); }
 void kasf_set_deterministic(int32_t on) { kasf_set_single_stream(on); }
 int32_t kasf_get_deterministic(void) { return kasf_get_single_stream(); }
-int kasf_version(void) { return 11; }
+int kasf_version(void) { return 12; }
 
 int kasf_model_create(const kasf_config* cfg, kasf_model** out) {
     if (cfg == nullptr || out == nullptr) return kasf_set_error(2, "null argument");
@@ -1252,6 +1252,46 @@ int kasf_op_attention_bwd_fused_do(const void* q, int64_t ldq, const void* k, co
         return kasf_set_error(2, "fused-d_o attention backward: groups of at most 96 positions (form 1: at most 32); bf16, 8 heads");
     HIPCHK(hipGetLastError());
     return g_err.empty() ? 0 : 3;
+}
+// ---- the GCN mixer on its own (kasf.h, kasf_op_gcn_fwd / kasf_op_gcn_bwd): the launch sequence and `count` of block_forward / block_backward ----
+static_assert(KASF_GCN_STAT_WORDS == KASF_STAT_SLOTS * KASF_STAT_LD * KASF_STAT_WORDS, "kasf.h and kernels.h disagree on the size of a statistics buffer");
+static int gcn_shape_check(int32_t batch, int32_t n_frames, int32_t mode) {
+    if (mode != 0 && mode != 1) return kasf_set_error(2, "gcn: mode must be 0 (spatial) or 1 (temporal)");
+    if (n_frames < 4 || n_frames > KASF_MAX_NODES) return kasf_set_error(2, "gcn: n_frames must be in [4, 256]");
+    if (batch < 1 || (int64_t)batch * n_frames * 17 * 16 >= ((int64_t)1 << 31)) return kasf_set_error(2, "gcn: batch >= 1 and batch * n_frames * 17 * 16 must stay below 2^31");
+    return 0;
+}
+int kasf_op_gcn_fwd(int32_t dtype, const void* x_in, const void* xn, const void* uv, const float* bn_w, const float* bn_b, float* run_mean, float* run_var,
+                    const float* ls1, void* y, uint32_t* mask, void* stats, float* coef, void* out, int32_t batch, int32_t n_frames, int32_t mode,
+                    int32_t neighbour_num, int32_t training, float momentum, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (gcn_shape_check(batch, n_frames, mode) != 0) return 2;
+    if (neighbour_num < 1 || neighbour_num > 4) return kasf_set_error(2, "gcn: neighbour_num must be in [1, 4]");
+    if (!x_in || !xn || !uv || !bn_w || !bn_b || !run_mean || !run_var || !ls1 || !y || !stats || !coef || !out || (mode == 1 && !mask))
+        return kasf_set_error(2, "null pointer argument");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(stats, 0, (size_t)KASF_GCN_STAT_WORDS * sizeof(int64_t), s));
+    kasf_launch_gcn_agg_fwd(dtype, s, uv, xn, y, mode == 1 ? mask : nullptr, (double*)stats, batch, n_frames, mode, neighbour_num);
+    const double count = mode == 0 ? (double)batch * n_frames * 128 : (double)batch * 17 * 128;
+    kasf_launch_gcn_apply(dtype, s, x_in, xn, y, (const double*)stats, bn_w, bn_b, run_mean, run_var, coef, ls1, out, batch, n_frames, mode, count,
+                          training ? 1 : 0, momentum);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int kasf_op_gcn_bwd(int32_t dtype, const void* g, const void* xn, const void* y, const float* coef, const uint32_t* mask, const float* ls1, void* r, void* duv,
+                    float* dls1, float* d_bn_w, float* d_bn_b, void* bstats, int32_t batch, int32_t n_frames, int32_t mode, int32_t training, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (gcn_shape_check(batch, n_frames, mode) != 0) return 2;
+    if (!g || !xn || !y || !coef || !ls1 || !r || !duv || !dls1 || !d_bn_w || !d_bn_b || !bstats || (mode == 1 && !mask))
+        return kasf_set_error(2, "null pointer argument");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(bstats, 0, (size_t)KASF_GCN_STAT_WORDS * sizeof(int64_t), s));
+    kasf_launch_gcn_bwd1(dtype, s, g, xn, y, coef, ls1, r, dls1, (double*)bstats, batch, n_frames, mode);
+    const double count = mode == 0 ? (double)batch * n_frames * 128 : (double)batch * 17 * 128;
+    kasf_launch_gcn_bwd2(dtype, s, r, y, coef, mode == 1 ? mask : nullptr, duv, batch, n_frames, mode, (const double*)bstats, d_bn_w, d_bn_b, count,
+                         training ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 int kasf_op_cast(int32_t dtype, const void* src, void* dst, int64_t n, int32_t to_f32, void* stream) {
     OP_DT_CHECK(dtype);

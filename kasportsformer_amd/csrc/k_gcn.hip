@@ -406,7 +406,10 @@ __global__ __launch_bounds__(256) void k_gcn_apply(const T* __restrict__ x_in, c
         load8(xn + tok * 128 + sub * 8, b);
         load8(y + tok * 128 + sub * 8, c);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) a[e] += ls[e] * fmaxf(b[e] + c[e] * sc + sh, 0.f);
+        for (int e = 0; e < 8; ++e) {
+            const float z = b[e] + c[e] * sc + sh;
+            a[e] += ls[e] * (z != z ? z : fmaxf(z, 0.f));           // fmaxf drops a NaN; F.relu keeps it (a poisoned statistic must reach the output: graph.py:128-129)
+        }
         store8(out + tok * 128 + sub * 8, a);
     }
 }

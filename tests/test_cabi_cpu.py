@@ -250,6 +250,19 @@ int main(void) {
     kasf_model* m = 0;
     (void)kasf_model_create_layout_only(0, &m);                  /* null arguments are errors, not crashes */
     (void)kasf_model_create_layout_only(&shipped, 0);
+    {                                                            /* the GCN unit-test entries refuse before touching a device or a pointer */
+        float f[8] = {0};
+        uint32_t u[8] = {0};
+        void* p = f;
+        if (kasf_op_gcn_fwd(0, p, p, p, f, f, f, f, f, p, u, p, f, p, 2, 3, 1, 4, 1, 0.1f, 0) != 2) return 8;       /* n_frames */
+        if (kasf_op_gcn_fwd(0, p, p, p, f, f, f, f, f, p, u, p, f, p, 2, 27, 1, 5, 1, 0.1f, 0) != 2) return 8;      /* neighbour_num */
+        if (kasf_op_gcn_fwd(0, p, p, p, f, f, f, f, f, p, u, p, f, p, 2, 27, 2, 4, 1, 0.1f, 0) != 2) return 8;      /* mode */
+        if (kasf_op_gcn_fwd(0, p, p, p, f, f, f, f, f, p, u, p, f, p, 30841, 256, 0, 4, 1, 0.1f, 0) != 2) return 8; /* 2^31 */
+        if (kasf_op_gcn_fwd(0, p, p, p, f, f, f, f, f, p, 0, p, f, p, 2, 27, 1, 4, 1, 0.1f, 0) != 2) return 8;      /* temporal needs the mask */
+        if (kasf_op_gcn_bwd(1, p, p, p, f, u, f, p, p, f, f, f, p, 0, 27, 0, 1, 0) != 2) return 9;                  /* batch */
+        if (kasf_op_gcn_bwd(1, p, p, p, f, u, f, p, p, f, f, f, 0, 2, 27, 0, 1, 0) != 2) return 9;                  /* bstats */
+        if (f[0] != 0.0f || u[0] != 0u) return 10;
+    }
     printf("ok %s\n", kasf_last_error());
     return 0;
 }
@@ -263,3 +276,58 @@ int main(void) {
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0 and r.stdout.startswith("ok"), (r.stdout[-2000:], r.stderr[-4000:])
+
+
+def test_abi_version_is_12():
+    from kasportsformer_amd import _lib
+    assert _lib.ABI_VERSION == 12 and _lib.load().kasf_version() == 12
+    hdr = open(os.path.join(ROOT, "include", "kasf.h")).read()
+    words = re.search(r"#define\s+KASF_GCN_STAT_WORDS\s+\((\d+) \* (\d+) \* (\d+)\)", hdr)
+    assert words and int(words[1]) * int(words[2]) * int(words[3]) == _lib.GCN_STAT_WORDS
+
+
+def test_gcn_entry_points_refuse_without_a_device():
+    """kasf_op_gcn_fwd / kasf_op_gcn_bwd: every refusal of include/kasf.h is error 2 and happens before a device or a pointer is touched (the pointers given
+    here are host memory, which must come back unchanged)."""
+    import numpy as np
+    from kasportsformer_amd import _lib
+    lib = _lib.load()
+    buf = np.zeros(64, np.float32)
+    p = buf.ctypes.data_as(C.c_void_p)
+
+    def fwd(dtype=0, batch=2, T=27, mode=1, k=4, training=1, null=None):
+        a = [p] * 13                                         # x_in xn uv bn_w bn_b run_mean run_var ls1 y mask stats coef out
+        if null is not None:
+            a[null] = None
+        return lib.kasf_op_gcn_fwd(dtype, *a, batch, T, mode, k, training, 0.1, None)
+
+    def bwd(dtype=0, batch=2, T=27, mode=1, training=1, null=None):
+        a = [p] * 12                                         # g xn y coef mask ls1 r duv dls1 d_bn_w d_bn_b bstats
+        if null is not None:
+            a[null] = None
+        return lib.kasf_op_gcn_bwd(dtype, *a, batch, T, mode, training, None)
+
+    for T in (3, 257, 0, -1):
+        assert fwd(T=T) == 2 and bwd(T=T) == 2
+    assert lib.kasf_last_error()
+    for k in (0, 5, -1):
+        assert fwd(k=k) == 2
+    for mode in (-1, 2):
+        assert fwd(mode=mode) == 2 and bwd(mode=mode) == 2
+    for batch in (0, -3):
+        assert fwd(batch=batch) == 2 and bwd(batch=batch) == 2
+    # batch * n_frames * 17 * 16 >= 2^31: 30841 * 256 * 272 = 2,147,520,512 is refused, 30840 * 256 * 272 = 2,147,450,880 would be the largest accepted
+    assert 30840 * 256 * 272 < 2 ** 31 <= 30841 * 256 * 272
+    for mode in (0, 1):
+        assert fwd(batch=30841, T=256, mode=mode) == 2 and bwd(batch=30841, T=256, mode=mode) == 2
+        assert fwd(batch=2 ** 31 - 1, T=256, mode=mode) == 2 and bwd(batch=2 ** 31 - 1, T=256, mode=mode) == 2      # (no 32-bit overflow in the check itself)
+    for mode in (0, 1):
+        for i in range(13):
+            want = 2 if (i != 9 or mode == 1) else None      # the mask is required in temporal mode only
+            if want is not None:
+                assert fwd(mode=mode, null=i) == 2, (mode, i)
+        for i in range(12):
+            if i != 4 or mode == 1:
+                assert bwd(mode=mode, null=i) == 2, (mode, i)
+    assert fwd(dtype=2) == 3 and bwd(dtype=-1) == 3          # the family's bad-dtype code
+    assert not buf.any()

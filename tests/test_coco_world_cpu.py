@@ -184,9 +184,9 @@ def test_a_bad_layout_raises_from_all_three_lift_surfaces():
             K.StreamLifter(m, 1280, 720, slots=2, layout=good)
 
 
-def test_abi_version_is_still_11():
+def test_abi_version_is_at_least_11():
     from kasportsformer_amd import _lib
-    assert _lib.ABI_VERSION == 11 and _lib.load().kasf_version() == 11
+    assert _lib.ABI_VERSION == _lib.load().kasf_version() >= 11       # the two entries are ABI 11's; tests/test_cabi_cpu.py pins the current number
     assert "kasf_coco_h36m" in _lib.SIGNATURES and "kasf_pose_world" in _lib.SIGNATURES
 
 
