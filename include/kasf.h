@@ -29,6 +29,9 @@
  *                             its last T frames (fewer: the demo's one resampled clip) lifted every tick            demo/demo.py:132-156,222-236
  *   kasf_coco_h36m         <- h36m_coco_format / coco_h36m (COCO-17 detector keypoints -> H36M-17)  demo/lib/preprocess.py:10-69, demo/demo.py:75-78
  *   kasf_pose_world        <- camera_to_world / qrot, feet on the floor, unit scale                demo/lib/utils.py:55-73, demo/demo.py:242-248
+ *   kasf_heatmap_keypoints <- get_final_preds (get_max_preds, POST_PROCESS, transform_preds) and box_to_center_scale: what the demo does on the host between
+ *                             HRNet's output tensor and the COCO keypoints   demo/lib/hrnet/gen_kpts.py:158-161, demo/lib/hrnet/lib/utils/inference.py:21-82,
+ *                             demo/lib/hrnet/lib/utils/transforms.py:50-101, demo/lib/hrnet/lib/utils/utilitys.py:102-135
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
  *   kasf_op_gcn_fwd, kasf_op_gcn_bwd <- GCN.forward between its U | V Linear and the residual, and autograd of it   model/modules/graph.py:19-134, KASportsFormer.py:109
  */
@@ -262,6 +265,35 @@ int kasf_coco_h36m(const float* coco, int64_t frames, float* h36m, void* stream)
  * value into the launch; trans3 = NULL means zero (the demo's t = 0).  poses and out must not overlap.  frames = 0 does nothing; error 2 for
  * frames < 0, or a null poses / quat4 / out with frames > 0 (no device needed to refuse). */
 int kasf_pose_world(const float* poses, int64_t frames, const float* quat4, const float* trans3, int32_t floor, int32_t unit, float* out, void* stream);
+
+/* ---- pose-network heatmaps -> keypoints (a symbol ADDED under ABI 12: no existing entry changed, so the number did not; look it up by name) ----
+ * hm [n][17][H][W], contiguous, of KASF_DTYPE_F32, KASF_DTYPE_F16 or KASF_DTYPE_BF16 (the 16-bit types are widened to fp32 on load, which is exact; every rule
+ * below is on the fp32 values) -> out [n][17][3] fp32 = image x, image y, score per joint: get_final_preds (inference.py:52-82) of a top-down pose network
+ * (HRNet, ViTPose, SimpleBaseline), per map:
+ *   argmax    score = the map's largest value, position = its FIRST occurrence in row-major order (np.argmax); a map with a NaN gives score NaN at the first
+ *             NaN.  x = idx % W, y = idx / W; where "score > 0" is false (zero, negative, NaN) the position is (0, 0)                  (inference.py:21-49)
+ *   refine    (refine != 0; the demo's TEST.POST_PROCESS) only where 1 < x < W - 1 and 1 < y < H - 1, strictly: x += 0.25 sign(hm[y][x + 1] - hm[y][x - 1]),
+ *             the same for y; fp32 differences, sign(0) = 0, a NaN difference gives NaN                                                 (inference.py:59-72)
+ *   to image  transform_preds with rot = 0: the anchors sw = fl32(scale_x * 200), s1y = fl32(cy - sw / 2), dy = fl32(cy - s1y), s2x = fl32(cx - dy) as the
+ *             reference stores them, then in fp64 kx = (cx - s2x) / (W / 2), ky = (cy - s1y) / (W / 2), x_img = cx + (x - W / 2) kx, y_img = cy + (y - H / 2) ky,
+ *             each rounded once to fp32.  Only scale_x enters and both axes divide by W / 2, as in the reference.  The reference solves the same three-point
+ *             system with cv2.getAffineTransform and is within 1 fp32 ulp of this closed form                                    (transforms.py:50-101)
+ * geom [n][4] fp32 (device), per person: KASF_GEOM_CENTER_SCALE = (cx, cy, scale_x, scale_y), the pair the crop was made with; KASF_GEOM_BOX = the detector's
+ * box (x1, y1, x2, y2), from which center and scale are derived as box_to_center_scale does (utilitys.py:102-135): in fp64 on the widened box, the box grown to
+ * width / height = `aspect`, divided by 200, stored as fp32, then * 1.25 in fp32 unless center x == -1.  `aspect` is a double because the demo passes
+ * frame_height / frame_width evaluated in fp64 (utilitys.py:151: image.shape[0], image.shape[1]); pass what the crop was made with.  It is ignored with
+ * KASF_GEOM_CENTER_SCALE.
+ * out_layout: KASF_LAYOUT_COCO = the network's joint order; KASF_LAYOUT_H36M = kasf_coco_h36m of that result, bit for bit, as a second launch on the same stream:
+ * coco_scratch [n][17][3] fp32 (device, not overlapping out) is then required and is left holding the COCO result; it is ignored (may be NULL) with KASF_LAYOUT_COCO.
+ * hm and geom are only read.  n = 0 does nothing.  Error 2, before a device or a pointer is touched: n < 0, H or W < 1, H * W > 2^24 (the reference's index
+ * arithmetic is fp32), an unknown dtype, geom_kind or out_layout, aspect <= 0 (or NaN) with KASF_GEOM_BOX, a required pointer that is null with n > 0. */
+#define KASF_DTYPE_F16 2           /* IEEE half: heatmap input only, no model runs in it */
+#define KASF_GEOM_CENTER_SCALE 0
+#define KASF_GEOM_BOX 1
+#define KASF_LAYOUT_COCO 0
+#define KASF_LAYOUT_H36M 1
+int kasf_heatmap_keypoints(const void* hm, int32_t dtype, int64_t n, int32_t H, int32_t W, const float* geom, int32_t geom_kind, double aspect, int32_t refine,
+                           int32_t out_layout, float* out, float* coco_scratch, void* stream);
 
 /* debugging / tests: locate a named activation inside the workspace (see kasf_ws_name()) */
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags);

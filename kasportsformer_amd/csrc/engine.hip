@@ -1157,6 +1157,25 @@ int kasf_pose_world(const float* poses, int64_t frames, const float* quat4, cons
     return 0;
 }
 
+// ---- pose-network heatmaps -> keypoints (kasf.h, kasf_heatmap_keypoints) ----
+int kasf_heatmap_keypoints(const void* hm, int32_t dtype, int64_t n, int32_t H, int32_t W, const float* geom, int32_t geom_kind, double aspect, int32_t refine,
+                           int32_t out_layout, float* out, float* coco_scratch, void* stream) {
+    if (n < 0) return kasf_set_error(2, "heatmap_keypoints: n must be >= 0");
+    if (H < 1 || W < 1) return kasf_set_error(2, "heatmap_keypoints: H and W must be >= 1");
+    if ((int64_t)H * W > ((int64_t)1 << 24)) return kasf_set_error(2, "heatmap_keypoints: H * W must be <= 2^24 (the reference's index arithmetic is fp32)");
+    if (dtype != KASF_F32 && dtype != KASF_F16 && dtype != KASF_BF16) return kasf_set_error(2, "heatmap_keypoints: dtype must be KASF_DTYPE_F32, _F16 or _BF16");
+    if (geom_kind != KASF_GEOM_CENTER_SCALE && geom_kind != KASF_GEOM_BOX) return kasf_set_error(2, "heatmap_keypoints: geom_kind must be KASF_GEOM_CENTER_SCALE or KASF_GEOM_BOX");
+    if (out_layout != KASF_LAYOUT_COCO && out_layout != KASF_LAYOUT_H36M) return kasf_set_error(2, "heatmap_keypoints: out_layout must be KASF_LAYOUT_COCO or KASF_LAYOUT_H36M");
+    if (geom_kind == KASF_GEOM_BOX && !(aspect > 0.0)) return kasf_set_error(2, "heatmap_keypoints: aspect must be > 0 with KASF_GEOM_BOX");
+    if (n == 0) return 0;
+    if (!hm || !geom || !out || (out_layout == KASF_LAYOUT_H36M && !coco_scratch)) return kasf_set_error(2, "null pointer argument");
+    const bool h36m = out_layout == KASF_LAYOUT_H36M;
+    kasf_launch_heatmap_keypoints((hipStream_t)stream, hm, dtype, n, H, W, geom, geom_kind, aspect, refine ? 1 : 0, h36m ? coco_scratch : out);
+    if (h36m) kasf_launch_coco_h36m((hipStream_t)stream, coco_scratch, n, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 #define OP_DT_CHECK(dt) \
     if ((dt) != KASF_F32 && (dt) != KASF_BF16) return kasf_set_error(3, "bad dtype")
 

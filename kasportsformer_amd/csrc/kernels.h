@@ -6,6 +6,7 @@
 
 #define KASF_F32 0
 #define KASF_BF16 1
+#define KASF_F16 2   // heatmap input only (kasf_heatmap_keypoints): no model runs in it
 
 struct KasfPackDesc {
     int64_t src;        // element offset into the fp32 parameter buffer
@@ -191,6 +192,11 @@ void kasf_launch_stream_emit(hipStream_t s, const float* pred, int flip, const i
 void kasf_launch_coco_h36m(hipStream_t s, const float* coco, int64_t frames, float* h36m);
 // q [4], t [3]: host arrays, passed by value into the launch
 void kasf_launch_pose_world(hipStream_t s, const float* poses, int64_t frames, const float* q, const float* t, int floor, int unit, float* out);
+
+// ---- k_heatmap.hip: pose-network heatmaps hm [n,17,H,W] (dtype KASF_F32 / KASF_F16 / KASF_BF16) -> out [n,17,3] fp32 image x, y, score in COCO order (kasf.h,
+// kasf_heatmap_keypoints); geom [n,4] fp32: kind 0 = center x, y, scale x, y; kind 1 = box x1, y1, x2, y2 widened to `aspect`; H * W <= 2^24 ----
+void kasf_launch_heatmap_keypoints(hipStream_t s, const void* hm, int dtype, int64_t n, int H, int W, const float* geom, int geom_kind, double aspect,
+                                   int refine, float* out);
 
 // ---- k_gemm2.hip (bf16, persistent, register-resident weights) ----
 // bf16 partial tiles a fused data + weight gradient launch left: out[e] += sum over z < nparts of part[z][e], e < elems (elems a multiple of 128)

@@ -3,6 +3,7 @@
     lifter = StreamLifter(model, width, height, slots=32, flip=True, lag=0)      # width / height: one value or one per slot; layout="coco": COCO-17 frames in
     poses = lifter.push(kp)                     # kp [slots,17,3] fp32 pixels + confidence, one new frame for every slot -> CUDA fp32 [slots,17,3]
     poses = lifter.push(kp, slots=[3, 7, 8])    # kp [3,17,3]: only these slots got a frame this tick -> [3,17,3]
+    poses = lifter.push_heatmaps(hm, center, scale)    # hm [slots,17,H,W]: the pose network's output, decoded on the device, then pushed
     rest = lifter.tail(slots=[3])               # [1,lag,17,3]: the frames push has not emitted yet, at the end of a track
     lifter.reset(slots=[7])                     # the player left: the slot starts a new history
     poses = lifter.replay(track)                # a recorded [N,17,3] / [P,N,17,3] track tick by tick, through a temporary state
@@ -20,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .heatmap import check_heatmap_args, decode
 from .pose import check_layout, convert_frames
 from .lift import _as_tensor, _forward_windows, _model_device, _stream, _upload, window_plan
 
@@ -145,6 +147,24 @@ class StreamLifter:
             else:
                 self._counts[ids] += 1
             return self._lift(ids_d, K, self.lag, 1).view(K, 17, 3)
+
+    def push_heatmaps(self, heatmaps, center=None, scale=None, *, boxes=None, aspect=None, refine: bool = True, slots=None) -> torch.Tensor:
+        """One new frame per slot straight from the pose network: ``heatmaps`` [K,17,H,W] (float32, float16 or bfloat16; normally the network's output
+        on the model's GPU, read in place) with ``center`` / ``scale`` [K,2] or ``boxes`` [K,4] and ``aspect`` as ``heatmaps_to_keypoints`` takes them,
+        decoded on the device and pushed: what ``push`` returns for ``heatmaps_to_keypoints(..., layout="h36m")`` of them (for the COCO result on a
+        ``layout="coco"`` lifter, which is the same frames).  Two launches in front of ``push``'s, no host round trip.  Nothing is filtered: a map that
+        holds a NaN gives a NaN score (and possibly coordinates) in the ring, as pushing those keypoints would."""
+        who = "StreamLifter.push_heatmaps"
+        hm, parts, kind, aspect = check_heatmap_args(heatmaps, center, scale, boxes, aspect, who)
+        ids = self._ids(slots, who)
+        K = self.slots if ids is None else int(ids.size)
+        if hm.dim() != 4 or hm.shape[0] != K:
+            raise ValueError(f"{who}: expected heatmaps [{K},17,H,W] (one person per pushed slot), got {tuple(hm.shape)}")
+        for t in (hm,) + parts:
+            if t.is_cuda and t.device != self.device:
+                raise RuntimeError(f"{who}: input on {t.device}, the model on {self.device}")
+        kp = decode(hm.to(self.device), tuple(t.to(self.device) for t in parts), kind, aspect, refine, not self._coco)
+        return self.push(kp, slots=slots)
 
     def tail(self, slots=None) -> torch.Tensor:
         """The ``lag`` frames ``push`` has not emitted yet, from the current windows, for the end of a track: [K,lag,17,3], row r = frame
