@@ -32,6 +32,9 @@
  *   kasf_heatmap_keypoints <- get_final_preds (get_max_preds, POST_PROCESS, transform_preds) and box_to_center_scale: what the demo does on the host between
  *                             HRNet's output tensor and the COCO keypoints   demo/lib/hrnet/gen_kpts.py:158-161, demo/lib/hrnet/lib/utils/inference.py:21-82,
  *                             demo/lib/hrnet/lib/utils/transforms.py:50-101, demo/lib/hrnet/lib/utils/utilitys.py:102-135
+ *   kasf_detect_boxes      <- predict_transform, write_results (objectness threshold, class arg-max, persons only, sort, greedy NMS) and the un-letterbox of
+ *                             yolo_human_det: what the demo does between the YOLOv3 network's output and the person boxes
+ *                             demo/lib/yolov3/util.py:34-81,107-225, demo/lib/yolov3/bbox.py:51-78, demo/lib/yolov3/human_detector.py:116-168
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
  *   kasf_op_gcn_fwd, kasf_op_gcn_bwd <- GCN.forward between its U | V Linear and the residual, and autograd of it   model/modules/graph.py:19-134, KASportsFormer.py:109
  */
@@ -294,6 +297,55 @@ int kasf_pose_world(const float* poses, int64_t frames, const float* quat4, cons
 #define KASF_LAYOUT_H36M 1
 int kasf_heatmap_keypoints(const void* hm, int32_t dtype, int64_t n, int32_t H, int32_t W, const float* geom, int32_t geom_kind, double aspect, int32_t refine,
                            int32_t out_layout, float* out, float* coco_scratch, void* stream);
+
+/* ---- YOLOv3 detector output -> person boxes in frame pixels (ADDED under ABI 12: additive, kasf_version() stays 12; a library without it fails to load on the
+ * missing symbol).  Replaces, on the device and without a host synchronisation, what yolo_human_det does behind the detector network (human_detector.py:116-168):
+ * predict_transform (util.py:34-81), write_results with det_hm (util.py:107-225) and the un-letterbox (human_detector.py:144-153).  Two launches on `stream`.
+ * src [n_src] (a HOST array of DEVICE pointers), of KASF_DTYPE_F32, _F16 or _BF16 (the 16-bit types are widened to fp32 on load, which is exact; every rule is on
+ * the fp32 values), contiguous, only read:
+ *   KASF_DETECT_PREDICTION  n_src = 1, src[0] = prediction [batch][N][5 + C] with N = grid[0]: what Darknet.forward returns (x, y, w, h at network-input scale,
+ *                           objectness, C class scores; already through predict_transform).  A, anchors are ignored.
+ *   KASF_DETECT_HEADS       src[k] = raw head [batch][A * (5 + C)][G_k][G_k], G_k = grid[k], as the conv layer in front of each detection layer writes it; anchors
+ *                           (HOST) [n_src][A][2] = the (w, h) pixel pairs of head k.  N = sum_k G_k^2 A.
+ * RULES.
+ *  1 candidate index   its position in the reference's concatenated prediction: heads in the given order, within a head (cy * G + cx) * A + a; in the prediction
+ *                      form the row number.
+ *  2 box decode        (heads form only) stride = inp_dim / G (inp_dim % G != 0 is refused); x = (sigmoid(tx) + cx) * stride, y likewise; w = exp(tw) *
+ *                      fl32(anchor_w / stride) * stride, h likewise; objectness and class score = sigmoid of their logits; all fp32, in this order.  The device's
+ *                      exp is not the host's: results sit within a few ulp of the reference's, not on its bits.
+ *  3 threshold         a candidate passes when objectness > confidence: strict, fp32.
+ *  4 person filter     keep a candidate only if the arg-max of its C class values is class_id; the values are compared with > from class 0 on, so the FIRST maximum
+ *                      wins (and a NaN neither wins nor, in first place, loses).  In the heads form the arg-max is taken on the logits and one sigmoid is computed for
+ *                      the winner, not C: this differs from the reference only where two class logits round to the same fp32 sigmoid.
+ *  5 corners           x1 = x - w / 2, y1 = y - h / 2, x2 = x + w / 2, y2 = y + h / 2, at network-input scale.
+ *  6 order             descending objectness; equal objectness: the lower candidate index first (torch.sort leaves that undefined; here it is defined).
+ *  7 NMS               greedy in that order at network-input scale; IoU as bbox_iou (bbox.py:51-78): sides (x2 - x1 + 1), intersection sides max(. + 1, 0), iou =
+ *                      inter / (a1 + a2 - inter), fp32.  A later box survives a kept one iff iou < nms (an equal IoU, or a NaN one, is suppressed).
+ *  8 un-letterbox      fp32: sf = min((1 / width) * inp_dim, (1 / height) * inp_dim) -- two roundings each, as torch evaluates `number / tensor` --; x -= (inp_dim - sf * width) / 2, y -= (inp_dim - sf * height) / 2; both / sf; x clamped
+ *                      to [0, width], y to [0, height].  frame_wh (device) [batch][2] = width, height of each image's frame.
+ *  9 caps              only the max_candidates best candidates by rule 6 enter NMS (1 <= max_candidates <= KASF_DETECT_MAX_CANDIDATES = 4,096: sort and NMS run in
+ *                      the 160 KiB of LDS of one CU), only the first max_boxes survivors are written (1 <= max_boxes <= max_candidates).  Greedy NMS depends only on
+ *                      better-ranked boxes, so a capped result is exactly a prefix of the uncapped one.  count[b][1] shows whether the candidate cap bit.
+ * 10 differences from the reference, deliberate:  images of a batch are independent (write_results returns at the first image without a person, util.py:156-157;
+ *                      here such an image has count 0 and the others are unaffected).  A candidate whose objectness is NaN, or one of whose four corners is not
+ *                      finite, is dropped before it is counted (the reference keeps NaN * 0 rows).  The host-side round(i, 2) of human_detector.py:161 and the SORT
+ *                      tracker behind it are not part of this.  With confidence < 0 a zero or negative objectness passes and is ordered by its value (the
+ *                      reference's nonzero() filter would drop an exact 0).
+ * 11 determinism       the same bits from run to run, and an image's result does not depend on what else is in the batch: no atomics; candidates are selected and
+ *                      ordered by the key (objectness, index) alone, through an order-preserving map of the fp32 bits.
+ * OUTPUT (device).  boxes [batch][max_boxes][6] fp32 = x1, y1, x2, y2 (frame pixels), objectness, class score; index [batch][max_boxes] int32 = candidate index of
+ * each row; count [batch][2] int32 = rows written, candidates that passed rules 3, 4 and 10 before any cap.  Rows past the count are 0 (index: -1).
+ * workspace (device, 16-byte aligned): kasf_detect_workspace_bytes(batch, N, max_candidates) bytes (28 per candidate slot; negative on a refused shape), contents undefined before
+ * and after.  batch = 0 does nothing.  Error 2, before a device or a pointer is touched: a null pointer (src, src[k], grid, frame_wh, boxes, index, count, workspace;
+ * anchors in the heads form), batch outside [0, 65535], n_src outside 1..4 (or not 1 in the prediction form), A outside 1..8, C < 1, class_id outside [0, C), a grid
+ * outside [1, 4096] or not dividing inp_dim, N outside [1, 2^24], the caps out of range, confidence or nms not finite, an unknown form or dtype, workspace too small or not 16-byte aligned. */
+#define KASF_DETECT_PREDICTION 0
+#define KASF_DETECT_HEADS 1
+#define KASF_DETECT_MAX_CANDIDATES 4096
+int64_t kasf_detect_workspace_bytes(int32_t batch, int64_t n_per_image, int32_t max_candidates);
+int kasf_detect_boxes(const void* const* src, int32_t n_src, int32_t form, int32_t dtype, int32_t batch, const int32_t* grid, int32_t A, int32_t C,
+                      const float* anchors, int32_t inp_dim, const float* frame_wh, float confidence, float nms, int32_t class_id, int32_t max_candidates,
+                      int32_t max_boxes, float* boxes, int32_t* index, int32_t* count, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* debugging / tests: locate a named activation inside the workspace (see kasf_ws_name()) */
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags);

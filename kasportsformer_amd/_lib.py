@@ -16,6 +16,8 @@ DTYPE_F32, DTYPE_BF16 = 0, 1
 DTYPE_F16 = 2                          # KASF_DTYPE_F16: heatmap input only (kasf_heatmap_keypoints)
 GEOM_CENTER_SCALE, GEOM_BOX = 0, 1
 LAYOUT_COCO, LAYOUT_H36M = 0, 1
+DETECT_PREDICTION, DETECT_HEADS = 0, 1
+DETECT_MAX_CANDIDATES = 4096           # KASF_DETECT_MAX_CANDIDATES
 FLAG_TRAIN, FLAG_RETURN_REP, FLAG_KEEP = 1, 2, 4
 EVAL_COLS = 22
 GCN_STAT_WORDS = 4 * 512 * 5     # KASF_GCN_STAT_WORDS: int64 words of one BatchNorm statistics buffer of kasf_op_gcn_fwd / kasf_op_gcn_bwd
@@ -83,6 +85,9 @@ SIGNATURES = {
     "kasf_coco_h36m": (_i32, [_vp, _i64, _vp, _vp]),
     "kasf_pose_world": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "kasf_heatmap_keypoints": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i32, C.c_double, _i32, _i32, _vp, _vp, _vp]),
+    "kasf_detect_workspace_bytes": (_i64, [_i32, _i64, _i32]),
+    "kasf_detect_boxes": (_i32, [_vp, _i32, _i32, _i32, _i32, _pi32, _i32, _i32, C.POINTER(_f32), _i32, _vp, _f32, _f32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                 _i64, _vp]),
     "kasf_ws_entries": (_i32, [_vp, _i32, _i32]),
     "kasf_ws_entry": (_i32, [_vp, _i32, _i32, _i32, C.c_char_p, _i32, _pi64, _pi64, _pi32]),
     "kasf_op_linear": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),

@@ -1176,6 +1176,55 @@ int kasf_heatmap_keypoints(const void* hm, int32_t dtype, int64_t n, int32_t H, 
     return 0;
 }
 
+// ---- detector output -> person boxes (kasf.h, kasf_detect_boxes) ----
+static const char* detect_shape_error(int32_t batch, int64_t n_per_image, int32_t max_candidates) {
+    if (batch < 0 || batch > 65535) return "detect: batch must be in [0, 65535]";
+    if (n_per_image < 1 || n_per_image > ((int64_t)1 << 24)) return "detect: candidates per image must be in [1, 2^24]";
+    if (max_candidates < 1 || max_candidates > KASF_DETECT_MAX_CANDIDATES) return "detect: max_candidates must be in [1, 4096] (KASF_DETECT_MAX_CANDIDATES: sort and NMS run in LDS)";
+    return nullptr;
+}
+int64_t kasf_detect_workspace_bytes(int32_t batch, int64_t n_per_image, int32_t max_candidates) {
+    if (const char* e = detect_shape_error(batch, n_per_image, max_candidates)) return -(int64_t)kasf_set_error(2, e);
+    return kasf_detect_ws_bytes(batch, n_per_image);
+}
+int kasf_detect_boxes(const void* const* src, int32_t n_src, int32_t form, int32_t dtype, int32_t batch, const int32_t* grid, int32_t A, int32_t C,
+                      const float* anchors, int32_t inp_dim, const float* frame_wh, float confidence, float nms, int32_t class_id, int32_t max_candidates,
+                      int32_t max_boxes, float* boxes, int32_t* index, int32_t* count, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (form != KASF_DETECT_PREDICTION && form != KASF_DETECT_HEADS) return kasf_set_error(2, "detect_boxes: form must be KASF_DETECT_PREDICTION or KASF_DETECT_HEADS");
+    if (dtype != KASF_F32 && dtype != KASF_F16 && dtype != KASF_BF16) return kasf_set_error(2, "detect_boxes: dtype must be KASF_DTYPE_F32, _F16 or _BF16");
+    if (n_src < 1 || n_src > KASF_DETECT_MAX_SRC || (form == KASF_DETECT_PREDICTION && n_src != 1))
+        return kasf_set_error(2, "detect_boxes: n_src must be in [1, 4], and 1 in the prediction form");
+    if (!src || !grid) return kasf_set_error(2, "null pointer argument");
+    if (C < 1 || C > 65536) return kasf_set_error(2, "detect_boxes: C must be in [1, 65536]");
+    if (class_id < 0 || class_id >= C) return kasf_set_error(2, "detect_boxes: class_id must be in [0, C)");
+    if (inp_dim < 1) return kasf_set_error(2, "detect_boxes: inp_dim must be >= 1");
+    int64_t N = 0;
+    if (form == KASF_DETECT_HEADS) {
+        if (A < 1 || A > KASF_DETECT_MAX_A) return kasf_set_error(2, "detect_boxes: A must be in [1, 8]");
+        if (!anchors) return kasf_set_error(2, "null pointer argument");
+        for (int k = 0; k < n_src; ++k) {
+            if (grid[k] < 1 || grid[k] > 4096 || inp_dim % grid[k] != 0) return kasf_set_error(2, "detect_boxes: every grid must be in [1, 4096] and divide inp_dim");
+            N += (int64_t)grid[k] * grid[k] * A;
+        }
+    } else {
+        N = grid[0];
+    }
+    if (const char* e = detect_shape_error(batch, N, max_candidates)) return kasf_set_error(2, e);
+    if (max_boxes < 1 || max_boxes > max_candidates) return kasf_set_error(2, "detect_boxes: max_boxes must be in [1, max_candidates]");
+    if (!std::isfinite(confidence) || !std::isfinite(nms)) return kasf_set_error(2, "detect_boxes: confidence and nms must be finite");
+    if (batch == 0) return 0;
+    for (int k = 0; k < n_src; ++k)
+        if (!src[k]) return kasf_set_error(2, "null pointer argument");
+    if (!frame_wh || !boxes || !index || !count || !workspace) return kasf_set_error(2, "null pointer argument");
+    if (((uintptr_t)workspace & 15) != 0) return kasf_set_error(2, "detect_boxes: workspace must be 16-byte aligned");
+    if (workspace_bytes < kasf_detect_ws_bytes(batch, N)) return kasf_set_error(2, "detect_boxes: workspace too small (see kasf_detect_workspace_bytes)");
+    if (const char* e = kasf_launch_detect_boxes((hipStream_t)stream, src, n_src, form, dtype, batch, grid, A, C, anchors, inp_dim, frame_wh, confidence, nms,
+                                                 class_id, max_candidates, max_boxes, boxes, index, count, workspace))
+        return kasf_set_error(3, e);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 #define OP_DT_CHECK(dt) \
     if ((dt) != KASF_F32 && (dt) != KASF_BF16) return kasf_set_error(3, "bad dtype")
 

@@ -198,6 +198,21 @@ void kasf_launch_pose_world(hipStream_t s, const float* poses, int64_t frames, c
 void kasf_launch_heatmap_keypoints(hipStream_t s, const void* hm, int dtype, int64_t n, int H, int W, const float* geom, int geom_kind, double aspect,
                                    int refine, float* out);
 
+// ---- k_detect.hip: YOLOv3 detector output -> person boxes (kasf.h, kasf_detect_boxes): a selection launch (every candidate's key slot, the box and score slots of the
+// passing ones) and one sort + NMS + output workgroup per image.  Arguments as checked by the entry point; returns nullptr or a message when the launch cannot be made ----
+#define KASF_DETECT_FORM_PREDICTION 0
+#define KASF_DETECT_FORM_HEADS 1
+#define KASF_DETECT_MAX_SRC 4
+#define KASF_DETECT_MAX_A 8
+#ifndef KASF_DETECT_MAX_CANDIDATES
+#define KASF_DETECT_MAX_CANDIDATES 4096
+#endif                                      // sort + NMS in LDS: 8,192 keys (64 KiB) + 4,096 boxes (64 KiB) + 4,096 flags of the CU's 160 KiB
+inline int64_t kasf_detect_round(int64_t bytes) { return (bytes + 255) / 256 * 256; }
+int64_t kasf_detect_ws_bytes(int64_t B, int64_t N);   // key [B][N] u64 | box [B][N] float4 | score [B][N] fp32, each rounded up to 256 bytes
+const char* kasf_launch_detect_boxes(hipStream_t s, const void* const* src, int n_src, int form, int dtype, int B, const int* grid, int A, int C,
+                                     const float* anchors, int inp_dim, const float* frame_wh, float confidence, float nms, int class_id, int max_candidates,
+                                     int max_boxes, float* boxes, int* index, int* count, void* workspace);
+
 // ---- k_gemm2.hip (bf16, persistent, register-resident weights) ----
 // bf16 partial tiles a fused data + weight gradient launch left: out[e] += sum over z < nparts of part[z][e], e < elems (elems a multiple of 128)
 // ---- persistent launches narrower than the chip (round 4) ----
