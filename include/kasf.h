@@ -35,6 +35,9 @@
  *   kasf_detect_boxes      <- predict_transform, write_results (objectness threshold, class arg-max, persons only, sort, greedy NMS) and the un-letterbox of
  *                             yolo_human_det: what the demo does between the YOLOv3 network's output and the person boxes
  *                             demo/lib/yolov3/util.py:34-81,107-225, demo/lib/yolov3/bbox.py:51-78, demo/lib/yolov3/human_detector.py:116-168
+ *   kasf_crop_persons      <- PreProcess: box_to_center_scale, get_affine_transform, cv2.warpAffine, ToTensor, Normalize and the [2, 1, 0] channel swap: what the
+ *                             demo does on the host between the person boxes and HRNet's input tensor
+ *                             demo/lib/hrnet/lib/utils/utilitys.py:139-169, demo/lib/hrnet/gen_kpts.py:152-157, demo/lib/hrnet/lib/utils/transforms.py:58-101
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
  *   kasf_op_gcn_fwd, kasf_op_gcn_bwd <- GCN.forward between its U | V Linear and the residual, and autograd of it   model/modules/graph.py:19-134, KASportsFormer.py:109
  */
@@ -290,7 +293,7 @@ int kasf_pose_world(const float* poses, int64_t frames, const float* quat4, cons
  * coco_scratch [n][17][3] fp32 (device, not overlapping out) is then required and is left holding the COCO result; it is ignored (may be NULL) with KASF_LAYOUT_COCO.
  * hm and geom are only read.  n = 0 does nothing.  Error 2, before a device or a pointer is touched: n < 0, H or W < 1, H * W > 2^24 (the reference's index
  * arithmetic is fp32), an unknown dtype, geom_kind or out_layout, aspect <= 0 (or NaN) with KASF_GEOM_BOX, a required pointer that is null with n > 0. */
-#define KASF_DTYPE_F16 2           /* IEEE half: heatmap input only, no model runs in it */
+#define KASF_DTYPE_F16 2           /* IEEE half: heatmap / detector input and crop output only, no model runs in it */
 #define KASF_GEOM_CENTER_SCALE 0
 #define KASF_GEOM_BOX 1
 #define KASF_LAYOUT_COCO 0
@@ -346,6 +349,46 @@ int64_t kasf_detect_workspace_bytes(int32_t batch, int64_t n_per_image, int32_t 
 int kasf_detect_boxes(const void* const* src, int32_t n_src, int32_t form, int32_t dtype, int32_t batch, const int32_t* grid, int32_t A, int32_t C,
                       const float* anchors, int32_t inp_dim, const float* frame_wh, float confidence, float nms, int32_t class_id, int32_t max_candidates,
                       int32_t max_boxes, float* boxes, int32_t* index, int32_t* count, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- person boxes -> pose-network inputs (ADDED under ABI 12: additive, kasf_version() stays 12; a library without it fails to load on the missing symbol).
+ * Replaces, on the device, the demo's PreProcess (utilitys.py:139-169): per person box_to_center_scale, get_affine_transform, cv2.warpAffine(frame, trans,
+ * (out_w, out_h), INTER_LINEAR), ToTensor, Normalize, torch.cat and the [:, [2, 1, 0]] swap of gen_kpts.py:155.  One launch on `stream`; the library allocates nothing.
+ * frames: uint8 (device), n_frames images of Hf rows of Wf pixels of 3 interleaved channels; pixel (f, y, x) channel c is the byte at
+ * frames + f * frame_stride + y * row_stride + 3 * x + c.  row_stride >= 3 * Wf: a decoder's padded pitch is read in place.  frames is only read.
+ * frame_index [n] int32 (device): the frame each person is cropped from; may be NULL when n_frames == 1 (every person from frame 0).  A value outside
+ * [0, n_frames) cannot be refused without a synchronisation: that person comes out as an all-border crop (rule 3 with every tap outside).
+ * geom [n][4] fp32 (device), geom_kind, aspect: exactly as kasf_heatmap_keypoints takes them.
+ * out [n][3][out_h][out_w] (device) of out_dtype = KASF_DTYPE_F32, _F16 or _BF16.  mean_std: a HOST pointer to six floats, mean[0..2] then std[0..2], indexed by the
+ * FRAME's channel (rule 4), read during the call and passed by value into the launch.  center_scale_out [n][4] fp32 (device; may be NULL).
+ * RULES.
+ *  1 geometry    center (cx, cy) and scale (scale_x, scale_y) as fp32: given, or derived from the box as kasf_heatmap_keypoints derives them, with
+ *                scale_y = fl32(box height grown to the aspect / 200) (* 1.25 in fp32 unless cx == -1).  The map from crop pixel (x, y) to frame position is the
+ *                closed form of get_affine_transform(center, scale, 0, (out_w, out_h), inv = 1), the one kasf_heatmap_keypoints applies, with out_w, out_h in
+ *                place of the heatmap's W, H: anchors sw = fl32(scale_x * 200), s1y = fl32(cy - sw / 2), dy = fl32(cy - s1y), s2x = fl32(cx - dy); then in fp64
+ *                kx = (cx - s2x) / (out_w / 2), ky = (cy - s1y) / (out_w / 2) (both by out_w / 2; only scale_x enters, as in the reference),
+ *                bx = cx - (out_w / 2) kx, by = cy - (out_h / 2) ky.  Position of (x, y): (bx + kx x, by + ky y).
+ *  2 positions   on a 1/32-pixel grid, by the 10-bit fixed-point scheme of OpenCV's portable warpAffine; rint = round half to even, integers are 64-bit (where
+ *                they fit 32 bits they are the same numbers; a rounded value beyond +-2^61 saturates there).  Column x: ad[x] = rint((kx x) 1024).  Row y:
+ *                X0 = rint(bx 1024) + 16, Y0 = rint((ky y + by) 1024) + 16.  X = (X0 + ad[x]) >> 5, Y = Y0 >> 5 (arithmetic shifts).  The tap is (X >> 5, Y >> 5),
+ *                the fractions are fx = X & 31, fy = Y & 31.  If any of kx, ky, bx, by is not finite the whole crop is border.
+ *  3 value       per channel, with p00 the tap, p01 its right, p10 its lower and p11 its lower right neighbour, each counted 0 on its own when it lies outside
+ *                the frame (BORDER_CONSTANT 0): S = (32 - fx)(32 - fy) p00 + fx (32 - fy) p01 + (32 - fx) fy p10 + fx fy p11, v = (S + 512) >> 10, an integer
+ *                0..255.  This is the 15-bit-weight form (32 S + 16384) >> 15, the weights being exact multiples of 32.  No antialiasing when the box is larger
+ *                than the crop (the reference has none either).
+ *  4 normalise   f = ((float)v / 255.0f - mean[c]) / std[c] in fp32, every operation rounded once, c the FRAME's channel.  With swap_rb != 0 output plane k holds
+ *                frame channel 2 - k, otherwise channel k.  This reproduces the demo as it is: it normalises the BGR frame with the RGB constants by position and
+ *                swaps afterwards, so the red plane is normalised with 0.406 / 0.225.  fp16 / bf16 outputs are the round-to-nearest-even of that fp32 value.
+ *  5 outputs     center_scale_out [p] = cx, cy, scale_x, scale_y of rule 1: what kasf_heatmap_keypoints takes as KASF_GEOM_CENTER_SCALE for the heatmaps of this crop.
+ *  6 determinism no atomics; a person's result depends on its geom row and its frame alone, not on n or its place in the batch; the same bits from run to run.
+ * NOT VERIFIED: rules 2 and 3 restate OpenCV's portable (non-SIMD) warpAffine / remap from its documented arithmetic; no OpenCV build was available to
+ * record a crop from, so equality with a particular cv2 build is unverified.  Rule 1 stands in for cv2.getAffineTransform's solve and cv2.warpAffine's own inversion of the
+ * forward matrix; against the fp64 inverse of the reference's forward matrix kx, ky, bx, by agree to 1e-12 relative (tests/test_crop_cpu.py).
+ * n = 0 does nothing.  Error 2, before a device or a device pointer is touched: n < 0; out_w or out_h outside 1..32767; Hf or Wf outside 1..32767; n_frames < 1;
+ * row_stride < 3 * Wf; a negative frame_stride with n_frames > 1; an unknown out_dtype or geom_kind; aspect <= 0 (or NaN) with KASF_GEOM_BOX; mean_std null, or a std that is 0
+ * or not finite; with n > 0 a null frames, geom or out, or a null frame_index with n_frames > 1. */
+int kasf_crop_persons(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, const int32_t* frame_index,
+                      const float* geom, int32_t geom_kind, double aspect, int64_t n, void* out, int32_t out_dtype, int32_t out_w, int32_t out_h,
+                      const float* mean_std, int32_t swap_rb, float* center_scale_out, void* stream);
 
 /* debugging / tests: locate a named activation inside the workspace (see kasf_ws_name()) */
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags);

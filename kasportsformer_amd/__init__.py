@@ -26,6 +26,9 @@ Public surface mirrors the reference's interface for this path:
   detections_to_boxes,                  demo/lib/yolov3/human_detector.py:116-168, demo/lib/yolov3/util.py:34-81,107-225, demo/lib/yolov3/bbox.py:51-78 (a YOLOv3
   yolo_heads_to_boxes, YOLOV3_ANCHORS   person detector's output -> person boxes in frame pixels, on the device: threshold, persons only, sort, greedy NMS,
                                         un-letterbox; what `heatmaps_to_keypoints(boxes=...)` takes)
+  crop_persons                          demo/lib/hrnet/lib/utils/utilitys.py:139-169, demo/lib/hrnet/gen_kpts.py:152-157 (person boxes -> the pose network's
+                                        normalised input crops, on the device: affine crop with bilinear sampling, ToTensor, Normalize, channel swap;
+                                        its center / scale are what `heatmaps_to_keypoints` takes)
   poses_to_world, DEMO_CAMERA_ROTATION  demo/lib/utils.py:55-73, demo/demo.py:242-248 (camera space -> world space, floor, unit scale; `--world`)
 """
 from .model import (KASportsFormer, load_model, set_single_stream, is_single_stream, set_deterministic, is_deterministic, set_fused_attention_backward,
@@ -45,10 +48,11 @@ from .stream import StreamLifter
 from .pose import coco_to_h36m, poses_to_world, DEMO_CAMERA_ROTATION
 from .heatmap import heatmaps_to_keypoints
 from .detect import detections_to_boxes, yolo_heads_to_boxes, DetectResult, YOLOV3_ANCHORS, YOLOV3_MASKS
+from .crop import crop_persons, CropResult
 
 __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_stream", "set_deterministic", "is_deterministic", "set_fused_attention_backward", "is_fused_attention_backward", "loss3", "FusedAdamW", "DataParallel", "joint_flip", "predict_flip_tta", "clip_metrics", "Evaluator",
            "evaluate_one_epoch", "PackedClips", "DeviceClipLoader", "pack_clip_directory", "read_clip_file", "shard_indices",
            "checkpoint_save", "checkpoint_load", "strip_module_prefix", "adamw_state_dict", "load_adamw_state_dict", "warmup_lr", "apply_warmup", "ReduceLROnPlateau", "train_one_epoch",
            "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample",
            "lift_track", "lift_tracks", "window_plan", "StreamLifter", "coco_to_h36m", "poses_to_world", "DEMO_CAMERA_ROTATION", "heatmaps_to_keypoints",
-           "detections_to_boxes", "yolo_heads_to_boxes", "DetectResult", "YOLOV3_ANCHORS", "YOLOV3_MASKS"]
+           "detections_to_boxes", "yolo_heads_to_boxes", "DetectResult", "YOLOV3_ANCHORS", "YOLOV3_MASKS", "crop_persons", "CropResult"]

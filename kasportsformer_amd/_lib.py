@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KASF_LIB") or os.path.join(_HERE, "libkasf_hip.so")
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
-DTYPE_F16 = 2                          # KASF_DTYPE_F16: heatmap input only (kasf_heatmap_keypoints)
+DTYPE_F16 = 2                          # KASF_DTYPE_F16: heatmap / detector input and crop output only, no model runs in it
 GEOM_CENTER_SCALE, GEOM_BOX = 0, 1
 LAYOUT_COCO, LAYOUT_H36M = 0, 1
 DETECT_PREDICTION, DETECT_HEADS = 0, 1
@@ -85,6 +85,7 @@ SIGNATURES = {
     "kasf_coco_h36m": (_i32, [_vp, _i64, _vp, _vp]),
     "kasf_pose_world": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "kasf_heatmap_keypoints": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i32, C.c_double, _i32, _i32, _vp, _vp, _vp]),
+    "kasf_crop_persons": (_i32, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _i32, C.c_double, _i64, _vp, _i32, _i32, _i32, C.POINTER(_f32), _i32, _vp, _vp]),
     "kasf_detect_workspace_bytes": (_i64, [_i32, _i64, _i32]),
     "kasf_detect_boxes": (_i32, [_vp, _i32, _i32, _i32, _i32, _pi32, _i32, _i32, C.POINTER(_f32), _i32, _vp, _f32, _f32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
                                  _i64, _vp]),

@@ -1176,6 +1176,30 @@ int kasf_heatmap_keypoints(const void* hm, int32_t dtype, int64_t n, int32_t H, 
     return 0;
 }
 
+// ---- person boxes -> pose-network inputs (kasf.h, kasf_crop_persons) ----
+int kasf_crop_persons(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, const int32_t* frame_index,
+                      const float* geom, int32_t geom_kind, double aspect, int64_t n, void* out, int32_t out_dtype, int32_t out_w, int32_t out_h,
+                      const float* mean_std, int32_t swap_rb, float* center_scale_out, void* stream) {
+    if (n < 0) return kasf_set_error(2, "crop_persons: n must be >= 0");
+    if (out_w < 1 || out_h < 1 || out_w > 32767 || out_h > 32767) return kasf_set_error(2, "crop_persons: out_w and out_h must be in [1, 32767]");
+    if (Hf < 1 || Hf > 32767 || Wf < 1 || Wf > 32767) return kasf_set_error(2, "crop_persons: Hf and Wf must be in [1, 32767]");
+    if (n_frames < 1) return kasf_set_error(2, "crop_persons: n_frames must be >= 1");
+    if (row_stride < (int64_t)3 * Wf) return kasf_set_error(2, "crop_persons: the row stride must be at least 3 * Wf bytes");
+    if (n_frames > 1 && frame_stride < 0) return kasf_set_error(2, "crop_persons: the frame stride must be >= 0");
+    if (out_dtype != KASF_F32 && out_dtype != KASF_F16 && out_dtype != KASF_BF16) return kasf_set_error(2, "crop_persons: out_dtype must be KASF_DTYPE_F32, _F16 or _BF16");
+    if (geom_kind != KASF_GEOM_CENTER_SCALE && geom_kind != KASF_GEOM_BOX) return kasf_set_error(2, "crop_persons: geom_kind must be KASF_GEOM_CENTER_SCALE or KASF_GEOM_BOX");
+    if (geom_kind == KASF_GEOM_BOX && !(aspect > 0.0)) return kasf_set_error(2, "crop_persons: aspect must be > 0 with KASF_GEOM_BOX");
+    if (!mean_std) return kasf_set_error(2, "null pointer argument");
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(mean_std[3 + c]) || mean_std[3 + c] == 0.0f) return kasf_set_error(2, "crop_persons: every std must be finite and not 0");
+    if (n == 0) return 0;
+    if (!frames || !geom || !out || (n_frames > 1 && !frame_index)) return kasf_set_error(2, "null pointer argument");
+    kasf_launch_crop_persons((hipStream_t)stream, frames, n_frames, Hf, Wf, row_stride, frame_stride, frame_index, geom, geom_kind, aspect, n, out, out_dtype,
+                             out_w, out_h, mean_std, swap_rb ? 1 : 0, center_scale_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // ---- detector output -> person boxes (kasf.h, kasf_detect_boxes) ----
 static const char* detect_shape_error(int32_t batch, int64_t n_per_image, int32_t max_candidates) {
     if (batch < 0 || batch > 65535) return "detect: batch must be in [0, 65535]";

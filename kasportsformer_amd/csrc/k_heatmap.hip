@@ -12,6 +12,7 @@
 // the person's crop geometry and applies the inverse crop affine in fp64: 2 of the 34 coordinates of a person.  The library is built with
 // -ffp-contract=off, so every expression below rounds where the reference's numpy expression rounds.
 #include "kernels.h"
+#include "crop_geom.h"
 
 #include <climits>
 
@@ -99,30 +100,12 @@ __global__ __launch_bounds__(HM_THREADS) void k_heatmap_keypoints(const typename
             x = x + sign_of(Elem<E>::up(c[1]) - Elem<E>::up(c[-1])) * 0.25f;
             y = y + sign_of(Elem<E>::up(c[W]) - Elem<E>::up(c[-W])) * 0.25f;
         }
-        // the person's crop: center and scale[0] as fp32, given or from the box (box_to_center_scale, utilitys.py:102-135, in fp64 on the upcast box)
-        const float* g = geom + (m / 17) * 4;
-        float cx, cy, sx;
-        if (geom_kind == 0) {
-            cx = g[0]; cy = g[1]; sx = g[2];
-        } else {
-            const double x1 = g[0], y1 = g[1], x2 = g[2], y2 = g[3];
-            double bw = x2 - x1, bh = y2 - y1;
-            cx = (float)(x1 + bw * 0.5);
-            cy = (float)(y1 + bh * 0.5);
-            if (bw > aspect * bh) bh = bw * 1.0 / aspect;
-            else if (bw < aspect * bh) bw = bh * aspect;
-            (void)bh;                                           // scale[1] never enters transform_preds
-            sx = (float)(bw * 1.0 / 200.0);
-            if (cx != -1.0f) sx = sx * 1.25f;
-        }
-        // transform_preds with rot = 0 (transforms.py:50-101): three anchor points stored as fp32, the affine through them solved and applied in fp64
-        const float sw = sx * 200.0f;                                        // scale_tmp[0]
-        const float s1y = (float)((double)cy + (double)(sw * -0.5f));        // src[1, 1] = center + src_dir, an fp64 sum stored as fp32
-        const float dy = cy - s1y;                                           // get_3rd_point: direct = src[0] - src[1]
-        const float s2x = cx + (-dy);                                        // src[2, 0] = src[1, 0] - direct[1]
+        // the person's crop: center and scale[0] as fp32, given or from the box (box_to_center_scale), and transform_preds with rot = 0 (transforms.py:50-101):
+        // three anchor points stored as fp32, the affine through them solved in fp64 (crop_geom.h, shared with k_crop.hip) and applied in fp64
+        const KasfCropGeom cg = kasf_crop_geom(geom + (m / 17) * 4, geom_kind, aspect, W);
+        const float cx = cg.cx, cy = cg.cy;
+        const double kx = cg.kx, ky = cg.ky;
         const double half_w = (double)W * 0.5, half_h = (double)H * 0.5;
-        const double kx = ((double)cx - (double)s2x) / half_w;
-        const double ky = ((double)cy - (double)s1y) / half_w;              // both axes divide by W / 2
         float* o = out + m * 3;
         o[0] = (float)((double)cx + ((double)x - half_w) * kx);
         o[1] = (float)((double)cy + ((double)y - half_h) * ky);

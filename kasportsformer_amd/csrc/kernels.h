@@ -198,6 +198,12 @@ void kasf_launch_pose_world(hipStream_t s, const float* poses, int64_t frames, c
 void kasf_launch_heatmap_keypoints(hipStream_t s, const void* hm, int dtype, int64_t n, int H, int W, const float* geom, int geom_kind, double aspect,
                                    int refine, float* out);
 
+// ---- k_crop.hip: person boxes -> pose-network inputs (kasf.h, kasf_crop_persons): frames uint8 [n_frames][Hf][Wf][3] with byte strides, geom as k_heatmap.hip takes it,
+// out [n,3,out_h,out_w] of out_dtype, mean_std = six HOST floats passed by value into the launch, center_scale_out [n,4] fp32 or null.  Arguments as checked by the entry point ----
+void kasf_launch_crop_persons(hipStream_t s, const void* frames, int n_frames, int Hf, int Wf, int64_t row_stride, int64_t frame_stride,
+                              const int* frame_index, const float* geom, int geom_kind, double aspect, int64_t n, void* out, int out_dtype, int out_w,
+                              int out_h, const float* mean_std, int swap_rb, float* center_scale_out);
+
 // ---- k_detect.hip: YOLOv3 detector output -> person boxes (kasf.h, kasf_detect_boxes): a selection launch (every candidate's key slot, the box and score slots of the
 // passing ones) and one sort + NMS + output workgroup per image.  Arguments as checked by the entry point; returns nullptr or a message when the launch cannot be made ----
 #define KASF_DETECT_FORM_PREDICTION 0
