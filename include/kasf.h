@@ -38,6 +38,9 @@
  *   kasf_crop_persons      <- PreProcess: box_to_center_scale, get_affine_transform, cv2.warpAffine, ToTensor, Normalize and the [2, 1, 0] channel swap: what the
  *                             demo does on the host between the person boxes and HRNet's input tensor
  *                             demo/lib/hrnet/lib/utils/utilitys.py:139-169, demo/lib/hrnet/gen_kpts.py:152-157, demo/lib/hrnet/lib/utils/transforms.py:58-101
+ *   kasf_sort_update       <- Sort.update (KalmanBoxTracker, associate_detections_to_trackers, iou) and, from gen_video_kpts, the empty-frame hold and the
+ *                             num_person oldest tracks: what the demo does on the host between the person boxes and the crops
+ *                             demo/lib/sort/sort.py:15-222, demo/lib/hrnet/gen_kpts.py:111-148
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
  *   kasf_op_gcn_fwd, kasf_op_gcn_bwd <- GCN.forward between its U | V Linear and the residual, and autograd of it   model/modules/graph.py:19-134, KASportsFormer.py:109
  */
@@ -389,6 +392,61 @@ int kasf_detect_boxes(const void* const* src, int32_t n_src, int32_t form, int32
 int kasf_crop_persons(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, const int32_t* frame_index,
                       const float* geom, int32_t geom_kind, double aspect, int64_t n, void* out, int32_t out_dtype, int32_t out_w, int32_t out_h,
                       const float* mean_std, int32_t swap_rb, float* center_scale_out, void* stream);
+
+/* ---- person boxes -> tracked person boxes (ABI 12): the SORT tracker of demo/lib/sort/sort.py, one launch per tick, no host synchronisation ----
+ * state: kasf_sort_state_bytes(streams, slots, max_dets) bytes on the device, 8-byte aligned; ALL ZERO IS AN EMPTY TRACKER, so creating and resetting it (or one
+ * stream's part: the bytes divide evenly by streams) is a memset.  Per stream: int32 [16] header (tracks, next id, ticks, held detections, 0 ...), then per list
+ * position p < slots x fp64 [7][slots], P fp64 [13][slots] (blocks k < 3 = (cx,vx), (cy,vy), (s,vs): 4k = pos-pos, 4k+1 = pos-vel, 4k+2 = vel-pos, 4k+3 = vel-vel;
+ * 12 = r-r), int32 [6][slots] = id, slot, time_since_update, hits, hit_streak, age, then the held detections fp32 [max_dets][4].
+ * dets [streams][det_rows][>= 4] fp32 (device; det_rows <= max_dets, the capacity the state was sized for) = x1, y1, x2, y2 in the first four columns, element strides det_stream_stride and det_row_stride (>= 4; columns are
+ * adjacent): kasf_detect_boxes' boxes [B][max_boxes][6] as they are.  det_count [streams] int32 (device; NULL = every row): rows that count, clamped to
+ * [0, det_rows].  Outputs (device), rows newest track first as Sort.update returns them: boxes [streams][slots][4] fp32 (what kasf_crop_persons takes as
+ * KASF_GEOM_BOX), ids (the track's id + 1), slot, born [streams][slots] int32, count, dropped, person_count [streams] int32, persons [streams][num_person][4] fp32.
+ * Rows past count are 0 with id -1; rows of persons past person_count are 0.
+ *
+ * EACH TRACK (sort.py:61-122).  x[7] = (cx, cy, s = w h, r = w / h, vx, vy, vs) and P[7][7], fp64.  F = I with F[0][4] = F[1][5] = F[2][6] = 1, H = the first four
+ * rows of I, R = diag(1, 1, 10, 10), P0 = diag(10, 10, 10, 10, 1e4, 1e4, 1e4), Q = diag(1, 1, 1, 1, 0.01, 0.01, 0.01 * 0.01) (sort.py:72-85).
+ *  predict     if x[6] + x[2] <= 0 then x[6] *= 0; x = F x; P = F P F^T + Q; age += 1; if time_since_update > 0 then hit_streak = 0; time_since_update += 1.
+ *  update      z = (x1 + w / 2, y1 + h / 2, w h, w / h) with w = x2 - x1, h = y2 - y1 of the detection widened to fp64; then y = z - H x, S = H P H^T + R,
+ *              K = P H^T S^-1, x = x + K y, P = (I - K H) P (I - K H)^T + K R K^T; time_since_update = 0, hits += 1, hit_streak += 1.  filterpy is not
+ *              installed where this was written: the update is RESTATED from the published form of filterpy's KalmanFilter.update, not recorded from it.
+ *  box         w = sqrt(x[2] x[3]), h = x[2] / w, corners cx -+ w / 2, cy -+ h / 2.
+ * With this F and H and a diagonal P0, P keeps the blocks (cx,vx), (cy,vy), (s,vs) and the scalar r: every other entry is an exact 0 (tests/test_track_cpu.py
+ * holds the dense form to that on every test sequence), S is diagonal and S^-1 is four reciprocals.  The kernel carries the 13 numbers of the blocks and leaves out
+ * the products with the exact zeros and ones of F and H, which change no finite value; what remains is the dense form's sequence, with contraction off.
+ *
+ * EACH TICK, per stream, in the reference's order (sort.py:177-222):
+ *  1 ticks += 1; predict every track.
+ *  2 IoU of every detection (bb_test) against every predicted box (bb_gt) as sort.py:16-30 in fp64, stored rounded to fp32.
+ *  3 the assignment of min(detections, tracks) pairs that maximises the sum of those fp32 values (scipy.optimize.linear_sum_assignment of the negated matrix).
+ *  4 a pair whose fp32 IoU is below (float)iou_threshold is unmatched again.
+ *  5 matched tracks update with their detection.
+ *  6 unmatched detections found tracks, appended to the list: first those outside the assignment by ascending index, then those unmatched by rule 4 by
+ *    ascending index (scipy returns its rows sorted).  A new track takes the stream's next id and the smallest slot in [0, slots) that no track of the list holds;
+ *    it keeps that slot until it dies.  born = 1 on this tick.
+ *  7 the list is walked newest first: a track is emitted iff time_since_update < 1 and (hit_streak >= min_hits or ticks <= min_hits), with its box from the
+ *    updated state; then it is removed iff time_since_update > max_age.  The list keeps its order.
+ * From gen_video_kpts (gen_kpts.py:125-143): with hold_last != 0 a tick without a valid detection runs on the stream's last non-empty set of valid detections
+ * (bboxs_pre; none yet: on none); persons[k] = the k-th OLDEST emitted track, k < person_count = min(count, num_person): people_track[-num_person:][::-1].  The
+ * host-side round(i, 2) is not applied.
+ *
+ * DELIBERATELY UNLIKE THE REFERENCE.
+ *  - The id counter is per stream; the reference's is one class attribute shared by every Sort object of the process.
+ *  - A track whose predicted box has a non-finite coordinate is dropped in step 1.  The reference masks inf rows out of the matrix but pops only NaN ones, after
+ *    which its matrix columns no longer line up with its list.
+ *  - A detection with a non-finite coordinate or h <= 0 is ignored (it is not part of "the detections" above).  An IoU that is not finite counts as 0.
+ *  - Where two assignments have exactly equal sums the choice is this kernel's (shortest augmenting paths, rows = the smaller side in ascending order, among
+ *    equal path costs an unassigned column first, then the lower index), which need not be scipy's; scipy promises none.
+ *  - When the list is full (slots tracks), further births of step 6 are dropped in that order, take no id, and are counted in dropped.
+ *
+ * streams = 0 does nothing.  Error 2, before a device or a device pointer is touched: streams outside 0..65535; slots or max_dets outside 1..64 (a track and a
+ * detection each take one lane of a wavefront); det_rows outside 0..max_dets; det_row_stride < 4; det_stream_stride < 0; max_age or min_hits < 0; iou_threshold not finite; num_person outside
+ * 1..65535; with streams > 0 a null pointer other than det_count (and dets when det_rows = 0), or a state that is not 8-byte aligned.  kasf_sort_state_bytes returns -2 for the first three. */
+#define KASF_SORT_MAX 64
+int64_t kasf_sort_state_bytes(int32_t streams, int32_t slots, int32_t max_dets);
+int kasf_sort_update(void* state, int32_t streams, int32_t slots, int32_t max_dets, const float* dets, int32_t det_rows, int64_t det_stream_stride, int64_t det_row_stride,
+                     const int32_t* det_count, int32_t max_age, int32_t min_hits, float iou_threshold, int32_t num_person, int32_t hold_last, float* boxes,
+                     int32_t* ids, int32_t* slot, int32_t* born, int32_t* count, int32_t* dropped, float* persons, int32_t* person_count, void* stream);
 
 /* debugging / tests: locate a named activation inside the workspace (see kasf_ws_name()) */
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags);

@@ -18,6 +18,8 @@ GEOM_CENTER_SCALE, GEOM_BOX = 0, 1
 LAYOUT_COCO, LAYOUT_H36M = 0, 1
 DETECT_PREDICTION, DETECT_HEADS = 0, 1
 DETECT_MAX_CANDIDATES = 4096           # KASF_DETECT_MAX_CANDIDATES
+SORT_MAX = 64                          # KASF_SORT_MAX: slots and max_dets of kasf_sort_update
+SORT_HEADER_BYTES = 64                 # KASF_SORT_HEADER_BYTES
 FLAG_TRAIN, FLAG_RETURN_REP, FLAG_KEEP = 1, 2, 4
 EVAL_COLS = 22
 GCN_STAT_WORDS = 4 * 512 * 5     # KASF_GCN_STAT_WORDS: int64 words of one BatchNorm statistics buffer of kasf_op_gcn_fwd / kasf_op_gcn_bwd
@@ -89,6 +91,8 @@ SIGNATURES = {
     "kasf_detect_workspace_bytes": (_i64, [_i32, _i64, _i32]),
     "kasf_detect_boxes": (_i32, [_vp, _i32, _i32, _i32, _i32, _pi32, _i32, _i32, C.POINTER(_f32), _i32, _vp, _f32, _f32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
                                  _i64, _vp]),
+    "kasf_sort_state_bytes": (_i64, [_i32, _i32, _i32]),
+    "kasf_sort_update": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i64, _i64, _vp, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kasf_ws_entries": (_i32, [_vp, _i32, _i32]),
     "kasf_ws_entry": (_i32, [_vp, _i32, _i32, _i32, C.c_char_p, _i32, _pi64, _pi64, _pi32]),
     "kasf_op_linear": (_i32, [_i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),

@@ -1249,6 +1249,36 @@ int kasf_detect_boxes(const void* const* src, int32_t n_src, int32_t form, int32
     return 0;
 }
 
+// ---- person boxes -> tracked person boxes (kasf.h, kasf_sort_update) ----
+static const char* sort_shape_error(int32_t streams, int32_t slots, int32_t max_dets) {
+    if (streams < 0 || streams > 65535) return "sort: streams must be in [0, 65535]";
+    if (slots < 1 || slots > KASF_SORT_MAX) return "sort: slots must be in [1, 64] (one lane of a wavefront per track)";
+    if (max_dets < 1 || max_dets > KASF_SORT_MAX) return "sort: max_dets must be in [1, 64] (one lane of a wavefront per detection)";
+    return nullptr;
+}
+int64_t kasf_sort_state_bytes(int32_t streams, int32_t slots, int32_t max_dets) {
+    if (const char* e = sort_shape_error(streams, slots, max_dets)) return -(int64_t)kasf_set_error(2, e);
+    return (int64_t)streams * kasf_sort_stream_bytes(slots, max_dets);
+}
+int kasf_sort_update(void* state, int32_t streams, int32_t slots, int32_t max_dets, const float* dets, int32_t det_rows, int64_t det_stream_stride, int64_t det_row_stride,
+                     const int32_t* det_count, int32_t max_age, int32_t min_hits, float iou_threshold, int32_t num_person, int32_t hold_last, float* boxes,
+                     int32_t* ids, int32_t* slot, int32_t* born, int32_t* count, int32_t* dropped, float* persons, int32_t* person_count, void* stream) {
+    if (const char* e = sort_shape_error(streams, slots, max_dets)) return kasf_set_error(2, e);
+    if (det_rows < 0 || det_rows > max_dets) return kasf_set_error(2, "sort_update: det_rows must be in [0, max_dets]");
+    if (det_row_stride < 4) return kasf_set_error(2, "sort_update: the detection row stride must be at least 4 elements");
+    if (det_stream_stride < 0) return kasf_set_error(2, "sort_update: the detection stream stride must be >= 0");
+    if (max_age < 0 || min_hits < 0) return kasf_set_error(2, "sort_update: max_age and min_hits must be >= 0");
+    if (!std::isfinite(iou_threshold)) return kasf_set_error(2, "sort_update: iou_threshold must be finite");
+    if (num_person < 1 || num_person > 65535) return kasf_set_error(2, "sort_update: num_person must be in [1, 65535]");
+    if (streams == 0) return 0;
+    if (!state || (!dets && det_rows > 0) || !boxes || !ids || !slot || !born || !count || !dropped || !persons || !person_count) return kasf_set_error(2, "null pointer argument");
+    if (((uintptr_t)state & 7) != 0) return kasf_set_error(2, "sort_update: state must be 8-byte aligned");
+    kasf_launch_sort_update((hipStream_t)stream, state, streams, slots, max_dets, dets, det_rows, det_stream_stride, det_row_stride, det_count, max_age, min_hits,
+                            iou_threshold, num_person, hold_last ? 1 : 0, boxes, ids, slot, born, count, dropped, persons, person_count);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 #define OP_DT_CHECK(dt) \
     if ((dt) != KASF_F32 && (dt) != KASF_BF16) return kasf_set_error(3, "bad dtype")
 

@@ -219,6 +219,18 @@ const char* kasf_launch_detect_boxes(hipStream_t s, const void* const* src, int 
                                      const float* anchors, int inp_dim, const float* frame_wh, float confidence, float nms, int class_id, int max_candidates,
                                      int max_boxes, float* boxes, int* index, int* count, void* workspace);
 
+// ---- k_track.hip: person boxes -> tracked person boxes (kasf.h, kasf_sort_update): one wave64 workgroup per stream, one launch per tick.  Per stream the state is
+// header int32 [16] (tracks, next id, ticks, held detections, 0...) | x fp64 [7][slots] | P fp64 [13][slots] | id, slot, time_since_update, hits, hit_streak, age
+// int32 [6][slots] | held detections fp32 [max_dets][4]; all zero = an empty tracker.  Arguments as checked by the entry point ----
+#ifndef KASF_SORT_MAX
+#define KASF_SORT_MAX 64
+#endif
+#define KASF_SORT_HEADER_BYTES 64
+int64_t kasf_sort_stream_bytes(int64_t slots, int64_t max_dets);
+void kasf_launch_sort_update(hipStream_t s, void* state, int B, int slots, int max_dets, const float* dets, int det_rows, int64_t det_bstride, int64_t det_rstride,
+                             const int* det_count, int max_age, int min_hits, float iou_threshold, int num_person, int hold_last, float* boxes, int* ids,
+                             int* slot, int* born, int* count, int* dropped, float* persons, int* person_count);
+
 // ---- k_gemm2.hip (bf16, persistent, register-resident weights) ----
 // bf16 partial tiles a fused data + weight gradient launch left: out[e] += sum over z < nparts of part[z][e], e < elems (elems a multiple of 128)
 // ---- persistent launches narrower than the chip (round 4) ----
