@@ -538,6 +538,55 @@ int kasf_op_gcn_fwd(int32_t dtype, const void* x_in, const void* xn, const void*
  * (0: mean and variance are constants, duv has no batch-mean terms). */
 int kasf_op_gcn_bwd(int32_t dtype, const void* g, const void* xn, const void* y, const float* coef, const uint32_t* mask, const float* ls1, void* r, void* duv,
                     float* dls1, float* d_bn_w, float* d_bn_b, void* bstats, int32_t batch, int32_t n_frames, int32_t mode, int32_t training, void* stream);
+/* ---- the prologue, gate, head and embedding kernels on their own (ADDED under ABI 12: additive, kasf_version() stays 12; a library without them fails to load on
+ * the missing symbol).  Thin entries over the launches kasf_forward / kasf_backward make (k_misc.hip, k_reduce.hip), for unit tests against fp64 math.
+ * Tensors of the model dtype are void*, everything else fp32.  frames = clips * n_frames, M = frames * 17 tokens in [clip][frame][joint] order.
+ * scratch / scratch_floats (embed_bwd, refusion_bwd, gate_bwd, head_bwd): device floats, 16-byte aligned, at least kasf_op_misc_scratch_floats(op, n).  Given: every
+ * workgroup stores its sums as one row of it and the entry finishes them in a fixed order on `stream` (what a backward stage does: bit-reproducible).  NULL: fp32
+ * atomics.  Scratch that is too small: the launch falls back to the atomics (results still complete) and the entry returns error 6.
+ * Gradients of parameters (dw, db, dpos, dls, grads) are ACCUMULATED into; everything else is written.
+ * Error 2, before any device is touched: a required pointer that is null, frames < 1 or frames * 17 * 384 >= 2^31, M < 1 or M * 384 >= 2^31, scratch with
+ * scratch_floats < 1 or misaligned, n of kasf_op_add not a multiple of 8 in [8, 2^40), (N, K) of kasf_op_finalize_ls other than (128, 128) / (128, 512).  Error 3: bad
+ * dtype.  Error 4: a layout-only model where the entry needs the device tables (prologue_fwd, refusion_bwd). */
+#define KASF_MISC_EMBED_BWD 0
+#define KASF_MISC_REFUSION_BWD 1
+#define KASF_MISC_GATE_BWD 2
+#define KASF_MISC_HEAD_BWD 3
+/* floats of scratch the op asks for at n = frames (embed, refusion) or M (gate, head); -2 with kasf_last_error() set for an unknown op or n < 1.  Needs no device. */
+int64_t kasf_op_misc_scratch_floats(int32_t op, int64_t n);
+/* x [frames,17,3] -> bone3 [frames,17,3] (direction x, y, length per bone, zero length -> 1; row 16 = mean of the 16), limb3 [frames,17,3] (the 51 limb MLPs on the raw
+ * joints), xj / xb / xl [frames*17,128] model dtype = Linear(3,128)(x / bone3 / limb3) + position embedding.  params: the flat fp32 parameter array of `model`. */
+int kasf_op_prologue_fwd(const kasf_model* model, const float* params, const float* x, void* xj, void* xb, void* xl, float* bone3, float* limb3, int64_t frames,
+                         void* stream);
+/* backward of one embedding: g [frames*17,128] model dtype, in3 [frames*17,3], w [128,3] -> dw [128,3], db [128], dpos [17,128] accumulated; din3 [frames*17,3] = g . w
+ * written when not NULL. */
+int kasf_op_embed_bwd(int32_t dtype, const void* g, const float* in3, const float* w, float* dw, float* db, float* dpos, float* din3, int64_t frames,
+                      float* scratch, int64_t scratch_floats, void* stream);
+/* backward of the 51 limb MLPs: x [frames,17,3] raw joints, dlimb3 [frames,17,3] -> the 204 limb-MLP tensors of grads (flat, laid out as params) accumulated; nothing
+ * else of grads is touched. */
+int kasf_op_refusion_bwd(const kasf_model* model, const float* params, const float* x, const float* dlimb3, float* grads, int64_t frames, float* scratch,
+                         int64_t scratch_floats, void* stream);
+/* alpha = softmax(cat(xa, xg, xb) w^T + bias) (w [3,384], bias [3]; adaptive == 0: 1/3 each), out = sum_k alpha_k x_k.  alpha [M,4] fp32 (slot 3 unused, not
+ * written) or NULL. */
+int kasf_op_gate_fwd(int32_t dtype, const void* xa, const void* xg, const void* xb, const float* w, const float* bias, void* out, float* alpha, int64_t M,
+                     int32_t adaptive, void* stream);
+/* gradients of the above for g (+ g1 + g2 when not NULL) = d/d(out), alpha as the forward stored it (16-byte aligned): ga / gg / gb [M,128] written; dw [3,384], db [3]
+ * accumulated (adaptive == 0: untouched, may be NULL). */
+int kasf_op_gate_bwd(int32_t dtype, const void* g, const void* g1, const void* g2, const void* xa, const void* xg, const void* xb, const float* w,
+                     const float* alpha, void* ga, void* gg, void* gb, float* dw, float* db, int64_t M, int32_t adaptive, float* scratch,
+                     int64_t scratch_floats, void* stream);
+/* out [M,3] fp32 = rep w^T + bias; rep [M,512] model dtype = tanh features, w [3,512]. */
+int kasf_op_head_fwd(int32_t dtype, const void* rep, const float* w, const float* bias, float* out, int64_t M, void* stream);
+/* dy [M,3] fp32 -> dpre [M,512] model dtype = (dy w) (1 - rep^2) written; dw [3,512], db [3] accumulated. */
+int kasf_op_head_bwd(int32_t dtype, const float* dy, const void* rep, const float* w, void* dpre, float* dw, float* db, int64_t M, float* scratch,
+                     int64_t scratch_floats, void* stream);
+/* return_rep backward: dpre [M,512] = drep (fp32) (1 - rep^2). */
+int kasf_op_rep_bwd(int32_t dtype, const float* drep, const void* rep, void* dpre, int64_t M, void* stream);
+/* layer-scale finish of a Linear [N,K] whose output is multiplied by ls [N]: in dw = unscaled g^T a, db = colsum(g); dls[n] += sum_k w[n][k] dw[n][k] + bias[n] db[n];
+ * then dw[n][:] *= ls[n], db[n] *= ls[n] in place. */
+int kasf_op_finalize_ls(float* dw, const float* w, const float* bias, const float* ls, float* db, float* dls, int32_t N, int32_t K, void* stream);
+/* n elements of the model dtype: b == NULL: dst += a (c must be NULL too); otherwise dst = a + b (+ c when not NULL). */
+int kasf_op_add(int32_t dtype, void* dst, const void* a, const void* b, const void* c, int64_t n, void* stream);
 /* fp32 <-> model dtype */
 int kasf_op_cast(int32_t dtype, const void* src, void* dst, int64_t n, int32_t to_f32, void* stream);
 

@@ -22,6 +22,7 @@ SORT_MAX = 64                          # KASF_SORT_MAX: slots and max_dets of ka
 SORT_HEADER_BYTES = 64                 # KASF_SORT_HEADER_BYTES
 FLAG_TRAIN, FLAG_RETURN_REP, FLAG_KEEP = 1, 2, 4
 EVAL_COLS = 22
+MISC_EMBED_BWD, MISC_REFUSION_BWD, MISC_GATE_BWD, MISC_HEAD_BWD = 0, 1, 2, 3      # KASF_MISC_*: ops of kasf_op_misc_scratch_floats
 GCN_STAT_WORDS = 4 * 512 * 5     # KASF_GCN_STAT_WORDS: int64 words of one BatchNorm statistics buffer of kasf_op_gcn_fwd / kasf_op_gcn_bwd
 ABI_VERSION = 12        # kasf_version() of the library these prototypes describe (a stale in-tree .so is refused)
 
@@ -108,6 +109,17 @@ SIGNATURES = {
     "kasf_op_attention_bwd_fused_do": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "kasf_op_gcn_fwd": (_i32, [_i32] + [_vp] * 13 + [_i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "kasf_op_gcn_bwd": (_i32, [_i32] + [_vp] * 12 + [_i32, _i32, _i32, _i32, _vp]),
+    "kasf_op_misc_scratch_floats": (_i64, [_i32, _i64]),
+    "kasf_op_prologue_fwd": (_i32, [_vp] * 8 + [_i64, _vp]),
+    "kasf_op_embed_bwd": (_i32, [_i32] + [_vp] * 7 + [_i64, _vp, _i64, _vp]),
+    "kasf_op_refusion_bwd": (_i32, [_vp] * 5 + [_i64, _vp, _i64, _vp]),
+    "kasf_op_gate_fwd": (_i32, [_i32] + [_vp] * 7 + [_i64, _i32, _vp]),
+    "kasf_op_gate_bwd": (_i32, [_i32] + [_vp] * 13 + [_i64, _i32, _vp, _i64, _vp]),
+    "kasf_op_head_fwd": (_i32, [_i32] + [_vp] * 4 + [_i64, _vp]),
+    "kasf_op_head_bwd": (_i32, [_i32] + [_vp] * 6 + [_i64, _vp, _i64, _vp]),
+    "kasf_op_rep_bwd": (_i32, [_i32] + [_vp] * 3 + [_i64, _vp]),
+    "kasf_op_finalize_ls": (_i32, [_vp] * 6 + [_i32, _i32, _vp]),
+    "kasf_op_add": (_i32, [_i32] + [_vp] * 4 + [_i64, _vp]),
     "kasf_op_cast": (_i32, [_i32, _vp, _vp, _i64, _i32, _vp]),
 }
 _EXTRA = {}

@@ -610,6 +610,25 @@ int check_model(const kasf_model* m) {
     return 0;
 }
 
+// the contiguous range of the flat parameter / gradient array that holds the 204 limb-MLP tensors (build_layout): kasf_backward and kasf_op_refusion_bwd
+inline void refusion_grad_range(const KasfProOff& po, int64_t& base, int64_t& end) {
+    base = po.mlp[0][0];
+    end = po.mlp[50][3] + 1;
+}
+// its length, for a caller that sizes a scratch row without a model: the range holds the same 204 tensors from an aligned start in every configuration, so the
+// layout of the smallest one is built once and asked
+inline int refusion_grad_len() {
+    static const int len = [] {
+        kasf_model m;
+        m.cfg = kasf_config{1, 4, 8, 4, 1, KASF_F32};
+        build_layout(&m);
+        int64_t base, end;
+        refusion_grad_range(m.pro, base, end);
+        return (int)(end - base);
+    }();
+    return len;
+}
+
 }  // namespace
 
 // ================================================================================================ C-ABI
@@ -941,7 +960,8 @@ int kasf_backward(const kasf_model* m, const float* params, const void* packed, 
                 if (st != c.s) HIPCHK(hipEventRecord(m->ev_join[sidx], st));
             }
             // the 204 limb-MLP tensors occupy one contiguous range of the gradient array (build_layout): a scratch row mirrors it
-            const int64_t rf_base = po.mlp[0][0], rf_end = po.mlp[50][3] + 1;
+            int64_t rf_base, rf_end;
+            refusion_grad_range(po, rf_base, rf_end);
             kasf_launch_refusion_bwd(c.s, (const float*)c.w(p.x3), (const float*)c.w(p.dlimb3), params, grads, m->d_pro, frames, &sinks[2], rf_base,
                                      (int)(rf_end - rf_base));
             if (!one_stream)
@@ -1412,6 +1432,141 @@ int kasf_op_gcn_bwd(int32_t dtype, const void* g, const void* xn, const void* y,
     const double count = mode == 0 ? (double)batch * n_frames * 128 : (double)batch * 17 * 128;
     kasf_launch_gcn_bwd2(dtype, s, r, y, coef, mode == 1 ? mask : nullptr, duv, batch, n_frames, mode, (const double*)bstats, d_bn_w, d_bn_b, count,
                          training ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// ---- the prologue, gate, head and embedding kernels on their own (kasf.h, kasf_op_prologue_fwd ... kasf_op_add): the engine's own launchers.  scratch != NULL: a local
+// KasfColSink on it and the fixed-order finish on the same stream, as a backward stage does; NULL: the fp32 atomics ----
+#define MISC_TOKENS_CHECK(M, what) \
+    if ((M) < 1 || (int64_t)(M) * 384 >= ((int64_t)1 << 31)) return kasf_set_error(2, what ": 1 <= tokens and tokens * 384 < 2^31")
+#define MISC_FRAMES_CHECK(f) \
+    if ((f) < 1 || (int64_t)(f) * 17 * 384 >= ((int64_t)1 << 31)) return kasf_set_error(2, "frames: 1 <= frames and frames * 17 * 384 < 2^31")
+namespace {
+struct MiscSink {
+    KasfColSink sink;
+    KasfColSink* p;
+    MiscSink(float* scratch, int64_t floats) : p(scratch != nullptr ? &sink : nullptr) { sink.scratch = scratch; sink.cap = floats; }
+    // the finish; error 6 (set by kasf_col_flush) when a launch found the scratch too small and fell back to atomics
+    int finish(hipStream_t s) {
+        if (p == nullptr) return 0;
+        const bool overflow = sink.overflow;
+        kasf_col_flush(s, &p, 1);
+        return overflow ? 6 : 0;
+    }
+};
+int misc_scratch_check(const float* scratch, int64_t floats) {
+    if (scratch != nullptr && floats < 1) return kasf_set_error(2, "scratch_floats must be >= 1 with a scratch pointer");
+    if (scratch != nullptr && ((uintptr_t)scratch & 15) != 0) return kasf_set_error(2, "scratch must be 16-byte aligned");
+    return 0;
+}
+}  // namespace
+int64_t kasf_op_misc_scratch_floats(int32_t op, int64_t n) {
+    if (n < 1) { kasf_set_error(2, "misc_scratch_floats: n must be >= 1"); return -2; }
+    const int64_t r = kasf_misc_scratch_floats(op, n, refusion_grad_len());
+    if (r < 0) { kasf_set_error(2, "misc_scratch_floats: unknown op"); return -2; }
+    return r;
+}
+int kasf_op_prologue_fwd(const kasf_model* m, const float* params, const float* x, void* xj, void* xb, void* xl, float* bone3, float* limb3, int64_t frames,
+                         void* stream) {
+    if (check_model(m)) return 2;
+    if (!params || !x || !xj || !xb || !xl || !bone3 || !limb3) return kasf_set_error(2, "null pointer argument");
+    MISC_FRAMES_CHECK(frames);
+    if (m->d_pro == nullptr) return kasf_set_error(4, "layout-only model cannot run");
+    kasf_launch_prologue_fwd(m->cfg.dtype, (hipStream_t)stream, x, params, m->d_pro, xj, xb, xl, bone3, limb3, frames);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int kasf_op_embed_bwd(int32_t dtype, const void* g, const float* in3, const float* w, float* dw, float* db, float* dpos, float* din3, int64_t frames,
+                      float* scratch, int64_t scratch_floats, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!g || !in3 || !w || !dw || !db || !dpos) return kasf_set_error(2, "null pointer argument");
+    MISC_FRAMES_CHECK(frames);
+    if (misc_scratch_check(scratch, scratch_floats)) return 2;
+    MiscSink ms(scratch, scratch_floats);
+    kasf_launch_embed_bwd(dtype, (hipStream_t)stream, g, in3, w, dw, db, dpos, din3, frames, ms.p);
+    const int rc = ms.finish((hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return rc;
+}
+int kasf_op_refusion_bwd(const kasf_model* m, const float* params, const float* x, const float* dlimb3, float* grads, int64_t frames, float* scratch,
+                         int64_t scratch_floats, void* stream) {
+    if (check_model(m)) return 2;
+    if (!params || !x || !dlimb3 || !grads) return kasf_set_error(2, "null pointer argument");
+    MISC_FRAMES_CHECK(frames);
+    if (misc_scratch_check(scratch, scratch_floats)) return 2;
+    if (m->d_pro == nullptr) return kasf_set_error(4, "layout-only model cannot run");
+    int64_t rf_base, rf_end;
+    refusion_grad_range(m->pro, rf_base, rf_end);
+    MiscSink ms(scratch, scratch_floats);
+    kasf_launch_refusion_bwd((hipStream_t)stream, x, dlimb3, params, grads, m->d_pro, frames, ms.p, rf_base, (int)(rf_end - rf_base));
+    const int rc = ms.finish((hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return rc;
+}
+int kasf_op_gate_fwd(int32_t dtype, const void* xa, const void* xg, const void* xb, const float* w, const float* bias, void* out, float* alpha, int64_t M,
+                     int32_t adaptive, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!xa || !xg || !xb || !w || !bias || !out) return kasf_set_error(2, "null pointer argument");
+    MISC_TOKENS_CHECK(M, "gate_fwd");
+    kasf_launch_gate_fwd(dtype, (hipStream_t)stream, xa, xg, xb, w, bias, out, alpha, M, adaptive ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int kasf_op_gate_bwd(int32_t dtype, const void* g, const void* g1, const void* g2, const void* xa, const void* xg, const void* xb, const float* w,
+                     const float* alpha, void* ga, void* gg, void* gb, float* dw, float* db, int64_t M, int32_t adaptive, float* scratch,
+                     int64_t scratch_floats, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!g || !xa || !xg || !xb || !w || !alpha || !ga || !gg || !gb || (adaptive && (!dw || !db))) return kasf_set_error(2, "null pointer argument");
+    if (((uintptr_t)alpha & 15) != 0) return kasf_set_error(2, "gate_bwd: alpha must be 16-byte aligned");
+    MISC_TOKENS_CHECK(M, "gate_bwd");
+    if (misc_scratch_check(scratch, scratch_floats)) return 2;
+    MiscSink ms(scratch, scratch_floats);
+    kasf_launch_gate_bwd(dtype, (hipStream_t)stream, g, g1, g2, xa, xg, xb, w, alpha, ga, gg, gb, dw, db, M, adaptive ? 1 : 0, ms.p);
+    const int rc = ms.finish((hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return rc;
+}
+int kasf_op_head_fwd(int32_t dtype, const void* rep, const float* w, const float* bias, float* out, int64_t M, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!rep || !w || !bias || !out) return kasf_set_error(2, "null pointer argument");
+    MISC_TOKENS_CHECK(M, "head_fwd");
+    kasf_launch_head_fwd(dtype, (hipStream_t)stream, rep, w, bias, out, M);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int kasf_op_head_bwd(int32_t dtype, const float* dy, const void* rep, const float* w, void* dpre, float* dw, float* db, int64_t M, float* scratch,
+                     int64_t scratch_floats, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!dy || !rep || !w || !dpre || !dw || !db) return kasf_set_error(2, "null pointer argument");
+    MISC_TOKENS_CHECK(M, "head_bwd");
+    if (misc_scratch_check(scratch, scratch_floats)) return 2;
+    MiscSink ms(scratch, scratch_floats);
+    kasf_launch_head_bwd(dtype, (hipStream_t)stream, dy, rep, w, dpre, dw, db, M, ms.p);
+    const int rc = ms.finish((hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return rc;
+}
+int kasf_op_rep_bwd(int32_t dtype, const float* drep, const void* rep, void* dpre, int64_t M, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!drep || !rep || !dpre) return kasf_set_error(2, "null pointer argument");
+    MISC_TOKENS_CHECK(M, "rep_bwd");
+    kasf_launch_rep_bwd(dtype, (hipStream_t)stream, drep, rep, dpre, M);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int kasf_op_finalize_ls(float* dw, const float* w, const float* bias, const float* ls, float* db, float* dls, int32_t N, int32_t K, void* stream) {
+    if (!dw || !w || !bias || !ls || !db || !dls) return kasf_set_error(2, "null pointer argument");
+    if (N != 128 || (K != 128 && K != 512)) return kasf_set_error(2, "finalize_ls: (N, K) must be (128, 128) or (128, 512), the two layer-scaled Linear layers of a block");
+    kasf_launch_finalize_ls((hipStream_t)stream, dw, w, bias, ls, db, dls, N, K);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int kasf_op_add(int32_t dtype, void* dst, const void* a, const void* b, const void* c, int64_t n, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!dst || !a || (!b && c)) return kasf_set_error(2, "null pointer argument (c needs b)");
+    if (n < 8 || n % 8 != 0 || n >= ((int64_t)1 << 40)) return kasf_set_error(2, "add: n must be a multiple of 8 in [8, 2^40)");
+    if (b == nullptr) kasf_launch_add_inplace(dtype, (hipStream_t)stream, dst, a, n);
+    else kasf_launch_add3(dtype, (hipStream_t)stream, dst, a, b, c, n);
     HIPCHK(hipGetLastError());
     return 0;
 }

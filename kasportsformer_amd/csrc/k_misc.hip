@@ -3,6 +3,7 @@
 // token row of 128 channels (8 channels / 16 B per lane) so every global access is a full 256/512-B line.
 #include "common.h"
 #include "kernels.h"
+#include "kasf.h"      // KASF_MISC_*
 
 namespace {
 
@@ -661,7 +662,25 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
     }
 }
 
+// workgroups of the launches that leave one scratch row each (kasf_misc_scratch_floats sizes the scratch by the same numbers)
+inline unsigned embed_bwd_grid(int64_t frames) { return (unsigned)(frames < 128 ? frames : 128); }
+inline unsigned refusion_bwd_grid(int64_t frames) { return (unsigned)(frames < 256 ? frames : 256); }
+inline unsigned gate_bwd_grid(int64_t M) { return ew_grid(M * 16, 768); }      // 3 workgroups per CU (168 VGPRs): enough loads in flight for an HBM stream of 7-9 tensors
+inline unsigned head_bwd_grid(int64_t M) { return ew_grid(M * 16, 256); }
+
 }  // namespace
+
+int64_t kasf_misc_scratch_floats(int op, int64_t n, int refusion_len) {
+    int64_t rows = 0, ld = 0;
+    switch (op) {
+        case KASF_MISC_EMBED_BWD: rows = embed_bwd_grid(n); ld = EMBED_ROW; break;
+        case KASF_MISC_REFUSION_BWD: rows = refusion_bwd_grid(n); ld = refusion_len; break;
+        case KASF_MISC_GATE_BWD: rows = gate_bwd_grid(n); ld = GATE_PART_LD; break;
+        case KASF_MISC_HEAD_BWD: rows = head_bwd_grid(n); ld = HEAD_ROW; break;
+        default: return -1;
+    }
+    return (rows * ld + 63) & ~int64_t(63);      // KasfColSink::take's rounding
+}
 
 void kasf_launch_prologue_fwd(int dt, hipStream_t s, const float* x, const float* params, const KasfProOff* off, void* xj, void* xb, void* xl,
                               float* bone3, float* limb3, int64_t frames) {
@@ -671,7 +690,7 @@ void kasf_launch_prologue_fwd(int dt, hipStream_t s, const float* x, const float
 }
 void kasf_launch_embed_bwd(int dt, hipStream_t s, const void* g, const float* in3, const float* W, float* dW, float* db, float* dpos, float* din3,
                            int64_t frames, KasfColSink* sink) {
-    const unsigned grid = (unsigned)(frames < 128 ? frames : 128);
+    const unsigned grid = embed_bwd_grid(frames);
     float* rows = sink != nullptr ? sink->take((int)grid, EMBED_ROW) : nullptr;
     if (dt == KASF_F32) hipLaunchKernelGGL(k_embed_bwd<float>, dim3(grid), dim3(256), 0, s, (const float*)g, in3, W, dW, db, dpos, din3, frames, rows);
     else hipLaunchKernelGGL(k_embed_bwd<bf16>, dim3(grid), dim3(256), 0, s, (const bf16*)g, in3, W, dW, db, dpos, din3, frames, rows);
@@ -683,7 +702,7 @@ void kasf_launch_embed_bwd(int dt, hipStream_t s, const void* g, const float* in
 }
 void kasf_launch_refusion_bwd(hipStream_t s, const float* x, const float* dlimb3, const float* params, float* grads, const KasfProOff* off,
                               int64_t frames, KasfColSink* sink, int64_t grad_base, int grad_len) {
-    const unsigned grid = (unsigned)(frames < 256 ? frames : 256);
+    const unsigned grid = refusion_bwd_grid(frames);
     float* rows = (sink != nullptr && grad_len > 0) ? sink->take((int)grid, grad_len) : nullptr;
     hipLaunchKernelGGL(k_refusion_bwd, dim3(grid), dim3(64), 0, s, x, dlimb3, params, grads, off, frames, rows, grad_base, grad_len);
     if (rows != nullptr) sink->add(rows, grad_len, (int)grid, grad_len, grads + grad_base);
@@ -696,7 +715,7 @@ void kasf_launch_gate_fwd(int dt, hipStream_t s, const void* xa, const void* xg,
 }
 void kasf_launch_gate_bwd(int dt, hipStream_t s, const void* g, const void* g1, const void* g2, const void* xa, const void* xg, const void* xb,
                           const float* W, const float* alpha, void* ga, void* gg, void* gb, float* dW, float* db, int64_t M, int adaptive, KasfColSink* sink) {
-    unsigned grid = ew_grid(M * 16, 768);               // 3 workgroups per CU (168 VGPRs): enough loads in flight for an HBM stream of 7-9 tensors
+    unsigned grid = gate_bwd_grid(M);
     float* part = (sink != nullptr && adaptive) ? sink->take((int)grid, GATE_PART_LD) : nullptr;      // one row of dW[3][384] | db[3] per workgroup
     if (part == nullptr && grid > 256) grid = 256;      // atomics: few workgroups
     if (dt == KASF_F32) hipLaunchKernelGGL(k_gate_bwd<float>, dim3(grid), dim3(256), 0, s, (const float*)g, (const float*)g1, (const float*)g2, (const float*)xa, (const float*)xg, (const float*)xb, W, alpha, (float*)ga, (float*)gg, (float*)gb, dW, db, part, M, adaptive);
@@ -728,7 +747,7 @@ void kasf_launch_rep_bwd(int dt, hipStream_t s, const float* drep, const void* r
 }
 void kasf_launch_head_bwd(int dt, hipStream_t s, const float* dy, const void* rep, const float* W, void* dpre, float* dW, float* db, int64_t M,
                           KasfColSink* sink) {
-    const unsigned grid = ew_grid(M * 16, 256);
+    const unsigned grid = head_bwd_grid(M);
     float* rows = sink != nullptr ? sink->take((int)grid, HEAD_ROW) : nullptr;
     if (dt == KASF_F32) hipLaunchKernelGGL(k_head_bwd<float>, dim3(grid), dim3(256), 0, s, dy, (const float*)rep, W, (float*)dpre, dW, db, M, rows);
     else hipLaunchKernelGGL(k_head_bwd<bf16>, dim3(grid), dim3(256), 0, s, dy, (const bf16*)rep, W, (bf16*)dpre, dW, db, M, rows);

@@ -132,6 +132,9 @@ void kasf_launch_gcn_bwd2(int dt, hipStream_t s, const void* r, const void* y, c
 // training == 0: backward of an evaluation-mode BatchNorm (running statistics are constants: no batch-mean terms)
 
 // ---- k_misc.hip ----
+// scratch floats one launch of a KasfColSink-taking kernel below asks of the sink (op: KASF_MISC_* of kasf.h; n = frames for embed / refusion, tokens for gate /
+// head); -1: unknown op
+int64_t kasf_misc_scratch_floats(int op, int64_t n, int refusion_len);
 void kasf_launch_prologue_fwd(int dt, hipStream_t s, const float* x, const float* params, const KasfProOff* off, void* xj, void* xb, void* xl,
                               float* bone3, float* limb3, int64_t frames);
 void kasf_launch_embed_bwd(int dt, hipStream_t s, const void* g, const float* in3, const float* W, float* dW, float* db, float* dpos, float* din3,

@@ -263,6 +263,31 @@ int main(void) {
         if (kasf_op_gcn_bwd(1, p, p, p, f, u, f, p, p, f, f, f, 0, 2, 27, 0, 1, 0) != 2) return 9;                  /* bstats */
         if (f[0] != 0.0f || u[0] != 0u) return 10;
     }
+    {                                                            /* so do the prologue / gate / head / embedding entries; a layout-only model is error 4 */
+        float f[8] = {0};
+        void* p = f;
+        kasf_model* lay = 0;
+        if (kasf_model_create_layout_only(&shipped, &lay) != 0) return 11;
+        if (kasf_op_prologue_fwd(lay, f, f, p, p, p, f, f, 0, 0) != 2) return 12;                                   /* frames */
+        if (kasf_op_prologue_fwd(lay, f, f, p, p, p, f, 0, 5, 0) != 2) return 12;                                   /* limb3 */
+        if (kasf_op_prologue_fwd(0, f, f, p, p, p, f, f, 5, 0) != 2) return 12;                                     /* model */
+        if (kasf_op_prologue_fwd(lay, f, f, p, p, p, f, f, 5, 0) != 4) return 12;                                   /* layout only */
+        if (kasf_op_refusion_bwd(lay, f, f, f, f, 5, 0, 0, 0) != 4) return 13;
+        if (kasf_op_refusion_bwd(lay, f, f, f, f, 328966, 0, 0, 0) != 2) return 13;                                 /* frames * 17 * 384 >= 2^31 */
+        if (kasf_op_embed_bwd(0, p, f, f, f, f, f, 0, -1, 0, 0, 0) != 2) return 14;
+        if (kasf_op_embed_bwd(0, p, f, f, f, f, f, 0, 5, f, 0, 0) != 2) return 14;                                  /* scratch without a size */
+        if (kasf_op_gate_fwd(1, p, p, p, f, f, p, 0, 0, 1, 0) != 2) return 15;
+        if (kasf_op_gate_bwd(1, p, 0, 0, p, p, p, f, f, p, p, p, 0, f, 5, 1, 0, 0, 0) != 2) return 15;              /* adaptive needs dw */
+        if (kasf_op_head_fwd(0, p, f, f, f, 5592406, 0) != 2) return 16;                                            /* M * 384 >= 2^31 */
+        if (kasf_op_head_bwd(0, f, p, f, p, f, 0, 5, 0, 0, 0) != 2) return 16;
+        if (kasf_op_rep_bwd(3, f, p, p, 5, 0) != 3) return 16;                                                      /* dtype */
+        if (kasf_op_finalize_ls(f, f, f, f, f, f, 128, 256, 0) != 2) return 17;
+        if (kasf_op_add(0, p, p, 0, 0, 12, 0) != 2) return 17;                                                      /* n % 8 */
+        if (kasf_op_misc_scratch_floats(KASF_MISC_GATE_BWD, 0) != -2 || kasf_op_misc_scratch_floats(9, 5) != -2) return 18;
+        if (kasf_op_misc_scratch_floats(KASF_MISC_HEAD_BWD, 17) != (2 * (3 * 512 + 4) + 63) / 64 * 64) return 18;
+        kasf_model_destroy(lay);
+        if (f[0] != 0.0f) return 19;
+    }
     printf("ok %s\n", kasf_last_error());
     return 0;
 }
