@@ -41,6 +41,8 @@
  *   kasf_sort_update       <- Sort.update (KalmanBoxTracker, associate_detections_to_trackers, iou) and, from gen_video_kpts, the empty-frame hold and the
  *                             num_person oldest tracks: what the demo does on the host between the person boxes and the crops
  *                             demo/lib/sort/sort.py:15-222, demo/lib/hrnet/gen_kpts.py:111-148
+ *   kasf_stream_track_front, kasf_stream_track_emit <- the seam between the two: gen_video_kpts hands each tracked person's keypoints to the lift by track
+ *                             order; here the tracker's ids and slots drive the lifter's per-player histories on the device   demo/lib/hrnet/gen_kpts.py:125-170
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
  *   kasf_op_gcn_fwd, kasf_op_gcn_bwd <- GCN.forward between its U | V Linear and the residual, and autograd of it   model/modules/graph.py:19-134, KASportsFormer.py:109
  */
@@ -447,6 +449,50 @@ int64_t kasf_sort_state_bytes(int32_t streams, int32_t slots, int32_t max_dets);
 int kasf_sort_update(void* state, int32_t streams, int32_t slots, int32_t max_dets, const float* dets, int32_t det_rows, int64_t det_stream_stride, int64_t det_row_stride,
                      const int32_t* det_count, int32_t max_age, int32_t min_hits, float iou_threshold, int32_t num_person, int32_t hold_last, float* boxes,
                      int32_t* ids, int32_t* slot, int32_t* born, int32_t* count, int32_t* dropped, float* persons, int32_t* person_count, void* stream);
+
+/* ---- the stream lifter's slots driven by the tracker's output (ADDED under ABI 12: additive, kasf_version stays 12; look the two symbols up by name) ----
+ * What a caller of kasf_stream_push / kasf_stream_windows / kasf_stream_emit had to do on the host between kasf_sort_update and the lift -- read ids, slot and
+ * count back, decide births and deaths, upload slot ids -- done on the device: two launches per tick, one in front of the model's forward and one behind it,
+ * nothing read back.  Neither entry allocates.
+ *
+ * State (device, the caller's, all zero at the start): ring [streams * track_slots][T][17][3] fp32 and count [streams * track_slots] int64 as the stream
+ * entries above keep them, owner [streams * track_slots] int32 = the track id whose history the slot holds (0: nobody's).  Entry g = b * track_slots + s belongs
+ * to tracker slot s of stream b.  width, height [streams] fp32, positive: one resolution per STREAM.  resample_tab, first_pos_tab: kasf_stream_tables' tables.
+ *
+ * The tick rule.  ids, slot, born [streams][track_slots] int32 and count_b [streams] int32 are kasf_sort_update's outputs of this tick (read in place), frames
+ * [streams * R][17][3] fp32 the new keypoint frame of every row (H36M-17 pixels + confidence; only read).  count_b is clamped to [0, track_slots].  Row k (k < R)
+ * of stream b takes track row
+ *     r = count_b - 1 - k   with rows_mode = KASF_ROWS_PERSONS (the k-th oldest emitted track: the row order of kasf_sort_update's persons), or
+ *     r = k                 with rows_mode = KASF_ROWS_TRACKS  (the row order of its boxes).
+ * The row is VALID iff k < min(count_b, R), id = ids[b][r] >= 1, s = slot[b][r] is in [0, track_slots), and no lower row of the same stream that passes these
+ * three tests has the same s (the tracker never emits such duplicates; with hand-made arrays the lowest row wins, the others are invalid).
+ * For a valid row, with g = b * track_slots + s:
+ *   1. if owner[g] != id or born[b][r] != 0, a new player has the slot: count[g] = 0, owner[g] = id;
+ *   2. the frame is stored at ring[g][count[g] % T];
+ *   3. count[g] += 1;
+ *   4. the row's window is the slot's last L = min(count[g], T) frames, its clips and its pose exactly what kasf_stream_windows and kasf_stream_emit (n_out = 1)
+ *      give for a slot with that ring and count at the stream's resolution: the pose is frame max(L - 1 - back, 0) of the window's lift.
+ * A track that is not emitted on a tick gets no frame that tick; its history goes on when it comes back under the same id.  A finished track's slot is left as
+ * it is: the next id on that slot starts it again.  Ids restart at 1 when the tracker's state is zeroed, so count and owner of those streams must be zeroed
+ * with it.  An INVALID row touches no state; its clips are all zero, its pose row is all zero, and valid, ids_out and frames_out are 0.
+ *
+ * kasf_stream_track_front: one launch, one workgroup per row: resolves the row, applies steps 1-3 and writes x_out [(1 + flip) * streams * R][T][17][3], clip
+ * h * streams * R + row, h = 1 the mirrored copy, bit for bit kasf_stream_windows' arithmetic; row_slot [streams * R] int32 receives g, or -1 for an invalid row.
+ * Valid rows have distinct g, so no two workgroups touch one state entry: no atomics, the same bits from run to run.  Every index formed from a device value
+ * (count_b, slot, count, a table entry) is clamped into the arrays streams, track_slots, R and T describe.
+ * kasf_stream_track_emit: out [n_rows][17][3] from the model's output pred [(1 + flip) * n_rows][T][17][3] in the clip order above, merged as kasf_stream_emit
+ * merges with n_out = 1; valid [n_rows] uint8 (1 / 0), ids_out [n_rows] int32 (owner[g]), frames_out [n_rows] int64 (count[g], after the push); zeros for
+ * rows with row_slot < 0.  row_slot must be what kasf_stream_track_front wrote for this state: its entries index count and owner as they are.
+ *
+ * n_rows = 0 does nothing.  Error 2, before a device or a device pointer is touched: T outside [1, 256]; streams < 1; track_slots outside 1..64; R < 1;
+ * streams * R or streams * track_slots beyond 32 bits; a rows_mode that is neither constant; back outside [0, T - 1]; n_rows < 0; a null pointer. */
+#define KASF_ROWS_PERSONS 0
+#define KASF_ROWS_TRACKS 1
+int kasf_stream_track_front(const float* frames, const int32_t* ids, const int32_t* slot, const int32_t* born, const int32_t* count_b, int32_t streams,
+                            int32_t track_slots, int32_t rows_mode, int32_t R, int32_t T, float* ring, int64_t* count, int32_t* owner, const float* width,
+                            const float* height, const int32_t* resample_tab, int32_t flip, float* x_out, int32_t* row_slot, void* stream);
+int kasf_stream_track_emit(const float* pred, int32_t flip, const int64_t* count, const int32_t* owner, const int32_t* row_slot, int32_t n_rows, int32_t T,
+                           const int32_t* first_pos_tab, int32_t back, float* out, uint8_t* valid, int32_t* ids_out, int64_t* frames_out, void* stream);
 
 /* debugging / tests: locate a named activation inside the workspace (see kasf_ws_name()) */
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags);

@@ -32,6 +32,9 @@ Public surface mirrors the reference's interface for this path:
   SortTracker, TrackResult              demo/lib/sort/sort.py:15-222, demo/lib/hrnet/gen_kpts.py:111-148 (the demo's SORT tracker between the person boxes and the
                                         crops, on the device: fp64 Kalman filters, IoU, optimal assignment, births, deaths, ids; one launch per tick
                                         for every stream, takes `DetectResult` as it is, gives what `crop_persons` takes)
+  TrackedLifter, TrackedTick            the seam between the two stages (demo/lib/hrnet/gen_kpts.py:125-170 hands each tracked person's keypoints to the lift):
+                                        `SortTracker`'s ids and slots drive `StreamLifter`-style per-player histories on the device, births and deaths
+                                        included; no read-back of the tracker's output, two launches and one forward per tick
   poses_to_world, DEMO_CAMERA_ROTATION  demo/lib/utils.py:55-73, demo/demo.py:242-248 (camera space -> world space, floor, unit scale; `--world`)
 """
 from .model import (KASportsFormer, load_model, set_single_stream, is_single_stream, set_deterministic, is_deterministic, set_fused_attention_backward,
@@ -53,10 +56,12 @@ from .heatmap import heatmaps_to_keypoints
 from .detect import detections_to_boxes, yolo_heads_to_boxes, DetectResult, YOLOV3_ANCHORS, YOLOV3_MASKS
 from .crop import crop_persons, CropResult
 from .track import SortTracker, TrackResult, TrackState
+from .tracked import TrackedLifter, TrackedTick
 
 __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_stream", "set_deterministic", "is_deterministic", "set_fused_attention_backward", "is_fused_attention_backward", "loss3", "FusedAdamW", "DataParallel", "joint_flip", "predict_flip_tta", "clip_metrics", "Evaluator",
            "evaluate_one_epoch", "PackedClips", "DeviceClipLoader", "pack_clip_directory", "read_clip_file", "shard_indices",
            "checkpoint_save", "checkpoint_load", "strip_module_prefix", "adamw_state_dict", "load_adamw_state_dict", "warmup_lr", "apply_warmup", "ReduceLROnPlateau", "train_one_epoch",
            "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample",
            "lift_track", "lift_tracks", "window_plan", "StreamLifter", "coco_to_h36m", "poses_to_world", "DEMO_CAMERA_ROTATION", "heatmaps_to_keypoints",
-           "detections_to_boxes", "yolo_heads_to_boxes", "DetectResult", "YOLOV3_ANCHORS", "YOLOV3_MASKS", "crop_persons", "CropResult", "SortTracker", "TrackResult", "TrackState"]
+           "detections_to_boxes", "yolo_heads_to_boxes", "DetectResult", "YOLOV3_ANCHORS", "YOLOV3_MASKS", "crop_persons", "CropResult", "SortTracker", "TrackResult", "TrackState",
+           "TrackedLifter", "TrackedTick"]

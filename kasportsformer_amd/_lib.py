@@ -16,6 +16,7 @@ DTYPE_F32, DTYPE_BF16 = 0, 1
 DTYPE_F16 = 2                          # KASF_DTYPE_F16: heatmap / detector input and crop output only, no model runs in it
 GEOM_CENTER_SCALE, GEOM_BOX = 0, 1
 LAYOUT_COCO, LAYOUT_H36M = 0, 1
+ROWS_PERSONS, ROWS_TRACKS = 0, 1         # KASF_ROWS_*: row order of kasf_stream_track_front
 DETECT_PREDICTION, DETECT_HEADS = 0, 1
 DETECT_MAX_CANDIDATES = 4096           # KASF_DETECT_MAX_CANDIDATES
 SORT_MAX = 64                          # KASF_SORT_MAX: slots and max_dets of kasf_sort_update
@@ -85,6 +86,8 @@ SIGNATURES = {
     "kasf_stream_push": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "kasf_stream_windows": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "kasf_stream_emit": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "kasf_stream_track_front": (_i32, [_vp] * 5 + [_i32] * 5 + [_vp] * 6 + [_i32, _vp, _vp, _vp]),
+    "kasf_stream_track_emit": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "kasf_coco_h36m": (_i32, [_vp, _i64, _vp, _vp]),
     "kasf_pose_world": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "kasf_heatmap_keypoints": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i32, C.c_double, _i32, _i32, _vp, _vp, _vp]),

@@ -1158,6 +1158,35 @@ int kasf_stream_emit(const float* pred, int32_t flip, const int64_t* count, cons
     return 0;
 }
 
+// ---- the stream lifter's slots driven by the tracker's output (kasf.h, kasf_stream_track_*) ----
+int kasf_stream_track_front(const float* frames, const int32_t* ids, const int32_t* slot, const int32_t* born, const int32_t* count_b, int32_t streams,
+                            int32_t track_slots, int32_t rows_mode, int32_t R, int32_t T, float* ring, int64_t* count, int32_t* owner, const float* width,
+                            const float* height, const int32_t* resample_tab, int32_t flip, float* x_out, int32_t* row_slot, void* stream) {
+    if (T < 1 || T > 256) return kasf_set_error(2, "stream_track: T must be in [1, 256]");
+    if (streams < 1) return kasf_set_error(2, "stream_track: streams must be >= 1");
+    if (track_slots < 1 || track_slots > KASF_SORT_MAX) return kasf_set_error(2, "stream_track: track_slots must be in [1, 64]");
+    if (R < 1) return kasf_set_error(2, "stream_track: R must be >= 1");
+    if (rows_mode != KASF_ROWS_PERSONS && rows_mode != KASF_ROWS_TRACKS) return kasf_set_error(2, "stream_track: rows_mode must be KASF_ROWS_PERSONS or KASF_ROWS_TRACKS");
+    if ((int64_t)streams * R > INT32_MAX || (int64_t)streams * track_slots > INT32_MAX) return kasf_set_error(2, "stream_track: streams * R and streams * track_slots must fit 32 bits");
+    if (!frames || !ids || !slot || !born || !count_b || !ring || !count || !owner || !width || !height || !resample_tab || !x_out || !row_slot)
+        return kasf_set_error(2, "null pointer argument");
+    kasf_launch_stream_track_front((hipStream_t)stream, frames, ids, slot, born, count_b, streams, track_slots, rows_mode, R, T, ring, count, owner, width, height,
+                                   resample_tab, flip ? 1 : 0, x_out, row_slot);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int kasf_stream_track_emit(const float* pred, int32_t flip, const int64_t* count, const int32_t* owner, const int32_t* row_slot, int32_t n_rows, int32_t T,
+                           const int32_t* first_pos_tab, int32_t back, float* out, uint8_t* valid, int32_t* ids_out, int64_t* frames_out, void* stream) {
+    if (T < 1 || T > 256) return kasf_set_error(2, "stream_track: T must be in [1, 256]");
+    if (back < 0 || back > T - 1) return kasf_set_error(2, "stream_track: back must be in [0, T - 1]");
+    if (n_rows < 0) return kasf_set_error(2, "stream_track: n_rows must be >= 0");
+    if (n_rows == 0) return 0;
+    if (!pred || !count || !owner || !row_slot || !first_pos_tab || !out || !valid || !ids_out || !frames_out) return kasf_set_error(2, "null pointer argument");
+    kasf_launch_stream_track_emit((hipStream_t)stream, pred, flip ? 1 : 0, count, owner, row_slot, n_rows, T, first_pos_tab, back, out, valid, ids_out, frames_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // ---- the two ends of the lift (kasf.h, kasf_coco_h36m / kasf_pose_world) ----
 int kasf_coco_h36m(const float* coco, int64_t frames, float* h36m, void* stream) {
     if (frames < 0) return kasf_set_error(2, "coco_h36m: frames must be >= 0");

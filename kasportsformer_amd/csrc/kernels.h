@@ -191,6 +191,18 @@ void kasf_launch_stream_windows(hipStream_t s, const float* ring, const int64_t*
 void kasf_launch_stream_emit(hipStream_t s, const float* pred, int flip, const int64_t* count, const int* slots, int K, int S, int T, const int* first_pos_tab,
                              int back, int n_out, float* out);
 
+// ---- k_stream_track.hip: the stream lifter's slots driven by a TrackResult on the device (kasf.h, kasf_stream_track_*): B streams of S_t tracker slots, state
+// ring [B*S_t,T,17,3] / count [B*S_t] / owner [B*S_t], R rows per stream in the order rows_mode names; arguments as checked by the entry points ----
+#ifndef KASF_ROWS_PERSONS
+#define KASF_ROWS_PERSONS 0
+#define KASF_ROWS_TRACKS 1
+#endif
+void kasf_launch_stream_track_front(hipStream_t s, const float* frames, const int* ids, const int* slot, const int* born, const int* count_b, int B, int S_t,
+                                    int rows_mode, int R, int T, float* ring, int64_t* count, int* owner, const float* width, const float* height,
+                                    const int* resample_tab, int flip, float* x, int* row_slot);
+void kasf_launch_stream_track_emit(hipStream_t s, const float* pred, int flip, const int64_t* count, const int* owner, const int* row_slot, int64_t n_rows, int T,
+                                   const int* first_pos_tab, int back, float* out, unsigned char* valid, int* ids_out, int64_t* frames_out);
+
 // ---- k_pose.hip: the two ends of the lift (kasf.h, kasf_coco_h36m / kasf_pose_world); frames of [17,3] fp32, src and dst distinct arrays ----
 void kasf_launch_coco_h36m(hipStream_t s, const float* coco, int64_t frames, float* h36m);
 // q [4], t [3]: host arrays, passed by value into the launch
