@@ -5,14 +5,12 @@
 
 namespace {
 
-// utils/utilities.py:128-135: destination joint j takes source joint c_flip_src[j]; left [1,2,3,14,15,16] <-> right [4,5,6,11,12,13]
-__constant__ int c_flip_src[17] = {0, 4, 5, 6, 1, 2, 3, 7, 8, 9, 10, 14, 15, 16, 11, 12, 13};
-
+// destination joint j takes source joint c_lift_flip_src[j] (lift_math.h, utils/utilities.py:128-135)
 __global__ __launch_bounds__(256) void k_joint_flip(const float* __restrict__ src, float* __restrict__ dst, int64_t n /* rows*51 */) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int64_t row = i / 51;
         const int r = (int)(i - row * 51), j = r / 3, c = r - 3 * j;
-        const float v = src[row * 51 + 3 * c_flip_src[j] + c];
+        const float v = src[row * 51 + 3 * c_lift_flip_src[j] + c];
         dst[i] = c == 0 ? -v : v;
     }
 }
@@ -24,7 +22,7 @@ __global__ __launch_bounds__(256) void k_tta_merge(const float* __restrict__ p, 
         const int r = (int)(i - row * 51), j = r / 3, c = r - 3 * j;
         float v = p[i];
         if (pf) {
-            const float f = pf[row * 51 + 3 * c_flip_src[j] + c];
+            const float f = pf[row * 51 + 3 * c_lift_flip_src[j] + c];
             v = (v + (c == 0 ? -f : f)) / 2;
         }
         out[i] = j == 0 ? 0.0f : v;
@@ -43,7 +41,7 @@ __global__ __launch_bounds__(256) void k_gather_clips(const float* __restrict__ 
         const bool f = flip && flip[b];
         float vx = 0.0f, vy = 0.0f;
         if (src >= 0 && src < n_clips) {
-            const int64_t o = src * clip_floats + row * 51 + 3 * (f ? c_flip_src[j] : j) + c;
+            const int64_t o = src * clip_floats + row * 51 + 3 * (f ? c_lift_flip_src[j] : j) + c;
             vx = xa[o];
             if (ya) vy = ya[o];
             if (f && c == 0) { vx = -vx; vy = -vy; }

@@ -4,6 +4,7 @@
 // Three forms: one track layout for all persons, many tracks of different lengths packed back to back, and one new frame per tick (k_stream_*).
 // The tracks are in the H36M-17 joint layout; COCO-17 detector keypoints are converted in front of these kernels, and the poses they give are taken to
 // world space behind them, by k_pose.hip (kasf_coco_h36m / kasf_pose_world).
+// The arithmetic of all three forms -- clip value, flip-TTA merge, mean over the covering windows -- is written once, in lift_math.h.
 //
 // Window plan (kasportsformer_amd/lift.py window_plan, kasf.h): W windows of T frames over an n-frame track.
 //   stride == T (the demo's turn_into_clips, demo.py:138-156): windows start at 0, T, 2T, ...; a last window of L < T frames is resampled to
@@ -15,88 +16,10 @@
 
 namespace {
 
-// utils/utilities.py:128-135 / demo/lib/utils.py:5-13: destination joint j takes source joint c_lift_flip_src[j]; left [1,2,3,14,15,16] <-> right [4,5,6,11,12,13]
-__constant__ int c_lift_flip_src[17] = {0, 4, 5, 6, 1, 2, 3, 7, 8, 9, 10, 14, 15, 16, 11, 12, 13};
-
 // First frame of window w (of W) on the track.
 __device__ inline int64_t lift_start(int64_t w, int64_t W, int64_t n, int T, int stride) {
     return (stride < T && n > T && w == W - 1) ? n - T : w * stride;
 }
-
-// x [(1+flip) * P * W, T, 17, 3]: clip (h * P + p) * W + w is window w of person p, mirrored when h == 1.
-// x / w * 2 in fp32, then the fp64 subtraction of [1, h / w], stored as fp32 (normalize_screen_coordinates, demo/lib/utils.py:16-20); confidence unchanged.
-__global__ __launch_bounds__(256) void k_lift_windows(const float* __restrict__ track, int64_t n, int64_t W, int T, int stride, const int* __restrict__ resample,
-                                                      float width, double shift_y, int64_t clips_per_half, int64_t total, float* __restrict__ x) {
-    const int64_t clip_floats = (int64_t)T * 51;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t clip = i / clip_floats, r = i - clip * clip_floats;
-        const int t = (int)(r / 51), q = (int)(r - (int64_t)t * 51), j = q / 3, c = q - 3 * j;
-        const bool mirrored = clip >= clips_per_half;
-        const int64_t pw = mirrored ? clip - clips_per_half : clip;
-        const int64_t p = pw / W, w = pw - p * W;
-        const int64_t start = lift_start(w, W, n, T, stride);
-        const int64_t L = n - start < T ? n - start : T;
-        int64_t f = t;
-        if (L < T) {                                   // the resampled window: table entries are clamped into it, a bad table never reads outside the track
-            const int64_t rt = resample[t];
-            f = rt < 0 ? 0 : (rt >= L ? L - 1 : rt);
-        }
-        const int js = mirrored ? c_lift_flip_src[j] : j;
-        float v = track[(p * n + start + f) * 51 + 3 * js + c];
-        if (c < 2) {
-            const float scaled = v / width * 2.0f;
-            v = (float)((double)scaled - (c == 0 ? 1.0 : shift_y));
-            if (mirrored && c == 0) v = -v;
-        }
-        x[i] = v;
-    }
-}
-
-// out [P, n, 17, 3] from pred [(1+flip) * P * W, T, 17, 3]: per covering window (p + joint_flip(p_f)) / 2 with the root zeroed (kasf_tta_merge,
-// train_and_evaluate_sp.py:46-55 / demo.py:229-235), summed over the covering windows in ascending order and divided by their number.
-__global__ __launch_bounds__(256) void k_lift_stitch(const float* __restrict__ pred, int flip, int64_t n, int64_t W, int T, int stride,
-                                                     const int* __restrict__ first_pos, int64_t clips_per_half, int64_t total, float* __restrict__ out) {
-    const int64_t clip_floats = (int64_t)T * 51;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t row = i / 51;
-        const int q = (int)(i - row * 51), j = q / 3, c = q - 3 * j;
-        const int64_t p = row / n, f = row - p * n;
-        if (j == 0) {
-            out[i] = 0.0f;
-            continue;
-        }
-        // windows covering frame f: the regular ones (start w * stride) in [w_lo, w_hi], then, in overlap mode, the last one (start n - T) when it reaches f
-        const bool tail = stride < T && n > T;
-        const int64_t w_lo = f < T ? 0 : (f - T) / stride + 1, last_regular = tail ? W - 2 : W - 1;
-        const int64_t w_hi = f / stride < last_regular ? f / stride : last_regular;
-        float acc = 0.0f;
-        int cnt = 0;
-        for (int64_t w = w_lo; w <= w_hi + (tail && f >= n - T ? 1 : 0); ++w) {
-            const int64_t start = w > w_hi ? n - T : w * stride;
-            const int64_t L = n - start < T ? n - start : T;
-            int64_t t = f - start;
-            if (L < T) {
-                const int64_t ft = first_pos[t];
-                t = ft < 0 ? 0 : (ft >= T ? T - 1 : ft);
-            }
-            const int64_t o = (p * W + (w > w_hi ? W - 1 : w)) * clip_floats + t * 51;
-            float v = pred[o + q];
-            if (flip) {
-                const float fv = pred[clips_per_half * clip_floats + o + 3 * c_lift_flip_src[j] + c];
-                v = (v + (c == 0 ? -fv : fv)) / 2;
-            }
-            acc += v;
-            ++cnt;
-        }
-        out[i] = acc / (float)cnt;
-    }
-}
-
-// ---- many tracks of different lengths in one launch (kasf.h, kasf_lift_*_ragged) ----
-// Tracks packed back to back: track p is rows [offsets[p], offsets[p + 1]) of [frames, 17, 3] and owns windows [win_first[p], win_first[p + 1]) of the
-// call, cut by its own plan (n = its length, W = its window count).  The two kernels are k_lift_windows / k_lift_stitch with (n, W) taken per track.
-// Every index formed from a device table is clamped into the arrays the host sized (frames, windows, tracks): an inconsistent table gives wrong values,
-// never an access outside track, pred or the tables.
 
 // The p in [0, P) with sorted[p] <= key < sorted[p + 1] (sorted: P + 1 non-decreasing entries); any table content gives some p in [0, P).
 __device__ inline int lift_track_of(const int64_t* __restrict__ sorted, int P, int64_t key) {
@@ -108,45 +31,66 @@ __device__ inline int lift_track_of(const int64_t* __restrict__ sorted, int P, i
     return lo;
 }
 
-__device__ inline int64_t lift_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// A plan says where the tracks of a call lie: `frames` rows of [17,3] and `windows` clips per half in all; clip g and output row `row` belong to tracks
+// clip_track(g) / row_track(row); track p is rows [base, base + n) and clips [wb, wb + W), its resample / first_pos tables start at entry `tab` of the
+// call's, and it is normalised with width(p) and shift_y(p) = h / w in fp64.  kTables: the spans are read from device tables, so every index formed from
+// them is clamped into the arrays the host sized (frames, windows, tracks) -- an inconsistent table gives wrong values, never an access outside them.
+struct LiftSpan { int64_t base, n, wb, W, tab; };
 
-// x [(1+flip) * windows, T, 17, 3]: clip h * windows + win_first[p] + w is window w of track p, mirrored when h == 1; track p normalised with width[p], height[p].
-__global__ __launch_bounds__(256) void k_lift_windows_ragged(const float* __restrict__ track, int64_t frames, const int64_t* __restrict__ offsets,
-                                                             const int64_t* __restrict__ win_first, int P, int64_t windows, const float* __restrict__ width,
-                                                             const float* __restrict__ height, int T, int stride, const int* __restrict__ resample,
-                                                             int64_t total, float* __restrict__ x) {
+// P persons with one n-frame layout (kasf_lift_windows / _stitch): one table, one resolution, h / w computed by the host.
+struct UniformPlan {
+    static constexpr bool kTables = false;
+    int64_t n, W, frames, windows;
+    float w;
+    double sy;
+    __device__ int64_t clip_track(int64_t g) const { return g / W; }
+    __device__ int64_t row_track(int64_t row) const { return row / n; }
+    __device__ LiftSpan span(int64_t p) const { return {p * n, n, p * W, W, 0}; }
+    __device__ float width(int64_t) const { return w; }
+    __device__ double shift_y(int64_t) const { return sy; }
+};
+
+// Tracks of different lengths packed back to back (kasf.h, kasf_lift_*_ragged): track p is rows [offsets[p], offsets[p + 1]) and owns windows
+// [win_first[p], win_first[p + 1]) of the call, cut by its own plan (n = its length, W = its window count), with row p of the [P, T] tables.
+struct RaggedPlan {
+    static constexpr bool kTables = true;
+    const int64_t* __restrict__ offsets;
+    const int64_t* __restrict__ win_first;
+    const float* __restrict__ w;
+    const float* __restrict__ h;
+    int P, T;
+    int64_t frames, windows;
+    __device__ int64_t clip_track(int64_t g) const { return lift_track_of(win_first, P, g); }
+    __device__ int64_t row_track(int64_t row) const { return lift_track_of(offsets, P, row); }
+    __device__ LiftSpan span(int64_t p) const { return {offsets[p], offsets[p + 1] - offsets[p], win_first[p], win_first[p + 1] - win_first[p], p * T}; }
+    __device__ float width(int64_t p) const { return w[p]; }
+    __device__ double shift_y(int64_t p) const { return (double)h[p] / (double)w[p]; }
+};
+
+// x [(1+flip) * windows, T, 17, 3]: clip h * windows + wb + w is window w of its track, mirrored when h == 1.
+template <class Plan>
+__global__ __launch_bounds__(256) void k_lift_windows(const float* __restrict__ track, Plan plan, int T, int stride, const int* __restrict__ resample,
+                                                      int64_t total, float* __restrict__ x) {
     const int64_t clip_floats = (int64_t)T * 51;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t clip = i / clip_floats, r = i - clip * clip_floats;
         const int t = (int)(r / 51), q = (int)(r - (int64_t)t * 51), j = q / 3, c = q - 3 * j;
-        const bool mirrored = clip >= windows;
-        const int64_t g = mirrored ? clip - windows : clip;
-        const int p = lift_track_of(win_first, P, g);
-        const int64_t base = offsets[p], n = offsets[p + 1] - base, W = win_first[p + 1] - win_first[p], w = g - win_first[p];
-        const int64_t start = lift_start(w, W, n, T, stride);
-        const int64_t L = n - start < T ? n - start : T;
+        const bool mirrored = clip >= plan.windows;
+        const int64_t g = mirrored ? clip - plan.windows : clip, p = plan.clip_track(g);
+        const LiftSpan k = plan.span(p);
+        const int64_t start = lift_start(g - k.wb, k.W, k.n, T, stride);
+        const int64_t L = k.n - start < T ? k.n - start : T;
         int64_t f = t;
-        if (L < T) {
-            const int64_t rt = resample[(int64_t)p * T + t];
-            f = rt < 0 ? 0 : (rt >= L ? L - 1 : rt);
-        }
-        const int js = mirrored ? c_lift_flip_src[j] : j;
-        float v = track[lift_clamp(base + start + f, 0, frames - 1) * 51 + 3 * js + c];
-        if (c < 2) {
-            const float wp = width[p];
-            const float scaled = v / wp * 2.0f;
-            v = (float)((double)scaled - (c == 0 ? 1.0 : (double)height[p] / (double)wp));
-            if (mirrored && c == 0) v = -v;
-        }
-        x[i] = v;
+        if (L < T) f = lift_clamp(resample[k.tab + t], 0, L - 1);        // the resampled window: a bad table never reads outside it
+        const int64_t row = Plan::kTables ? lift_clamp(k.base + start + f, 0, plan.frames - 1) : k.base + start + f;
+        x[i] = lift_clip_value(track, row * 51, j, c, plan.width(p), plan.shift_y(p), mirrored);
     }
 }
 
-// out [frames, 17, 3] from pred [(1+flip) * windows, T, 17, 3] in the clip order above: k_lift_stitch's loop over the windows of the frame's track.
-__global__ __launch_bounds__(256) void k_lift_stitch_ragged(const float* __restrict__ pred, int flip, int64_t windows, const int64_t* __restrict__ offsets,
-                                                            const int64_t* __restrict__ win_first, int P, int T, int stride, const int* __restrict__ first_pos,
-                                                            int64_t total, float* __restrict__ out) {
-    const int64_t clip_floats = (int64_t)T * 51;
+// out [frames, 17, 3] from pred [(1+flip) * windows, T, 17, 3] in the clip order above: the root zeroed, every other float the mean over its covering windows.
+template <class Plan>
+__global__ __launch_bounds__(256) void k_lift_stitch(const float* __restrict__ pred, int flip, Plan plan, int T, int stride, const int* __restrict__ first_pos,
+                                                     int64_t total, float* __restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t row = i / 51;
         const int q = (int)(i - row * 51), j = q / 3, c = q - 3 * j;
@@ -154,31 +98,8 @@ __global__ __launch_bounds__(256) void k_lift_stitch_ragged(const float* __restr
             out[i] = 0.0f;
             continue;
         }
-        const int p = lift_track_of(offsets, P, row);
-        const int64_t n = offsets[p + 1] - offsets[p], f = row - offsets[p], wb = win_first[p], W = win_first[p + 1] - wb;
-        const bool tail = stride < T && n > T;
-        const int64_t w_lo = f < T ? 0 : (f - T) / stride + 1, last_regular = tail ? W - 2 : W - 1;
-        const int64_t w_hi = f / stride < last_regular ? f / stride : last_regular;
-        float acc = 0.0f;
-        int cnt = 0;
-        for (int64_t w = w_lo; w <= w_hi + (tail && f >= n - T ? 1 : 0); ++w) {
-            const int64_t start = w > w_hi ? n - T : w * stride;
-            const int64_t L = n - start < T ? n - start : T;
-            int64_t t = lift_clamp(f - start, 0, T - 1);
-            if (L < T) {
-                const int64_t ft = first_pos[(int64_t)p * T + t];
-                t = ft < 0 ? 0 : (ft >= T ? T - 1 : ft);
-            }
-            const int64_t o = lift_clamp(wb + (w > w_hi ? W - 1 : w), 0, windows - 1) * clip_floats + t * 51;
-            float v = pred[o + q];
-            if (flip) {
-                const float fv = pred[windows * clip_floats + o + 3 * c_lift_flip_src[j] + c];
-                v = (v + (c == 0 ? -fv : fv)) / 2;
-            }
-            acc += v;
-            ++cnt;
-        }
-        out[i] = acc / (float)cnt;
+        const LiftSpan k = plan.span(plan.row_track(row));
+        out[i] = lift_cover_mean<Plan::kTables>(pred, flip, plan.windows, row - k.base, k.n, k.W, k.wb, T, stride, first_pos + k.tab, j, c);
     }
 }
 
@@ -205,8 +126,8 @@ __global__ __launch_bounds__(256) void k_stream_push(const float* __restrict__ f
     }
 }
 
-// x [(1+flip) * K, T, 17, 3]: clip h * K + i is the current window of slot i of the call, mirrored when h == 1; k_lift_windows_ragged's arithmetic with the
-// slot's width and height.  Clip frame t is window frame resample_tab[L][t], i.e. ring position (k - L + that) % T.
+// x [(1+flip) * K, T, 17, 3]: clip h * K + i is the current window of slot i of the call, mirrored when h == 1, normalised with the slot's width and
+// height.  Clip frame t is window frame resample_tab[L][t], i.e. ring position (k - L + that) % T.
 __global__ __launch_bounds__(256) void k_stream_windows(const float* __restrict__ ring, const int64_t* __restrict__ count, const int* __restrict__ slots,
                                                         int64_t K, int S, int T, const float* __restrict__ width, const float* __restrict__ height,
                                                         const int* __restrict__ resample_tab, int64_t total, float* __restrict__ x) {
@@ -218,20 +139,13 @@ __global__ __launch_bounds__(256) void k_stream_windows(const float* __restrict_
         const int64_t slot = stream_slot(slots, mirrored ? clip - K : clip, S);
         const int64_t kc = count[slot], k = kc < 1 ? 1 : kc, L = k < T ? k : T;
         const int64_t f = lift_clamp(resample_tab[L * T + t], 0, L - 1);
-        const int js = mirrored ? c_lift_flip_src[j] : j;
-        float v = ring[(slot * T + (k - L + f) % T) * 51 + 3 * js + c];
-        if (c < 2) {
-            const float wp = width[slot];
-            const float scaled = v / wp * 2.0f;
-            v = (float)((double)scaled - (c == 0 ? 1.0 : (double)height[slot] / (double)wp));
-            if (mirrored && c == 0) v = -v;
-        }
-        x[i] = v;
+        const float wp = width[slot];
+        x[i] = lift_clip_value(ring, (slot * T + (k - L + f) % T) * 51, j, c, wp, (double)height[slot] / (double)wp, mirrored);
     }
 }
 
 // out [K, n_out, 17, 3] from pred [(1+flip) * K, T, 17, 3] in the clip order above: row r of slot i is window frame clamp(L - 1 - back + r, 0, L - 1), read at
-// clip position first_pos_tab[L][that] and merged as k_lift_stitch merges a frame that one window covers.
+// clip position first_pos_tab[L][that] and merged as a frame that one window covers: lift_cover_mean's 0.0f + v, divided by 1.
 __global__ __launch_bounds__(256) void k_stream_emit(const float* __restrict__ pred, int flip, const int64_t* __restrict__ count, const int* __restrict__ slots,
                                                      int64_t K, int S, int T, const int* __restrict__ first_pos_tab, int back, int n_out, int64_t total,
                                                      float* __restrict__ out) {
@@ -248,12 +162,7 @@ __global__ __launch_bounds__(256) void k_stream_emit(const float* __restrict__ p
         const int64_t jw = lift_clamp(L - 1 - back + r, 0, L - 1);
         const int64_t t = lift_clamp(first_pos_tab[L * T + jw], 0, T - 1);
         const int64_t o = g * clip_floats + t * 51;
-        float v = pred[o + q];
-        if (flip) {
-            const float fv = pred[K * clip_floats + o + 3 * c_lift_flip_src[j] + c];
-            v = (v + (c == 0 ? -fv : fv)) / 2;
-        }
-        out[i] = 0.0f + v;                             // k_lift_stitch's sum over the one covering window, divided by 1
+        out[i] = 0.0f + lift_merge(pred, o, K * clip_floats + o, j, c, flip);
     }
 }
 
@@ -269,30 +178,32 @@ void kasf_launch_lift_windows(hipStream_t s, const float* track, int P, int64_t 
     const int64_t W = kasf_lift_window_count_of(n, T, stride);
     const int64_t per_half = (int64_t)P * W, total = (flip ? 2 : 1) * per_half * T * 51;
     if (total <= 0) return;
-    hipLaunchKernelGGL(k_lift_windows, dim3(grid_for(total)), dim3(256), 0, s, track, n, W, T, stride, resample, width, (double)height / (double)width,
-                       per_half, total, x);
+    const UniformPlan plan{n, W, (int64_t)P * n, per_half, width, (double)height / (double)width};
+    hipLaunchKernelGGL(k_lift_windows<UniformPlan>, dim3(grid_for(total)), dim3(256), 0, s, track, plan, T, stride, resample, total, x);
 }
 
 void kasf_launch_lift_stitch(hipStream_t s, const float* pred, int flip, int P, int64_t n, int T, int stride, const int* first_pos, float* out) {
     const int64_t W = kasf_lift_window_count_of(n, T, stride);
     const int64_t total = (int64_t)P * n * 51;
     if (total <= 0 || W <= 0) return;
-    hipLaunchKernelGGL(k_lift_stitch, dim3(grid_for(total)), dim3(256), 0, s, pred, flip, n, W, T, stride, first_pos, (int64_t)P * W, total, out);
+    const UniformPlan plan{n, W, (int64_t)P * n, (int64_t)P * W, 0.0f, 0.0};
+    hipLaunchKernelGGL(k_lift_stitch<UniformPlan>, dim3(grid_for(total)), dim3(256), 0, s, pred, flip, plan, T, stride, first_pos, total, out);
 }
 
 void kasf_launch_lift_windows_ragged(hipStream_t s, const float* track, int64_t frames, const int64_t* offsets, const int64_t* win_first, int P,
                                      int64_t windows, const float* width, const float* height, int T, int stride, const int* resample, int flip, float* x) {
     const int64_t total = (flip ? 2 : 1) * windows * T * 51;
     if (total <= 0 || P <= 0 || frames <= 0) return;
-    hipLaunchKernelGGL(k_lift_windows_ragged, dim3(grid_for(total)), dim3(256), 0, s, track, frames, offsets, win_first, P, windows, width, height, T, stride,
-                       resample, total, x);
+    const RaggedPlan plan{offsets, win_first, width, height, P, T, frames, windows};
+    hipLaunchKernelGGL(k_lift_windows<RaggedPlan>, dim3(grid_for(total)), dim3(256), 0, s, track, plan, T, stride, resample, total, x);
 }
 
 void kasf_launch_lift_stitch_ragged(hipStream_t s, const float* pred, int flip, int64_t windows, const int64_t* offsets, const int64_t* win_first, int P,
                                     int64_t frames, int T, int stride, const int* first_pos, float* out) {
     const int64_t total = frames * 51;
     if (total <= 0 || P <= 0 || windows <= 0) return;
-    hipLaunchKernelGGL(k_lift_stitch_ragged, dim3(grid_for(total)), dim3(256), 0, s, pred, flip, windows, offsets, win_first, P, T, stride, first_pos, total, out);
+    const RaggedPlan plan{offsets, win_first, nullptr, nullptr, P, T, frames, windows};
+    hipLaunchKernelGGL(k_lift_stitch<RaggedPlan>, dim3(grid_for(total)), dim3(256), 0, s, pred, flip, plan, T, stride, first_pos, total, out);
 }
 
 void kasf_launch_stream_push(hipStream_t s, const float* frames, const int* slots, int K, int S, int T, float* ring, int64_t* count) {

@@ -11,32 +11,21 @@
 //
 // Valid rows of a launch have distinct g, so every ring / count / owner entry is read and written by one workgroup only: no atomics, no hand-off between
 // workgroups, the same bits from run to run.  Every index formed from a device value (count_b, slot, count, table entry) is clamped into the arrays the host sized.
+// The clip value and the flip-TTA merge are lift_math.h's, the ones k_lift.hip's kernels compute with.
 #include "kernels.h"
 
 namespace {
 
-// k_lift.hip's c_lift_flip_src (utils/utilities.py:128-135): destination joint j takes source joint c_track_flip_src[j]
-__constant__ int c_track_flip_src[17] = {0, 4, 5, 6, 1, 2, 3, 7, 8, 9, 10, 14, 15, 16, 11, 12, 13};
-
-__device__ inline int64_t track_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // Track row of row k of a stream with cb emitted tracks, k < cb.
 __device__ inline int track_row(int rows_mode, int cb, int k) { return rows_mode == KASF_ROWS_PERSONS ? cb - 1 - k : k; }
 
-// Float e of a clip of the slot whose count is k (>= 1, the new frame included) and window length L: k_stream_windows' arithmetic operation for operation.  The
-// window's newest frame is read from the caller's frame, the older ones from ring positions this launch does not write.
+// Float e of a clip of the slot whose count is k (>= 1, the new frame included) and window length L.  The window's newest frame is read from the caller's
+// frame, the older ones from ring positions this launch does not write.
 __device__ inline float track_clip_value(const float* ring_slot, const float* __restrict__ frame, const int* __restrict__ resample_row, int64_t k, int64_t L, int T,
                                          float wp, float hp, bool mirrored, int e) {
     const int t = e / 51, q = e - t * 51, j = q / 3, c = q - 3 * j;
-    const int64_t f = track_clamp(resample_row[t], 0, L - 1);
-    const int js = mirrored ? c_track_flip_src[j] : j;
-    float v = f == L - 1 ? frame[3 * js + c] : ring_slot[((k - L + f) % T) * 51 + 3 * js + c];
-    if (c < 2) {
-        const float scaled = v / wp * 2.0f;
-        v = (float)((double)scaled - (c == 0 ? 1.0 : (double)hp / (double)wp));
-        if (mirrored && c == 0) v = -v;
-    }
-    return v;
+    const int64_t f = lift_clamp(resample_row[t], 0, L - 1);
+    return lift_clip_value(f == L - 1 ? frame : ring_slot, f == L - 1 ? 0 : ((k - L + f) % T) * 51, j, c, wp, (double)hp / (double)wp, mirrored);
 }
 
 // One workgroup per row.  x [(1 + flip) * n_rows, T, 17, 3]: clip h * n_rows + row, h == 1 mirrored.  ring is read and written here, so it carries no __restrict__.
@@ -49,17 +38,17 @@ __global__ __launch_bounds__(256) void k_stream_track_front(const float* __restr
     const int clip_floats = T * 51, halves = flip ? 2 : 1;
     for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
         const int b = (int)(row / R), k = (int)(row - (int64_t)b * R);
-        const int cb = (int)track_clamp(count_b[b], 0, S_t);
+        const int cb = (int)lift_clamp(count_b[b], 0, S_t);
         const int* ids_b = ids + (int64_t)b * S_t;
         const int* slot_b = slot + (int64_t)b * S_t;
         bool valid = k < cb;                                       // k < R by construction
-        const int r = (int)track_clamp(track_row(rows_mode, cb, k), 0, S_t - 1);
+        const int r = (int)lift_clamp(track_row(rows_mode, cb, k), 0, S_t - 1);
         const int id = ids_b[r], s = slot_b[r];
         valid = valid && id >= 1 && s >= 0 && s < S_t;
         // the lower rows of this stream, one per thread (k < cb <= S_t <= 64 where it matters): the lowest row of a slot wins
         bool hit = false;
         if (valid && (int)threadIdx.x < k) {
-            const int r2 = (int)track_clamp(track_row(rows_mode, cb, (int)threadIdx.x), 0, S_t - 1);
+            const int r2 = (int)lift_clamp(track_row(rows_mode, cb, (int)threadIdx.x), 0, S_t - 1);
             hit = ids_b[r2] >= 1 && slot_b[r2] == s;
         }
         if (__syncthreads_or(hit ? 1 : 0)) valid = false;
@@ -134,15 +123,10 @@ __global__ __launch_bounds__(256) void k_stream_track_emit(const float* __restri
             continue;
         }
         const int64_t kc = count[g], k = kc < 1 ? 1 : kc, L = k < T ? k : T;
-        const int64_t jw = track_clamp(L - 1 - back, 0, L - 1);
-        const int64_t t = track_clamp(first_pos_tab[L * T + jw], 0, T - 1);
+        const int64_t jw = lift_clamp(L - 1 - back, 0, L - 1);
+        const int64_t t = lift_clamp(first_pos_tab[L * T + jw], 0, T - 1);
         const int64_t o = row * clip_floats + t * 51;
-        float v = pred[o + q];
-        if (flip) {
-            const float fv = pred[n_rows * clip_floats + o + 3 * c_track_flip_src[j] + c];
-            v = (v + (c == 0 ? -fv : fv)) / 2;
-        }
-        out[i] = 0.0f + v;                             // as k_stream_emit: the sum over the one covering window, divided by 1
+        out[i] = 0.0f + lift_merge(pred, o, n_rows * clip_floats + o, j, c, flip);    // as k_stream_emit: the sum over the one covering window, divided by 1
     }
 }
 

@@ -172,10 +172,7 @@ void kasf_launch_gather_clips(hipStream_t s, const float* xa, const float* ya, c
                               int T, float* xo, float* yo);
 
 // ---- k_lift.hip: windows of a 2-D track in, 3-D poses back on the track (kasf.h, kasf_lift_*) ----
-// Windows of T frames over an n-frame track: none for n = 0, one for n <= T, else ceil((n - T) / stride) + 1 (stride == T: ceil(n / T)).
-inline int64_t kasf_lift_window_count_of(int64_t n, int T, int stride) {
-    return n <= 0 ? 0 : (n <= T ? 1 : (n - T + stride - 1) / stride + 1);
-}
+#include "lift_math.h"   // kasf_lift_window_count_of and the device arithmetic the lifting kernels share
 void kasf_launch_lift_windows(hipStream_t s, const float* track, int P, int64_t n, float width, float height, int T, int stride, const int* resample, int flip,
                               float* x);
 void kasf_launch_lift_stitch(hipStream_t s, const float* pred, int flip, int P, int64_t n, int T, int stride, const int* first_pos, float* out);

@@ -139,11 +139,7 @@ def lift_track(model, keypoints, width, height, *, stride=None, flip: bool = Tru
     kp4 = kp if kp.dim() == 4 else kp.unsqueeze(0)
     P, n = int(kp4.shape[0]), int(kp4.shape[1])
     T = int(model.n_frames)
-    stride = T if stride is None else int(stride)
-    if not 1 <= stride <= T:
-        raise ValueError(f"lift_track: stride must be in [1, T={T}], got {stride}")
-    if int(max_windows) < 1:
-        raise ValueError("lift_track: max_windows must be >= 1")
+    stride = _stride(T, stride, max_windows, "lift_track")
     if not (float(width) > 0 and float(height) > 0):
         raise ValueError("lift_track: width and height must be positive")
     if P == 0 or n == 0:
@@ -162,37 +158,33 @@ def lift_track(model, keypoints, width, height, *, stride=None, flip: bool = Tru
         x = torch.empty((halves * PW, T, 17, 3), dtype=torch.float32, device=device)
         _lib.check(lib.kasf_lift_windows(kp4.data_ptr(), P, n, float(width), float(height), T, stride,
                                          r_dev.data_ptr() if r_dev is not None else None, int(flip), x.data_ptr(), _stream()))
-        was_training = model.training
-        model.eval()
-        try:
-            if PW <= max_windows:
-                pred = model(x)                                      # the whole lift in one stacked batch
-            else:
-                pred = torch.empty_like(x)
-                for a in range(0, PW, max_windows):
-                    b = min(a + max_windows, PW)
-                    idx = [slice(h * PW + a, h * PW + b) for h in range(halves)]
-                    out = model(torch.cat([x[i] for i in idx]) if flip else x[idx[0]])
-                    for h, i in enumerate(idx):
-                        pred[i].copy_(out[h * (b - a):(h + 1) * (b - a)])
-        finally:
-            model.train(was_training)
+        pred = _forward_windows(model, x, PW, halves, int(max_windows))
         poses = torch.empty((P, n, 17, 3), dtype=torch.float32, device=device)
         _lib.check(lib.kasf_lift_stitch(pred.data_ptr(), int(flip), P, n, T, stride, fp_dev.data_ptr() if fp_dev is not None else None,
                                         poses.data_ptr(), _stream()))
     return poses.view(lead + (17, 3))
 
 
-def _per_track(value, P: int, name: str) -> np.ndarray:
-    """``width`` / ``height``: one value for every track or one per track -> float32 [P] (what the C entry points receive)."""
+def _stride(T: int, stride, max_windows, who: str) -> int:
+    """The ``stride`` (None: T) and ``max_windows`` of a call, checked -> the stride."""
+    stride = T if stride is None else int(stride)
+    if not 1 <= stride <= T:
+        raise ValueError(f"{who}: stride must be in [1, T={T}], got {stride}")
+    if int(max_windows) < 1:
+        raise ValueError(f"{who}: max_windows must be >= 1")
+    return stride
+
+
+def _per_row(value, count: int, name: str, who: str, unit: str) -> np.ndarray:
+    """``width`` / ``height``: one value for every track (slot, stream: ``unit``) or one per track -> float32 [count] (what the C entry points receive)."""
     v = np.asarray(value.detach().cpu() if isinstance(value, torch.Tensor) else value, dtype=np.float64)
     if v.ndim == 0:
-        v = np.full(P, v)
-    elif v.shape != (P,):
-        raise ValueError(f"lift_tracks: {name} must be one value or one per track ({P}), got shape {v.shape}")
+        v = np.full(count, v)
+    elif v.shape != (count,):
+        raise ValueError(f"{who}: {name} must be one value or one per {unit} ({count}), got shape {v.shape}")
     v = v.astype(np.float32)
     if not np.all(v > 0):
-        raise ValueError("lift_tracks: width and height must be positive")
+        raise ValueError(f"{who}: width and height must be positive")
     return v
 
 
@@ -244,11 +236,7 @@ def lift_tracks(model, tracks, width, height, *, stride=None, flip: bool = True,
     coco = check_layout(layout, "lift_tracks")
     device = _model_device(model, "lift_tracks")
     T = int(model.n_frames)
-    stride = T if stride is None else int(stride)
-    if not 1 <= stride <= T:
-        raise ValueError(f"lift_tracks: stride must be in [1, T={T}], got {stride}")
-    if int(max_windows) < 1:
-        raise ValueError("lift_tracks: max_windows must be >= 1")
+    stride = _stride(T, stride, max_windows, "lift_tracks")
     if offsets is None:
         parts = [_as_tensor(a, device, "lift_tracks") for a in tracks]
         for a in parts:
@@ -265,7 +253,7 @@ def lift_tracks(model, tracks, width, height, *, stride=None, flip: bool = True,
             raise ValueError(f"lift_tracks: offsets must be integers [P+1] from 0 up to the packed length {packed.shape[0]}, non-decreasing")
         off = off.astype(np.int64)
     P = len(off) - 1
-    w32, h32 = _per_track(width, P, "width"), _per_track(height, P, "height")
+    w32, h32 = _per_row(width, P, "width", "lift_tracks", "track"), _per_row(height, P, "height", "lift_tracks", "track")
     lengths = np.diff(off)
     win_first, resample, first_pos = ragged_plan(lengths, T, stride)
     frames, windows = int(off[-1]), int(win_first[-1])

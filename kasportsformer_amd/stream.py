@@ -23,7 +23,7 @@ import torch
 from . import _lib
 from .heatmap import check_heatmap_args, decode
 from .pose import check_layout, convert_frames
-from .lift import _as_tensor, _forward_windows, _model_device, _stream, _upload, window_plan
+from .lift import _as_tensor, _forward_windows, _model_device, _per_row, _stream, _upload, window_plan
 
 
 def stream_tables(T: int):
@@ -40,17 +40,21 @@ def stream_tables(T: int):
     return resample, first_pos
 
 
-def _per_slot(value, S: int, name: str) -> np.ndarray:
-    """``width`` / ``height``: one value for every slot or one per slot -> float32 [S]."""
-    v = np.asarray(value.detach().cpu() if isinstance(value, torch.Tensor) else value, dtype=np.float64)
-    if v.ndim == 0:
-        v = np.full(S, v)
-    elif v.shape != (S,):
-        raise ValueError(f"StreamLifter: {name} must be one value or one per slot ({S}), got shape {v.shape}")
-    v = v.astype(np.float32)
-    if not np.all(v > 0):
-        raise ValueError("StreamLifter: width and height must be positive")
-    return v
+def _checked_tables(lib, T: int, who: str):
+    """``stream_tables(T)``, held to what the library's ``kasf_stream_tables`` builds."""
+    r_tab, fp_tab = stream_tables(T)
+    c_r, c_fp = np.full_like(r_tab, -1), np.full_like(fp_tab, -1)
+    if lib.kasf_stream_tables(T, c_r.ctypes.data, c_fp.ctypes.data) != 0 or not np.array_equal(c_r, r_tab) or not np.array_equal(c_fp, fp_tab):
+        raise _lib.KasfError(f"{who}: the library's window tables disagree with stream_tables (stale build?)")
+    return r_tab, fp_tab
+
+
+def _decode_on(device, hm, parts, kind, aspect, refine: bool, h36m: bool, who: str) -> torch.Tensor:
+    """``push_heatmaps``: the checked heatmaps and their geometry, refused when on another GPU, decoded on ``device`` -> keypoints [n,17,3]."""
+    for t in (hm,) + parts:
+        if t.is_cuda and t.device != device:
+            raise RuntimeError(f"{who}: input on {t.device}, the model on {device}")
+    return decode(hm.to(device), tuple(t.to(device) for t in parts), kind, aspect, refine, h36m)
 
 
 class StreamLifter:
@@ -70,18 +74,11 @@ class StreamLifter:
         self.lag = int(lag)
         if not 0 <= self.lag <= T - 1:
             raise ValueError(f"StreamLifter: lag must be in [0, T - 1 = {T - 1}], got {lag}")
-        w32, h32 = _per_slot(width, S, "width"), _per_slot(height, S, "height")
+        w32, h32 = _per_row(width, S, "width", "StreamLifter", "slot"), _per_row(height, S, "height", "StreamLifter", "slot")
         one = all((v.dim() if isinstance(v, torch.Tensor) else np.ndim(v)) == 0 for v in (width, height))
         self._one_resolution = (float(w32[0]), float(h32[0])) if one else None      # what replay lifts a recorded track at
-        self._lib = lib = _lib.load()
-        if _tables is None:
-            r_tab, fp_tab = stream_tables(T)
-            c_r, c_fp = np.full_like(r_tab, -1), np.full_like(fp_tab, -1)
-            if (lib.kasf_stream_tables(T, c_r.ctypes.data, c_fp.ctypes.data) != 0 or not np.array_equal(c_r, r_tab)
-                    or not np.array_equal(c_fp, fp_tab)):
-                raise _lib.KasfError("StreamLifter: the library's window tables disagree with stream_tables (stale build?)")
-            _tables = (r_tab, fp_tab)
-        self._tables = _tables
+        self._lib = _lib.load()
+        self._tables = _tables = _checked_tables(self._lib, T, "StreamLifter") if _tables is None else _tables
         self._r_tab, self._fp_tab, self._width, self._height = _upload(self.device, _tables[0], _tables[1], w32, h32)
         self._ring = torch.zeros((S, T, 17, 3), dtype=torch.float32, device=self.device)
         self._count = torch.zeros(S, dtype=torch.int64, device=self.device)
@@ -160,11 +157,7 @@ class StreamLifter:
         K = self.slots if ids is None else int(ids.size)
         if hm.dim() != 4 or hm.shape[0] != K:
             raise ValueError(f"{who}: expected heatmaps [{K},17,H,W] (one person per pushed slot), got {tuple(hm.shape)}")
-        for t in (hm,) + parts:
-            if t.is_cuda and t.device != self.device:
-                raise RuntimeError(f"{who}: input on {t.device}, the model on {self.device}")
-        kp = decode(hm.to(self.device), tuple(t.to(self.device) for t in parts), kind, aspect, refine, not self._coco)
-        return self.push(kp, slots=slots)
+        return self.push(_decode_on(self.device, hm, parts, kind, aspect, refine, not self._coco, who), slots=slots)
 
     def tail(self, slots=None) -> torch.Tensor:
         """The ``lag`` frames ``push`` has not emitted yet, from the current windows, for the end of a track: [K,lag,17,3], row r = frame
@@ -209,7 +202,7 @@ class StreamLifter:
         out = torch.empty((P, N, 17, 3), dtype=torch.float32, device=self.device)
         if P == 0 or N == 0:
             if P > 0:
-                _per_slot(width, P, "width"), _per_slot(height, P, "height")
+                _per_row(width, P, "width", "StreamLifter", "slot"), _per_row(height, P, "height", "StreamLifter", "slot")
             return out.view(lead + (17, 3))
         temp = StreamLifter(self.model, width, height, slots=P, flip=self.flip, lag=lag, layout=self.layout, _tables=self._tables)
         ticks = kp4.to(self.device).transpose(0, 1).contiguous()   # [N,P,17,3]: one upload, every tick reads its frame in place

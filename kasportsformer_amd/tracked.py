@@ -33,10 +33,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .heatmap import check_heatmap_args, decode
-from .lift import _as_tensor, _forward_windows, _model_device, _stream, _upload
+from .heatmap import check_heatmap_args
+from .lift import _as_tensor, _forward_windows, _model_device, _per_row, _stream, _upload
 from .pose import check_layout, convert_frames
-from .stream import stream_tables
+from .stream import _checked_tables, _decode_on
 from .track import MAX_PERSONS, MAX_SLOTS, MAX_STREAMS, _int
 
 ROWS = ("persons", "tracks")
@@ -47,18 +47,6 @@ class TrackedTick(NamedTuple):
     valid: torch.Tensor          # CUDA bool [B, R]
     ids: torch.Tensor            # CUDA int32 [B, R]: the track id of the row (TrackResult.ids), 0 for an invalid row
     frames: torch.Tensor         # CUDA int64 [B, R]: frames in the row's history after this push, 0 for an invalid row
-
-
-def _per_stream(value, B: int, name: str, who: str) -> np.ndarray:
-    v = np.asarray(value.detach().cpu() if isinstance(value, torch.Tensor) else value, dtype=np.float64)
-    if v.ndim == 0:
-        v = np.full(B, v)
-    elif v.shape != (B,):
-        raise ValueError(f"{who}: {name} must be one value or one per stream ({B}), got shape {v.shape}")
-    v = v.astype(np.float32)
-    if not np.all(v > 0):
-        raise ValueError(f"{who}: width and height must be positive")
-    return v
 
 
 def check_tracked_args(T, width, height, streams, track_slots, rows, num_person, lag, layout, who: str = "TrackedLifter"):
@@ -74,7 +62,7 @@ def check_tracked_args(T, width, height, streams, track_slots, rows, num_person,
     track_slots = _int(track_slots, who, "track_slots", 1, MAX_SLOTS)
     num_person = _int(num_person, who, "num_person", 1, MAX_PERSONS)
     lag = _int(lag, who, "lag", 0, T - 1)
-    w32, h32 = _per_stream(width, streams, "width", who), _per_stream(height, streams, "height", who)
+    w32, h32 = _per_row(width, streams, "width", who, "stream"), _per_row(height, streams, "height", who, "stream")
     R = num_person if rows == "persons" else track_slots
     return T, w32, h32, streams, track_slots, (_lib.ROWS_PERSONS if rows == "persons" else _lib.ROWS_TRACKS), R, lag, coco
 
@@ -127,11 +115,8 @@ class TrackedLifter:
             model.n_frames, width, height, streams, track_slots, rows, num_person, lag, layout, who)
         self.model, self.flip, self.rows, self.layout = model, bool(flip), rows, layout
         T, n = self.T, self.streams * self.track_slots
-        self._lib = lib = _lib.load()
-        r_tab, fp_tab = stream_tables(T)
-        c_r, c_fp = np.full_like(r_tab, -1), np.full_like(fp_tab, -1)
-        if lib.kasf_stream_tables(T, c_r.ctypes.data, c_fp.ctypes.data) != 0 or not np.array_equal(c_r, r_tab) or not np.array_equal(c_fp, fp_tab):
-            raise _lib.KasfError(f"{who}: the library's window tables disagree with stream_tables (stale build?)")
+        self._lib = _lib.load()
+        r_tab, fp_tab = _checked_tables(self._lib, T, who)
         self._r_tab, self._fp_tab, self._width, self._height = _upload(self.device, r_tab, fp_tab, w32, h32)
         self._ring = torch.zeros((n, T, 17, 3), dtype=torch.float32, device=self.device)
         self._count = torch.zeros(n, dtype=torch.int64, device=self.device)
@@ -199,8 +184,4 @@ class TrackedLifter:
         if track is None:
             raise TypeError(f"{who}: track (the TrackResult of this tick) is required")
         check_tracked_tick(track, self.streams, self.track_slots, self.device, who)
-        for t in (hm,) + parts:
-            if t.is_cuda and t.device != self.device:
-                raise RuntimeError(f"{who}: input on {t.device}, the model on {self.device}")
-        kp = decode(hm.to(self.device), tuple(t.to(self.device) for t in parts), kind, aspect, refine, not self._coco)
-        return self.push(kp, track)
+        return self.push(_decode_on(self.device, hm, parts, kind, aspect, refine, not self._coco, who), track)

@@ -10,52 +10,11 @@ import pytest
 import torch
 
 from tests.gpu_util import make_pair, ptr, stream
+from tests.lift_ref import H_PX, W_PX, _stitch_t, _track, _windows_np
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-LEFT, RIGHT = [1, 2, 3, 14, 15, 16], [4, 5, 6, 11, 12, 13]
-W_PX, H_PX = 1280, 720
-
-
-def _flip_np(a):
-    """flip_data (demo/lib/utils.py:5-13) on a copy."""
-    f = a.copy()
-    f[..., 0] *= -1
-    f[..., LEFT + RIGHT, :] = f[..., RIGHT + LEFT, :]
-    return f
-
-
-def _flip_t(a):
-    f = a.clone()
-    f[..., 0] *= -1
-    f[..., LEFT + RIGHT, :] = f[..., RIGHT + LEFT, :]
-    return f
-
-
-def _track(P, N, seed):
-    g = np.random.default_rng(seed)
-    xy = g.uniform((0, 0), (W_PX, H_PX), size=(P, N, 17, 2))
-    return np.concatenate((xy, g.uniform(0.2, 1.0, size=(P, N, 17, 1))), axis=-1).astype(np.float32)
-
-
-def _windows_np(kp, T, s, flip):
-    """The demo's clips (or the overlap plan) of every person, normalised with normalize_screen_coordinates's own expression."""
-    from kasportsformer_amd.lift import window_plan
-    starts, lengths, r, _ = window_plan(kp.shape[1], T, s)
-    clips = []
-    for p in range(kp.shape[0]):
-        for a, L in zip(starts, lengths):
-            c = kp[p, a:a + L]
-            if L < T:
-                c = c[r]
-            res = np.copy(c)
-            res[..., :2] = c[..., :2] / W_PX * 2 - [1, H_PX / W_PX]
-            clips.append(res)
-    x = np.stack(clips)
-    return np.concatenate((x, _flip_np(x))) if flip else x
-
-
 CASES = [(1, 1, 27, 27), (1, 20, 27, 27), (2, 61, 27, 27), (1, 54, 27, 27), (3, 200, 81, 81), (2, 100, 27, 9), (1, 30, 27, 9),
          (1, 28, 27, 1), (2, 20, 27, 9), (1, 300, 81, 27)]
 
@@ -75,23 +34,6 @@ def test_windows_kernel_is_bit_exact(P, N, T, s, flip):
     torch.cuda.synchronize()
     assert torch.equal(x.cpu(), want)
     assert torch.equal(track.cpu(), torch.from_numpy(kp))
-
-
-def _stitch_t(pred, P, N, T, s, flip):
-    """(p + flip(p_f)) / 2, root zeroed, per window; frames of a resampled window read first_pos; covering windows summed in ascending order, then divided."""
-    from kasportsformer_amd.lift import window_plan
-    starts, lengths, _, fp = window_plan(N, T, s)
-    W = len(starts)
-    merged = (pred[:P * W] + _flip_t(pred[P * W:])) / 2 if flip else pred[:P * W].clone()
-    merged[:, :, 0, :] = 0
-    merged = merged.view(P, W, T, 17, 3)
-    acc = torch.zeros(P, N, 17, 3)
-    cnt = torch.zeros(N)
-    for w, (a, L) in enumerate(zip(starts, lengths)):
-        win = merged[:, w, torch.from_numpy(fp).long()] if L < T else merged[:, w]
-        acc[:, a:a + L] += win
-        cnt[a:a + L] += 1
-    return acc / cnt.view(1, N, 1, 1)
 
 
 @pytest.mark.parametrize("flip", [True, False])

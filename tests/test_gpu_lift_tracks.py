@@ -1,5 +1,5 @@
 """Lifting many tracks of different lengths in one call (kasportsformer_amd.lift_tracks, kasf_lift_windows_ragged / kasf_lift_stitch_ragged):
-both kernels bit-exact against tests/test_gpu_lift.py's per-track restatements in the packed clip order, the whole call against lift_track
+both kernels bit-exact against tests/lift_ref.py's per-track restatements in the packed clip order and, for equal lengths, against the uniform kernels, the whole call against lift_track
 track by track and against its parts, chunking, the reference demo's lifts (tests/golden/lift_e2e.npz), the call's contract and the CLI."""
 import os
 import pickle
@@ -11,7 +11,8 @@ import pytest
 import torch
 
 from tests.gpu_util import make_pair, ptr, stream
-from tests.test_gpu_lift import GOLDEN, H_PX, ROOT, W_PX, _flip_np, _stitch_t, _track
+from tests.lift_ref import H_PX, W_PX, _flip_np, _stitch_t, _track
+from tests.test_gpu_lift import GOLDEN, ROOT
 
 pytestmark = pytest.mark.gpu
 T = 27
@@ -116,6 +117,34 @@ def test_stitch_kernel_is_bit_exact(s, flip):
     torch.cuda.synchronize()
     assert torch.equal(out.cpu(), want)
     assert torch.equal(pred_d.cpu(), pred)
+
+
+@pytest.mark.parametrize("flip", [True, False])
+@pytest.mark.parametrize("N,s", [(1, 5), (3, 5), (5, 5), (10, 5), (13, 5), (6, 2), (12, 2)])
+def test_equal_lengths_give_the_uniform_kernels_bits(N, s, flip):
+    """Three tracks of one length at one resolution, T = 5: the ragged launches write the bits of kasf_lift_windows / kasf_lift_stitch -- a few launches, no model."""
+    from kasportsformer_amd import _lib
+    from kasportsformer_amd.lift import ragged_plan, window_plan
+    lib, P, T5, halves = _lib.load(), 3, 5, (2 if flip else 1)
+    w_px, h_px = RES[(N + s) % len(RES)]
+    _, _, r, fp = window_plan(N, T5, s)
+    wf, r_tab, fp_tab = ragged_plan([N] * P, T5, s)
+    windows = int(wf[-1])
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda() if a is not None else None      # noqa: E731
+    track, off, wf_d = d(_track(P, N, seed=N + s)), d(np.arange(P + 1, dtype=np.int64) * N), d(wf)
+    ws, hs = d(np.full(P, w_px, np.float32)), d(np.full(P, h_px, np.float32))
+    r_d, fp_d, r_tab_d, fp_tab_d = d(r), d(fp), d(r_tab), d(fp_tab)
+    x_u, x_r = (torch.full((halves * windows, T5, 17, 3), float("nan"), device="cuda") for _ in range(2))
+    _lib.check(lib.kasf_lift_windows(ptr(track), P, N, float(w_px), float(h_px), T5, s, ptr(r_d), int(flip), ptr(x_u), stream()))
+    _lib.check(lib.kasf_lift_windows_ragged(ptr(track), ptr(off), ptr(wf_d), P, P * N, windows, ptr(ws), ptr(hs), T5, s, ptr(r_tab_d), int(flip), ptr(x_r),
+                                            stream()))
+    pred = torch.randn((halves * windows, T5, 17, 3), generator=torch.Generator().manual_seed(N + 2 * flip)).cuda()
+    o_u, o_r = (torch.full((P, N, 17, 3), float("nan"), device="cuda") for _ in range(2))
+    _lib.check(lib.kasf_lift_stitch(ptr(pred), int(flip), P, N, T5, s, ptr(fp_d), ptr(o_u), stream()))
+    _lib.check(lib.kasf_lift_stitch_ragged(ptr(pred), int(flip), ptr(off), ptr(wf_d), P, P * N, windows, T5, s, ptr(fp_tab_d), ptr(o_r), stream()))
+    torch.cuda.synchronize()
+    assert torch.equal(x_r.view(torch.int32), x_u.view(torch.int32)) and not torch.isnan(x_u).any()
+    assert torch.equal(o_r.view(torch.int32), o_u.view(torch.int32)) and not torch.isnan(o_u).any()
 
 
 _MODELS = {}

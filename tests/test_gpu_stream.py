@@ -1,5 +1,5 @@
 """Lifting live keypoint streams frame by frame (kasportsformer_amd.StreamLifter, kasf_stream_push / _windows / _emit): the three kernels bit-exact
-against numpy / torch restatements built from tests/test_gpu_lift.py's, the rule (every pose is lift_track of the slot's current window) tick by
+against the numpy / torch restatements of tests/lift_ref.py, the rule (every pose is lift_track of the slot's current window) tick by
 tick, the call against its parts in both modes, replay against the rule and the reference demo's lifts (tests/golden/lift_e2e.npz), the contract
 and the CLI."""
 import os
@@ -11,7 +11,8 @@ import pytest
 import torch
 
 from tests.gpu_util import make_pair, ptr, stream
-from tests.test_gpu_lift import GOLDEN, H_PX, ROOT, W_PX, _flip_np, _stitch_t, _track
+from tests.lift_ref import H_PX, W_PX, _emit_t, _frames, _ring_state, _track, _windows_stream_np
+from tests.test_gpu_lift import GOLDEN, ROOT
 
 pytestmark = pytest.mark.gpu
 RES = [(1280, 720), (1920, 1080), (3840, 2160), (1000, 1000), (1437, 913), (640, 480), (800, 600)]
@@ -19,10 +20,6 @@ RES = [(1280, 720), (1920, 1080), (3840, 2160), (1000, 1000), (1437, 913), (640,
 
 def _ks(T):
     return [1, 2, T - 1, T, T + 1, 2 * T, 3 * T + 5]
-
-
-def _frames(n, seed):
-    return _track(1, n, seed=seed)[0]                                   # [n,17,3] pixels + confidence
 
 
 def _script(S, ticks, seed, always=()):
@@ -36,43 +33,6 @@ def _script(S, ticks, seed, always=()):
         ids = [int(i) for i in g.permutation(S)[:int(g.integers(1, S + 1))]]
         out.append(ids + [a for a in always if a not in ids])
     return out
-
-
-def _clip_np(w, T, w_px, h_px):
-    """test_gpu_lift._windows_np's expression on one window of L <= T frames (L < T: the demo's resampled clip), normalised at w_px x h_px."""
-    from kasportsformer_amd.lift import window_plan
-    r = window_plan(w.shape[0], T)[2]
-    c = w[r] if r is not None else w
-    res = np.copy(c)
-    res[..., :2] = c[..., :2] / w_px * 2 - [1, h_px / w_px]
-    return res
-
-
-def _windows_stream_np(windows, T, res, flip):
-    """Clip h * K + i: window i of the call, mirrored when h == 1."""
-    x = np.stack([_clip_np(w, T, *wh) for w, wh in zip(windows, res)])
-    return np.concatenate((x, _flip_np(x))) if flip else x
-
-
-def _emit_t(pred, Ls, T, back, n_out, flip):
-    """test_gpu_lift._stitch_t on each slot's one window (plain and mirrored clip), then rows clamp(L - 1 - back + r, 0, L - 1)."""
-    K = len(Ls)
-    rows = []
-    for i, L in enumerate(Ls):
-        mine = torch.cat((pred[i:i + 1], pred[K + i:K + i + 1])) if flip else pred[i:i + 1]
-        st = _stitch_t(mine, 1, L, T, T, flip)[0]
-        rows.append(st[[min(max(L - 1 - back + r, 0), L - 1) for r in range(n_out)]])
-    return torch.stack(rows)
-
-
-def _ring_state(T, ks, seed):
-    """Histories of ks[s] frames per slot and the ring / count they leave: frame number c at ring position c % T; unwritten positions hold -1."""
-    hist = [_frames(k, seed + 5 * s) for s, k in enumerate(ks)]
-    ring = np.full((len(ks), T, 17, 3), -1.0, np.float32)
-    for s, h in enumerate(hist):
-        for c in range(len(h)):
-            ring[s, c % T] = h[c]
-    return hist, ring, np.asarray(ks, np.int64)
 
 
 @pytest.mark.parametrize("T", [27, 81])

@@ -27,7 +27,8 @@ def emul(tmp_path_factory):
     d = tmp_path_factory.mktemp("tracked_host")
     for f in ("kernels.h", "emul.cpp"):
         shutil.copy(os.path.join(ROOT, "tests", "tracked_host", f), d)
-    shutil.copy(os.path.join(ROOT, "kasportsformer_amd", "csrc", "k_stream_track.hip"), d)       # its #include "kernels.h" now finds the stand-in
+    for f in ("k_stream_track.hip", "lift_math.h"):                                             # the kernel's #include "kernels.h" now finds the stand-in
+        shutil.copy(os.path.join(ROOT, "kasportsformer_amd", "csrc", f), d)
     r = subprocess.run([gxx, "-std=c++20", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-x", "c++", "-I.", "emul.cpp", "-o", "libemul.so", "-lpthread"],
                        cwd=d, capture_output=True, text=True)
     if r.returncode != 0 and "barrier" in r.stderr and "No such file" in r.stderr:

@@ -1,5 +1,5 @@
-// Host stand-in for csrc/kernels.h, for tests/test_tracked_host_cpu.py only: just what csrc/k_stream_track.hip needs to compile with g++, and a lockstep emulation
-// of its workgroups -- one host thread per GPU thread of a block, the blocks one after the other, a barrier at every __syncthreads / __syncthreads_or.  That is a
+// Host stand-in for csrc/kernels.h, for tests/test_tracked_host_cpu.py and tests/test_lift_host_cpu.py only: just what csrc/k_stream_track.hip and csrc/k_lift.hip
+// need to compile with g++, and a lockstep emulation of their workgroups -- one host thread per GPU thread of a block, the blocks one after the other, a barrier at every __syncthreads / __syncthreads_or.  That is a
 // faithful model exactly when every barrier sits in block-uniform control flow, which the kernels are written to guarantee; a barrier in divergent control flow
 // deadlocks here (the test's time limit reports it) instead of returning garbage.
 #pragma once
@@ -47,3 +47,4 @@ template <class F> void emul_launch(F f, unsigned nblocks, unsigned nthreads) {
     }
 }
 #define hipLaunchKernelGGL(kern, grid, block, lds, stream, ...) emul_launch([=]() { kern(__VA_ARGS__); }, (grid).x, (block).x)
+#include "lift_math.h"                                 // the real one, copied next to the kernel source by the fixture
