@@ -38,6 +38,9 @@
  *   kasf_crop_persons      <- PreProcess: box_to_center_scale, get_affine_transform, cv2.warpAffine, ToTensor, Normalize and the [2, 1, 0] channel swap: what the
  *                             demo does on the host between the person boxes and HRNet's input tensor
  *                             demo/lib/hrnet/lib/utils/utilitys.py:139-169, demo/lib/hrnet/gen_kpts.py:152-157, demo/lib/hrnet/lib/utils/transforms.py:58-101
+ *   kasf_letterbox_plan, kasf_letterbox_frames <- prep_image: letterbox_image (cv2.resize INTER_CUBIC onto a canvas of 128), the [:, :, ::-1] channel reversal,
+ *                             transpose and float().div(255.0): what the demo does on the host between a video frame and the YOLOv3 network's input
+ *                             demo/lib/yolov3/preprocess.py:9-38, demo/lib/yolov3/human_detector.py:131
  *   kasf_sort_update       <- Sort.update (KalmanBoxTracker, associate_detections_to_trackers, iou) and, from gen_video_kpts, the empty-frame hold and the
  *                             num_person oldest tracks: what the demo does on the host between the person boxes and the crops
  *                             demo/lib/sort/sort.py:15-222, demo/lib/hrnet/gen_kpts.py:111-148
@@ -394,6 +397,51 @@ int kasf_detect_boxes(const void* const* src, int32_t n_src, int32_t form, int32
 int kasf_crop_persons(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, const int32_t* frame_index,
                       const float* geom, int32_t geom_kind, double aspect, int64_t n, void* out, int32_t out_dtype, int32_t out_w, int32_t out_h,
                       const float* mean_std, int32_t swap_rb, float* center_scale_out, void* stream);
+
+/* ---- video frames -> detector inputs (ADDED under ABI 12: additive, kasf_version() stays 12; a caller checks for the two symbols by name).
+ * Replaces, on the device, the demo's prep_image (demo/lib/yolov3/preprocess.py:9-38, called at human_detector.py:131): letterbox_image = cv2.resize(frame,
+ * (new_w, new_h), INTER_CUBIC) placed on a canvas of 128, the [:, :, ::-1] channel reversal, the transpose to planes and float().div(255.0).  One launch on
+ * `stream` that writes EVERY element of out, padding included (no memset in front of it); the library allocates nothing.
+ * frames: uint8 (device), n_frames images of Hf rows of Wf pixels of 3 interleaved channels, all of one Hf x Wf; pixel (f, y, x) channel c is the byte at
+ * frames + f * frame_stride + y * row_stride + 3 * x + c, exactly as kasf_crop_persons reads it.  row_stride >= 3 * Wf: a decoder's padded pitch is read in
+ * place.  frames is only read.  out [n_frames][3][out_h][out_w] (device) of out_dtype = KASF_DTYPE_F32, _F16 or _BF16.  out_w and out_h are at most
+ * KASF_LETTERBOX_MAX_SIDE = 4096: the kernel keeps one table entry per output column in LDS (12 bytes each, 48 KiB at the limit).
+ * RULES.
+ *  1 geometry    letterbox_image in C doubles (the IEEE operations of the reference's Python floats): r = min((double)out_w / Wf, (double)out_h / Hf);
+ *                new_w = (int)(Wf * r), new_h = (int)(Hf * r), by truncation; pad_x = (out_w - new_w) / 2, pad_y = (out_h - new_h) / 2, by integer division.
+ *                The resized image occupies rows [pad_y, pad_y + new_h) and columns [pad_x, pad_x + new_w) of every plane; everything else is padding.
+ *                kasf_letterbox_plan returns these four numbers (host only, no device); new_w < 1 or new_h < 1 -- a frame so elongated that the reference's
+ *                cv2.resize would raise -- is error 2.
+ *  2 positions   per axis, shown for x (y: Hf, new_h, dy): scale_x = 1.0 / ((double)new_w / (double)Wf), two roundings in that order;
+ *                fx = (float)((dx + 0.5) * scale_x - 0.5) for column dx of the resized image, product and subtraction in double and not contracted;
+ *                sx = floorf(fx), t = fx - sx in fp32.  The four weights in fp32 with A = -0.75f, every operation rounded once, in exactly this order:
+ *                  c0 = ((A*(t+1) - 5*A)*(t+1) + 8*A)*(t+1) - 4*A       c1 = ((A+2)*t - (A+3))*t*t + 1
+ *                  c2 = ((A+2)*(1-t) - (A+3))*(1-t)*(1-t) + 1           c3 = 1 - c0 - c1 - c2   (left to right)
+ *                a[k] = (int)rintf(c[k] * 2048.0f), round half to even; every value fits a short.  b[k] is the same for a row.
+ *  3 value       integers only.  Tap k of an axis is source index clamp(sx - 1 + k, 0, Wf - 1): the edge is replicated; rows clamp the same way with Hf.
+ *                V = sum_ky b[ky] * sum_kx a[kx] * src[row_ky][col_kx][c];  v = clamp((V + (1 << 21)) >> 22, 0, 255), an arithmetic shift.  |V| < 2^31 for every
+ *                frame (255 * 1.375^2 * 2^22 = 2.02e9 bounds it; 1.53e9 is the largest seen, on frames of 0 / 255 noise), and integer sums are exact, so the
+ *                16-tap form and a horizontal-then-vertical form give the same v.  No antialiasing when shrinking (the reference has none either).
+ *  4 output      plane k of a resized pixel is (float)v / 255.0f, one fp32 division, of frame channel 2 - k with swap_rb != 0 (the reference's [:, :, ::-1]),
+ *                of channel k otherwise.  Padding is (float)pad_value / 255.0f in every plane (the reference: 128).  fp16 / bf16 outputs are the
+ *                round-to-nearest-even of that fp32 value.
+ *  5 determinism no atomics, no scratch, nothing that depends on n_frames: a frame's planes are a function of that frame alone; the same bits from run to run.
+ * ACCURACY of rules 2-3 against exact cubic convolution (fp64, A = -0.75, positions (dx + 0.5) Wf / new_w - 0.5, replicated edge, clamped to [0, 255]):
+ * at most 1.25 grey levels on every pixel = 0.5 for the final rounding + about 0.69 for the 11-bit coefficients (each is off by at most 2^-12, so a pass is
+ * off by at most 255 * 2^-12 * 4 = 0.25 times the other pass's sum of |weights| <= 1.375: 0.34 for the columns as the rows amplify them, 0.34 for the rows
+ * applied to column sums of up to 255 * 1.375) + about 0.03 for the fp32 position at coordinates up to 1920.  Measured worst case: 0.75 (tests/test_letterbox_cpu.py).
+ * NOT VERIFIED: rules 2 and 3 restate the fixed-point scheme of OpenCV's portable 8-bit resize(INTER_CUBIC) -- 11-bit coefficients, two passes, a 22-bit
+ * rounding shift -- from its documented arithmetic; no OpenCV build was available to record an image from, and cv2's SIMD paths may round differently, so
+ * equality with a particular cv2 build is not verified.  The un-letterbox of kasf_detect_boxes keeps the reference's own fp32 offsets, which differ from
+ * rule 1's truncated integers by under a pixel, exactly as in the reference.
+ * kasf_letterbox_plan: error 2 on Wf or Hf outside 1..32767, out_w or out_h outside 1..4096, a null pointer, or new_w < 1 or new_h < 1.
+ * kasf_letterbox_frames: n_frames = 0 does nothing.  Error 2, before a device or a device pointer is touched: n_frames < 0; Hf or Wf outside 1..32767; out_w or
+ * out_h outside 1..4096; row_stride < 3 * Wf; frame_stride < 0; frame_stride < Hf * row_stride with n_frames > 1; an unknown out_dtype; pad_value outside
+ * 0..255; a plan that fails; with n_frames > 0 a null frames or out. */
+#define KASF_LETTERBOX_MAX_SIDE 4096
+int kasf_letterbox_plan(int32_t Wf, int32_t Hf, int32_t out_w, int32_t out_h, int32_t* new_w, int32_t* new_h, int32_t* pad_x, int32_t* pad_y);
+int kasf_letterbox_frames(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, void* out, int32_t out_dtype,
+                          int32_t out_w, int32_t out_h, int32_t pad_value, int32_t swap_rb, void* stream);
 
 /* ---- person boxes -> tracked person boxes (ABI 12): the SORT tracker of demo/lib/sort/sort.py, one launch per tick, no host synchronisation ----
  * state: kasf_sort_state_bytes(streams, slots, max_dets) bytes on the device, 8-byte aligned; ALL ZERO IS AN EMPTY TRACKER, so creating and resetting it (or one

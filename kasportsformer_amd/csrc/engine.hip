@@ -1249,6 +1249,41 @@ int kasf_crop_persons(const void* frames, int32_t n_frames, int32_t Hf, int32_t 
     return 0;
 }
 
+// ---- video frames -> detector inputs (kasf.h, kasf_letterbox_plan / kasf_letterbox_frames) ----
+int kasf_letterbox_plan(int32_t Wf, int32_t Hf, int32_t out_w, int32_t out_h, int32_t* new_w, int32_t* new_h, int32_t* pad_x, int32_t* pad_y) {
+    if (Hf < 1 || Hf > 32767 || Wf < 1 || Wf > 32767) return kasf_set_error(2, "letterbox: Hf and Wf must be in [1, 32767]");
+    if (out_w < 1 || out_h < 1 || out_w > KASF_LETTERBOX_MAX_SIDE || out_h > KASF_LETTERBOX_MAX_SIDE)
+        return kasf_set_error(2, "letterbox: out_w and out_h must be in [1, 4096] (KASF_LETTERBOX_MAX_SIDE: one table entry per output column in LDS)");
+    if (!new_w || !new_h || !pad_x || !pad_y) return kasf_set_error(2, "null pointer argument");
+    // rule 1: the reference's int(img_w * min(w / img_w, h / img_h)) in the same IEEE doubles
+    const double rw = (double)out_w / (double)Wf, rh = (double)out_h / (double)Hf;
+    const double r = rh < rw ? rh : rw;
+    const int32_t nw = (int32_t)((double)Wf * r), nh = (int32_t)((double)Hf * r);
+    if (nw < 1 || nh < 1) return kasf_set_error(2, "letterbox: the frame is so elongated that the resized image has no pixels (new_w or new_h < 1)");
+    *new_w = nw; *new_h = nh;
+    *pad_x = (out_w - nw) / 2; *pad_y = (out_h - nh) / 2;
+    return 0;
+}
+
+int kasf_letterbox_frames(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, void* out, int32_t out_dtype,
+                          int32_t out_w, int32_t out_h, int32_t pad_value, int32_t swap_rb, void* stream) {
+    if (n_frames < 0) return kasf_set_error(2, "letterbox_frames: n_frames must be >= 0");
+    int32_t new_w, new_h, pad_x, pad_y;
+    if (kasf_letterbox_plan(Wf, Hf, out_w, out_h, &new_w, &new_h, &pad_x, &pad_y)) return 2;
+    if (row_stride < (int64_t)3 * Wf) return kasf_set_error(2, "letterbox_frames: the row stride must be at least 3 * Wf bytes");
+    if (frame_stride < 0) return kasf_set_error(2, "letterbox_frames: the frame stride must be >= 0");
+    if (n_frames > 1 && frame_stride / Hf < row_stride)     // frame_stride < Hf * row_stride, without the product that a huge row_stride overflows
+        return kasf_set_error(2, "letterbox_frames: the frame stride must be at least Hf * row_stride with more than one frame");
+    if (out_dtype != KASF_F32 && out_dtype != KASF_F16 && out_dtype != KASF_BF16) return kasf_set_error(2, "letterbox_frames: out_dtype must be KASF_DTYPE_F32, _F16 or _BF16");
+    if (pad_value < 0 || pad_value > 255) return kasf_set_error(2, "letterbox_frames: pad_value must be in [0, 255]");
+    if (n_frames == 0) return 0;
+    if (!frames || !out) return kasf_set_error(2, "null pointer argument");
+    kasf_launch_letterbox((hipStream_t)stream, frames, n_frames, Hf, Wf, row_stride, frame_stride, out, out_dtype, out_w, out_h, new_w, new_h, pad_x, pad_y,
+                          pad_value, swap_rb ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // ---- detector output -> person boxes (kasf.h, kasf_detect_boxes) ----
 static const char* detect_shape_error(int32_t batch, int64_t n_per_image, int32_t max_candidates) {
     if (batch < 0 || batch > 65535) return "detect: batch must be in [0, 65535]";

@@ -216,6 +216,11 @@ void kasf_launch_crop_persons(hipStream_t s, const void* frames, int n_frames, i
                               const int* frame_index, const float* geom, int geom_kind, double aspect, int64_t n, void* out, int out_dtype, int out_w,
                               int out_h, const float* mean_std, int swap_rb, float* center_scale_out);
 
+// ---- k_letterbox.hip: video frames -> detector inputs (kasf.h, kasf_letterbox_frames): frames as k_crop.hip takes them, out [n_frames,3,out_h,out_w] of out_dtype;
+// new_w, new_h, pad_x, pad_y = kasf_letterbox_plan's (rule 1).  Arguments as checked by the entry point: 1 <= new_w <= out_w <= 4096, the same for the height ----
+void kasf_launch_letterbox(hipStream_t s, const void* frames, int n_frames, int Hf, int Wf, int64_t row_stride, int64_t frame_stride, void* out, int out_dtype,
+                           int out_w, int out_h, int new_w, int new_h, int pad_x, int pad_y, int pad_value, int swap_rb);
+
 // ---- k_detect.hip: YOLOv3 detector output -> person boxes (kasf.h, kasf_detect_boxes): a selection launch (every candidate's key slot, the box and score slots of the
 // passing ones) and one sort + NMS + output workgroup per image.  Arguments as checked by the entry point; returns nullptr or a message when the launch cannot be made ----
 #define KASF_DETECT_FORM_PREDICTION 0
