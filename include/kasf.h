@@ -41,6 +41,9 @@
  *   kasf_letterbox_plan, kasf_letterbox_frames <- prep_image: letterbox_image (cv2.resize INTER_CUBIC onto a canvas of 128), the [:, :, ::-1] channel reversal,
  *                             transpose and float().div(255.0): what the demo does on the host between a video frame and the YOLOv3 network's input
  *                             demo/lib/yolov3/preprocess.py:9-38, demo/lib/yolov3/human_detector.py:131
+ *   kasf_yuv420_to_bgr     <- cap.read(): the YUV 4:2:0 -> BGR conversion behind cv2.VideoCapture, which the demo leaves to the host; here from the decoder's
+ *                             NV12 / I420 surface in device memory to the uint8 BGR frame the two entries above take
+ *                             demo/lib/hrnet/gen_kpts.py:106,118
  *   kasf_sort_update       <- Sort.update (KalmanBoxTracker, associate_detections_to_trackers, iou) and, from gen_video_kpts, the empty-frame hold and the
  *                             num_person oldest tracks: what the demo does on the host between the person boxes and the crops
  *                             demo/lib/sort/sort.py:15-222, demo/lib/hrnet/gen_kpts.py:111-148
@@ -442,6 +445,55 @@ int kasf_crop_persons(const void* frames, int32_t n_frames, int32_t Hf, int32_t 
 int kasf_letterbox_plan(int32_t Wf, int32_t Hf, int32_t out_w, int32_t out_h, int32_t* new_w, int32_t* new_h, int32_t* pad_x, int32_t* pad_y);
 int kasf_letterbox_frames(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, void* out, int32_t out_dtype,
                           int32_t out_w, int32_t out_h, int32_t pad_value, int32_t swap_rb, void* stream);
+
+/* ---- decoder surfaces -> BGR frames (ADDED under ABI 12: additive, kasf_version() stays 12; a caller checks for the symbol by name).
+ * Replaces, on the device, the YUV 4:2:0 -> BGR conversion that stands behind the demo's cap.read() (demo/lib/hrnet/gen_kpts.py:106,118): a hardware decoder
+ * (VCN through rocDecode or VA-API) leaves NV12 surfaces in device memory, a software decoder (FFmpeg yuv420p) planar I420.  The result is the uint8
+ * [Hf][Wf][3] frame that kasf_letterbox_frames and kasf_crop_persons read.  One launch on `stream`; the library allocates nothing; the planes are only read.
+ * RULES.
+ *  1 layouts     8-bit 4:2:0: a luma plane of Hf rows of Wf samples and chroma planes of ch = (Hf + 1) / 2 rows of cw = (Wf + 1) / 2 samples.  Odd Wf / Hf are
+ *                legal: the last column / row shares the last chroma sample.  Luma sample (f, y, x) is the byte at y + f * y_frame_stride + y * y_row_stride + x.
+ *                KASF_YUV_NV12: c0 is ONE interleaved plane, chroma sample (cy, cx) is the byte pair U, V at c0 + f * c_frame_stride + cy * c_row_stride + 2 * cx;
+ *                c1 must be NULL.  KASF_YUV_I420: c0 is the U plane and c1 the V plane, one byte per sample at + f * c_frame_stride + cy * c_row_stride + cx
+ *                (both planes share the two strides).  Strides are in bytes; no alignment is asked of any pointer or stride.
+ *  2 siting      nearest: pixel (y, x) takes chroma sample (y >> 1, x >> 1), as cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420) does.  Interpolated chroma
+ *                (bilinear upsampling, co-sited or centred) is out of scope.
+ *  3 arithmetic  integers only, 20 fractional bits.  y1 = max(0, Y - 16) * CY with full_range == 0, Y * CY otherwise; u = U - 128, v = V - 128;
+ *                  R = sat8((y1 + CVR * v + (1 << 19)) >> 20)
+ *                  G = sat8((y1 + CVG * v + CUG * u + (1 << 19)) >> 20)
+ *                  B = sat8((y1 + CUB * u + (1 << 19)) >> 20)
+ *                the shift is arithmetic and sat8 clamps to 0..255.  Every intermediate fits int32: y1 <= 255 * 1220945 < 3.12e8, |u|, |v| <= 128 and the largest
+ *                chroma term is 128 * 2215014 < 2.84e8 (G: 128 * (852492 + 409993) < 1.62e8), so |sum| < 3.12e8 + 2.84e8 + 2^19 < 5.97e8 < 2^31; integer sums are
+ *                exact, so any grouping of the terms gives the same bits.
+ *  4 tables      { CY, CVR, CVG, CUG, CUB } per (matrix, range), the literals below.  KASF_YUV_BT601 limited is OpenCV's five published constants =
+ *                rint(c * 2^20) of 1.164, 1.596, 0.813, 0.391, 2.018.  The other three are rint(c * 2^20) of the exact doubles from Kr, Kb (0.299 / 0.114 for
+ *                BT.601, 0.2126 / 0.0722 for BT.709), Kg = 1 - Kr - Kb, the luma scale ls (255 / 219 limited, 1 full) and the chroma scale cs (255 / 224
+ *                limited, 1 full): CY = ls, CVR = 2 (1 - Kr) cs, CVG = -2 (1 - Kr) Kr / Kg cs, CUG = -2 (1 - Kb) Kb / Kg cs, CUB = 2 (1 - Kb) cs.
+ *  5 output      out[f][y][x][0..2] = B, G, R, or R, G, B with rgb != 0, uint8, at out + f * out_frame_stride + y * out_row_stride + 3 * x.  out_row_stride >=
+ *                3 * Wf: a caller's pitched buffer is written in place.  Every byte of the 3 * Wf payload of every row is written; no byte of the row padding is.
+ *  6 determinism no atomics, no scratch, no LDS: a pixel is a function of its three samples alone; the same bits from run to run and for a frame alone or in a batch.
+ * ACCURACY of rules 3-4 against the exact fp64 conversion (the same Kr, Kb and scales, the same max(0, Y - 16), clamped to [0, 255]), over all 2^24 (Y, U, V): at
+ * most 0.5 + sum |c_int / 2^20 - c_exact| * max|operand| grey levels per channel (operands: 239 or 255 for luma, 128 for chroma) = about 0.8 for BT.601
+ * limited, whose constants are three-decimal roundings, and under 0.5003 for the derived tables (tests/test_yuv_cpu.py).
+ * NOT VERIFIED: rules 2 and 3 restate the fixed-point scheme of OpenCV's portable cvtColor for 4:2:0 input from its documented arithmetic; what
+ * cv2.VideoCapture.read() returns additionally depends on the FFmpeg build behind it.  No OpenCV build was available to record a frame from, so equality
+ * with a particular cv2 / FFmpeg build is not verified.
+ * n_frames = 0 does nothing.  Error 2, before a device or a device pointer is touched: n_frames < 0; Hf or Wf outside 1..32767; y_row_stride < Wf;
+ * c_row_stride < 2 * cw (NV12) or < cw (I420); out_row_stride < 3 * Wf; a negative frame stride; with n_frames > 1 y_frame_stride < Hf * y_row_stride,
+ * c_frame_stride < ch * c_row_stride or out_frame_stride < Hf * out_row_stride; an unknown layout or matrix; a non-null c1 with NV12 or a null c1 with
+ * I420; with n_frames > 0 a null y, c0 or out. */
+#define KASF_YUV_NV12 0
+#define KASF_YUV_I420 1
+#define KASF_YUV_BT601 0
+#define KASF_YUV_BT709 1
+#define KASF_YUV_COEF_BT601_LIMITED { 1220542, 1673527, -852492, -409993, 2116026 }
+#define KASF_YUV_COEF_BT601_FULL    { 1048576, 1470104, -748826, -360853, 1858077 }
+#define KASF_YUV_COEF_BT709_LIMITED { 1220945, 1879825, -558796, -223607, 2215014 }
+#define KASF_YUV_COEF_BT709_FULL    { 1048576, 1651297, -490864, -196424, 1945738 }
+int kasf_yuv420_to_bgr(const void* y, const void* c0, const void* c1, int32_t layout, int32_t n_frames, int32_t Hf, int32_t Wf,
+                       int64_t y_row_stride, int64_t c_row_stride, int64_t y_frame_stride, int64_t c_frame_stride,
+                       void* out, int64_t out_row_stride, int64_t out_frame_stride,
+                       int32_t matrix, int32_t full_range, int32_t rgb, void* stream);
 
 /* ---- person boxes -> tracked person boxes (ABI 12): the SORT tracker of demo/lib/sort/sort.py, one launch per tick, no host synchronisation ----
  * state: kasf_sort_state_bytes(streams, slots, max_dets) bytes on the device, 8-byte aligned; ALL ZERO IS AN EMPTY TRACKER, so creating and resetting it (or one

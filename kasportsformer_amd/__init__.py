@@ -26,6 +26,9 @@ Public surface mirrors the reference's interface for this path:
   letterbox_frames, LetterboxResult     demo/lib/yolov3/preprocess.py:9-38, demo/lib/yolov3/human_detector.py:131 (video frames -> the YOLOv3 network's input, on the
                                         device: letterbox with bicubic resampling onto a canvas of 128, channel reversal, planes, / 255; one launch,
                                         reads the decoder's frame in place; its width / height are what `yolo_heads_to_boxes` takes)
+  yuv_to_bgr, nv12_to_bgr, i420_to_bgr  demo/lib/hrnet/gen_kpts.py:106,118 (`cap.read()`'s colour conversion: a decoder's NV12 / I420 surface -> the uint8 BGR frame, on the
+                                        device: nearest chroma, 20-bit fixed point, BT.601 / BT.709, limited / full range; one launch, reads the surface in
+                                        place through its pitch; what `letterbox_frames` and `crop_persons` take)
   detections_to_boxes,                  demo/lib/yolov3/human_detector.py:116-168, demo/lib/yolov3/util.py:34-81,107-225, demo/lib/yolov3/bbox.py:51-78 (a YOLOv3
   yolo_heads_to_boxes, YOLOV3_ANCHORS   person detector's output -> person boxes in frame pixels, on the device: threshold, persons only, sort, greedy NMS,
                                         un-letterbox; what `heatmaps_to_keypoints(boxes=...)` takes)
@@ -59,6 +62,7 @@ from .heatmap import heatmaps_to_keypoints
 from .detect import detections_to_boxes, yolo_heads_to_boxes, DetectResult, YOLOV3_ANCHORS, YOLOV3_MASKS
 from .crop import crop_persons, CropResult
 from .letterbox import letterbox_frames, LetterboxResult
+from .yuv import yuv_to_bgr, nv12_to_bgr, i420_to_bgr
 from .track import SortTracker, TrackResult, TrackState
 from .tracked import TrackedLifter, TrackedTick
 
@@ -67,5 +71,5 @@ __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_strea
            "checkpoint_save", "checkpoint_load", "strip_module_prefix", "adamw_state_dict", "load_adamw_state_dict", "warmup_lr", "apply_warmup", "ReduceLROnPlateau", "train_one_epoch",
            "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample",
            "lift_track", "lift_tracks", "window_plan", "StreamLifter", "coco_to_h36m", "poses_to_world", "DEMO_CAMERA_ROTATION", "heatmaps_to_keypoints",
-           "detections_to_boxes", "yolo_heads_to_boxes", "DetectResult", "YOLOV3_ANCHORS", "YOLOV3_MASKS", "crop_persons", "CropResult", "letterbox_frames", "LetterboxResult", "SortTracker", "TrackResult", "TrackState",
+           "detections_to_boxes", "yolo_heads_to_boxes", "DetectResult", "YOLOV3_ANCHORS", "YOLOV3_MASKS", "crop_persons", "CropResult", "letterbox_frames", "LetterboxResult", "yuv_to_bgr", "nv12_to_bgr", "i420_to_bgr", "SortTracker", "TrackResult", "TrackState",
            "TrackedLifter", "TrackedTick"]

@@ -1284,6 +1284,34 @@ int kasf_letterbox_frames(const void* frames, int32_t n_frames, int32_t Hf, int3
     return 0;
 }
 
+// ---- decoder surfaces -> BGR frames (kasf.h, kasf_yuv420_to_bgr) ----
+int kasf_yuv420_to_bgr(const void* y, const void* c0, const void* c1, int32_t layout, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t y_row_stride,
+                       int64_t c_row_stride, int64_t y_frame_stride, int64_t c_frame_stride, void* out, int64_t out_row_stride, int64_t out_frame_stride,
+                       int32_t matrix, int32_t full_range, int32_t rgb, void* stream) {
+    static const int kCoef[2][2][5] = {{KASF_YUV_COEF_BT601_LIMITED, KASF_YUV_COEF_BT601_FULL}, {KASF_YUV_COEF_BT709_LIMITED, KASF_YUV_COEF_BT709_FULL}};
+    if (n_frames < 0) return kasf_set_error(2, "yuv420_to_bgr: n_frames must be >= 0");
+    if (Hf < 1 || Hf > 32767 || Wf < 1 || Wf > 32767) return kasf_set_error(2, "yuv420_to_bgr: Hf and Wf must be in [1, 32767]");
+    if (layout != KASF_YUV_NV12 && layout != KASF_YUV_I420) return kasf_set_error(2, "yuv420_to_bgr: layout must be KASF_YUV_NV12 or KASF_YUV_I420");
+    if (matrix != KASF_YUV_BT601 && matrix != KASF_YUV_BT709) return kasf_set_error(2, "yuv420_to_bgr: matrix must be KASF_YUV_BT601 or KASF_YUV_BT709");
+    const bool nv12 = layout == KASF_YUV_NV12;
+    const int64_t cw = (Wf + 1) / 2, ch = (Hf + 1) / 2;
+    if (y_row_stride < Wf) return kasf_set_error(2, "yuv420_to_bgr: the luma row stride must be at least Wf bytes");
+    if (c_row_stride < (nv12 ? 2 * cw : cw))
+        return kasf_set_error(2, "yuv420_to_bgr: the chroma row stride must be at least 2 * ((Wf + 1) / 2) bytes for NV12, (Wf + 1) / 2 for I420");
+    if (out_row_stride < (int64_t)3 * Wf) return kasf_set_error(2, "yuv420_to_bgr: the output row stride must be at least 3 * Wf bytes");
+    if (y_frame_stride < 0 || c_frame_stride < 0 || out_frame_stride < 0) return kasf_set_error(2, "yuv420_to_bgr: the frame strides must be >= 0");
+    // frame_stride < rows * row_stride, without the product that a huge row stride overflows
+    if (n_frames > 1 && (y_frame_stride / Hf < y_row_stride || c_frame_stride / ch < c_row_stride || out_frame_stride / Hf < out_row_stride))
+        return kasf_set_error(2, "yuv420_to_bgr: with more than one frame every frame stride must cover its plane (rows * row stride)");
+    if (nv12 ? c1 != nullptr : c1 == nullptr) return kasf_set_error(2, "yuv420_to_bgr: c1 is the V plane of I420 and must be NULL for NV12");
+    if (n_frames == 0) return 0;
+    if (!y || !c0 || !out) return kasf_set_error(2, "null pointer argument");
+    kasf_launch_yuv420_to_bgr((hipStream_t)stream, y, c0, c1, nv12 ? 1 : 0, n_frames, Hf, Wf, y_row_stride, c_row_stride, y_frame_stride, c_frame_stride, out,
+                              out_row_stride, out_frame_stride, kCoef[matrix][full_range ? 1 : 0], full_range ? 1 : 0, rgb ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // ---- detector output -> person boxes (kasf.h, kasf_detect_boxes) ----
 static const char* detect_shape_error(int32_t batch, int64_t n_per_image, int32_t max_candidates) {
     if (batch < 0 || batch > 65535) return "detect: batch must be in [0, 65535]";

@@ -221,6 +221,12 @@ void kasf_launch_crop_persons(hipStream_t s, const void* frames, int n_frames, i
 void kasf_launch_letterbox(hipStream_t s, const void* frames, int n_frames, int Hf, int Wf, int64_t row_stride, int64_t frame_stride, void* out, int out_dtype,
                            int out_w, int out_h, int new_w, int new_h, int pad_x, int pad_y, int pad_value, int swap_rb);
 
+// ---- k_yuv.hip: decoder surfaces -> BGR frames (kasf.h, kasf_yuv420_to_bgr): nv12 != 0: c0 is the interleaved UV plane and c1 unused, else c0 / c1 are the U / V
+// planes; coef = rule 4's { CY, CVR, CVG, CUG, CUB }.  Arguments as checked by the entry point: every stride covers its plane's row, Hf, Wf in 1..32767 ----
+void kasf_launch_yuv420_to_bgr(hipStream_t s, const void* y, const void* c0, const void* c1, int nv12, int n_frames, int Hf, int Wf, int64_t y_row_stride,
+                               int64_t c_row_stride, int64_t y_frame_stride, int64_t c_frame_stride, void* out, int64_t out_row_stride, int64_t out_frame_stride,
+                               const int coef[5], int full_range, int rgb);
+
 // ---- k_detect.hip: YOLOv3 detector output -> person boxes (kasf.h, kasf_detect_boxes): a selection launch (every candidate's key slot, the box and score slots of the
 // passing ones) and one sort + NMS + output workgroup per image.  Arguments as checked by the entry point; returns nullptr or a message when the launch cannot be made ----
 #define KASF_DETECT_FORM_PREDICTION 0
