@@ -44,6 +44,9 @@
  *   kasf_yuv420_to_bgr     <- cap.read(): the YUV 4:2:0 -> BGR conversion behind cv2.VideoCapture, which the demo leaves to the host; here from the decoder's
  *                             NV12 / I420 surface in device memory to the uint8 BGR frame the two entries above take
  *                             demo/lib/hrnet/gen_kpts.py:106,118
+ *   kasf_draw_poses, kasf_bgr_to_nv12, kasf_pose_panel <- plot_on_frame's lines and dots, the score threshold of plot_keypoint / write, the 3-D plot's projection
+ *                             and the frame cv2.VideoWriter takes; here painted on the device frame and written as the encoder's NV12 surface (exact geometry,
+ *                             not cv2's rasteriser)   demo/demo.py:91-105,159-191,307-323, demo/lib/hrnet/lib/utils/utilitys.py:24-58
  *   kasf_sort_update       <- Sort.update (KalmanBoxTracker, associate_detections_to_trackers, iou) and, from gen_video_kpts, the empty-frame hold and the
  *                             num_person oldest tracks: what the demo does on the host between the person boxes and the crops
  *                             demo/lib/sort/sort.py:15-222, demo/lib/hrnet/gen_kpts.py:111-148
@@ -494,6 +497,87 @@ int kasf_yuv420_to_bgr(const void* y, const void* c0, const void* c1, int32_t la
                        int64_t y_row_stride, int64_t c_row_stride, int64_t y_frame_stride, int64_t c_frame_stride,
                        void* out, int64_t out_row_stride, int64_t out_frame_stride,
                        int32_t matrix, int32_t full_range, int32_t rgb, void* stream);
+
+/* ---- skeletons over the frame, and the encoder's NV12 surface (ADDED under ABI 12: additive, kasf_version() stays 12; a caller checks for the symbols by name).
+ * Replaces, on the device, the demo's plot_on_frame (demo/demo.py:91-105: cv2.line and cv2.circle per bone on a copy of the frame), the score threshold of
+ * plot_keypoint / write (demo/lib/hrnet/lib/utils/utilitys.py:24-58) and the host frame that cv2.VideoWriter takes (demo/demo.py:307-323).  kasf_draw_poses
+ * paints the tracked skeletons and filled rectangles over the uint8 frame and writes the painted frame, its NV12 surface, or both, as ONE launch on `stream`;
+ * kasf_bgr_to_nv12 is the same launch with nothing to paint: the inverse of kasf_yuv420_to_bgr.  The library allocates nothing; the inputs are only read.
+ *   frames    uint8 [n_frames][Hf][Wf][3] = B, G, R (R, G, B with rgb != 0): pixel (f, y, x) at frames + f * frame_stride + y * row_stride + 3 * x (bytes),
+ *             what kasf_yuv420_to_bgr writes and kasf_crop_persons reads.
+ *   keypoints fp32 [n_frames][P][J][C], C = 2 (x, y) or 3 (x, y, score) in frame pixels: element (f, p, j, c) at keypoints + f * kp_frame_stride +
+ *             p * kp_person_stride + j * kp_joint_stride + c * kp_coord_stride (ELEMENTS).  1 <= J <= 32.  valid uint8 [n_frames][P] behind two byte strides,
+ *             or NULL for every row.
+ *   segments  int32 [S][2] joint pairs, colors uint8 [S][3] in the frame's channel order (device memory), 0 <= S <= 32; a pair that names a joint outside
+ *             0..J-1 makes that joint not visible.  dot_color[3]: HOST memory, read before the call returns.  thickness t in 1..64, dot_radius r in 0..32.
+ *   fills     int32 [R][7] = x0, y0, x1, y1, c0, c1, c2 (device memory, the same for every frame), R <= 8: the half-open rectangle [x0, x1) x [y0, y1) clipped
+ *             to the frame, painted with the low 8 bits of c0, c1, c2.
+ *   out_bgr   as frames, behind its own strides; it may be exactly `frames` with the same strides (in place) or disjoint from it -- any other overlap is the
+ *             caller's error and is not detected.  out_y / out_uv: an NV12 surface, luma (f, y, x) at out_y + f * y_frame_stride + y * y_row_stride + x, the
+ *             pair U, V of chroma sample (cy, cx) at out_uv + f * uv_frame_stride + cy * uv_row_stride + 2 * cx.  out_bgr may be NULL, or out_y and out_uv
+ *             both, not all three.  Strides are in bytes; no alignment is asked of any pointer or stride.
+ * RULES.  All geometry is in integers and exact.
+ *  1 joints      xi = trunc(x), yi = trunc(y), toward zero (Python's int() in plot_on_frame: int(-0.5) = 0).  Joint (f, p, j) is VISIBLE iff x and y are finite,
+ *                -32768 <= xi, yi <= 65535, valid is NULL or valid[f][p] != 0, and -- with C = 3 and a finite min_score -- score > min_score (a NaN score is not
+ *                visible; a NaN or infinite min_score switches the test off).  Pixels are 0 <= px, py <= 32766.  So with d = B - A and w = pixel - A every
+ *                component has |.| <= 98303 < 2^17, and L2 = d . d, s = w . d, w . w and c = w x d are below 2^35 in magnitude.
+ *  2 order       painting is opaque: fills 0..R-1, then persons p = 0..P-1 and within a person for s = 0..S-1 line s, the dot at its first joint, the dot at
+ *                its second joint (plot_on_frame's loop).  A line is drawn iff both its joints are visible, a dot iff its joint is.  The output pixel is the
+ *                colour of the LAST primitive in this order that covers it, else the input pixel.
+ *  3 coverage    a dot at A covers (px, py) iff wx^2 + wy^2 <= r^2 (r = 0: the one pixel).  Line A -> B covers it iff the squared distance from the pixel to
+ *                the closed segment is <= (t / 2)^2: if L2 = 0 or s <= 0, iff 4 (w . w) <= t^2; if s >= L2, the same with u = w - d; otherwise iff
+ *                4 c^2 <= t^2 L2.  4 (w . w) < 2^38 and t^2 L2 <= 2^12 * 2^35 = 2^47 fit int64; 4 c^2 alone could reach 2^72, but |d| <= |dx| + |dy|, so
+ *                2 |c| > t (|dx| + |dy|) implies 4 c^2 > t^2 L2: not covered, decided with operands below 2^37; otherwise 2 |c| <= 64 * 196606 < 2^24 and
+ *                4 c^2 < 2^48.  Every intermediate fits int64.
+ *  4 NOT cv2     this is exact Euclidean geometry.  It is NOT a restatement of OpenCV's polygon-fill ThickLine or of its midpoint circle, whose pixels differ
+ *                at the rim; NOT VERIFIED against any cv2 build, and no equality with cv2.line / cv2.circle is claimed.  Anti-aliasing, alpha, text: out of scope.
+ *  5 surface     from the PAINTED pixels.  Y = sat8((CRY R + CGY G + CBY B + (yoff << 20) + (1 << 19)) >> 20), yoff = 16 (limited) or 0 (full).  One chroma
+ *                sample per 2 x 2 quad from the sums S_R, S_G, S_B of its four painted pixels -- at an odd right / bottom edge the last column / row is
+ *                replicated, so there are always four --: U = sat8((CRU S_R + CGU S_G + CH S_B + (128 << 22) + (1 << 21)) >> 22),
+ *                V = sat8((CH S_R + CGV S_G + CBV S_B + (128 << 22) + (1 << 21)) >> 22); shifts are arithmetic.  The literals below are
+ *                { CRY, CGY, CBY, CRU, CGU, CH, CGV, CBV } = rint(c * 2^20) of the exact doubles from Kr, Kb (0.299 / 0.114, 0.2126 / 0.0722), Kg = 1 - Kr - Kb,
+ *                ls = 219 / 255 and cs = 224 / 255 (limited) or 1 (full): Kr ls, Kg ls, Kb ls, -Kr cs / (2 (1 - Kb)), -Kg cs / (2 (1 - Kb)), cs / 2 (= CBU = CRV:
+ *                eight distinct coefficients), -Kg cs / (2 (1 - Kr)), -Kb cs / (2 (1 - Kr)) -- the same four (matrix, range) pairs as KASF_YUV_COEF_*.
+ *                int32: luma <= 255 * 2^20 + 2^24 + 2^19 < 2.9e8; chroma sums are <= 1020 and |CRU| + |CGU| = |CGV| + |CBV| = CH <= 524288, so each sum lies
+ *                in [-5.35e8, 5.35e8] + 5.37e8 + 2^21, inside (-2^31, 2^31).
+ *  6 determinism no atomics and no scratch; a pixel is a function of the frame's primitives and its own quad: the same bits from run to run, for a frame alone
+ *                or in a batch, whatever the tiling.  Every byte of the 3 * Wf payload of out_bgr's rows is written (in place, a byte that no primitive covers
+ *                keeps its value), every byte of the Wf luma payload and of the 2 * ((Wf + 1) / 2) chroma payload of the surface's rows; no padding byte is.
+ * ACCURACY of rule 5 against the exact fp64 conversion of the pixel (luma) or of the quad's mean (chroma), clamped to [0, 255]: at most
+ * 0.5 + sum |c_int / 2^20 - c| * 255 grey levels per channel, under 0.5004 for every table (tests/test_draw_cpu.py).  NOT VERIFIED: what a particular encoder
+ * makes of the surface (its matrix and range flags, its chroma siting) is the caller's to set; no equality with an encoder's or cv2's colour handling is claimed.
+ * n_frames = 0 does nothing.  Error 2, before a device or a device pointer is touched: n_frames < 0; Hf or Wf outside 1..32767; row_stride or out_row_stride
+ * < 3 * Wf; y_row_stride < Wf; uv_row_stride < 2 * ((Wf + 1) / 2); a negative frame stride; with n_frames > 1 a frame stride that does not cover its plane
+ * (rows * row stride); all outputs NULL, or one of out_y / out_uv without the other; P < 0 or > 2^20; S outside 0..32; with P > 0 and S > 0: J outside 1..32,
+ * C not 2 or 3, a null keypoints, segments or colors; a null dot_color; thickness outside 1..64; dot_radius outside 0..32; R outside 0..8 or R > 0 with a null
+ * fills; an unknown matrix; with n_frames > 0 a null frames. */
+#define KASF_RGB2YUV_COEF_BT601_LIMITED { 269262, 528618, 102662, -155423, -305128, 460551, -385654, -74897 }
+#define KASF_RGB2YUV_COEF_BT601_FULL    { 313524, 615514, 119538, -176932, -347356, 524288, -439026, -85262 }
+#define KASF_RGB2YUV_COEF_BT709_LIMITED { 191455, 644067, 65019, -105533, -355018, 460551, -418321, -42230 }
+#define KASF_RGB2YUV_COEF_BT709_FULL    { 222927, 749942, 75707, -120138, -404150, 524288, -476214, -48074 }
+int kasf_draw_poses(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride,
+                    const float* keypoints, int32_t P, int32_t J, int32_t C,
+                    int64_t kp_frame_stride, int64_t kp_person_stride, int64_t kp_joint_stride, int64_t kp_coord_stride,
+                    const uint8_t* valid, int64_t valid_frame_stride, int64_t valid_person_stride,
+                    const int32_t* segments, const uint8_t* colors, int32_t S, const uint8_t* dot_color,
+                    int32_t thickness, int32_t dot_radius, float min_score, const int32_t* fills, int32_t R,
+                    void* out_bgr, int64_t out_row_stride, int64_t out_frame_stride,
+                    void* out_y, void* out_uv, int64_t y_row_stride, int64_t uv_row_stride, int64_t y_frame_stride, int64_t uv_frame_stride,
+                    int32_t matrix, int32_t full_range, int32_t rgb, void* stream);
+int kasf_bgr_to_nv12(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride,
+                     void* out_y, void* out_uv, int64_t y_row_stride, int64_t uv_row_stride, int64_t y_frame_stride, int64_t uv_frame_stride,
+                     int32_t matrix, int32_t full_range, int32_t rgb, void* stream);
+
+/* kasf_pose_panel: the 3-D plot beside the frame (demo/demo.py:159-191), as the projection that puts world-space poses into a panel rectangle for
+ * kasf_draw_poses to draw after a background fill.  poses [n][17][3] fp32 (kasf_pose_world's output) -> out [n][17][2] fp32 pixel coordinates; one launch.
+ * view = eight HOST floats { ax0, ax1, ax2, ay0, ay1, ay2, cx, cy }, read before the call returns.  For the orthographic view of view_init(elev, azim) into the
+ * panel [x0, x1) x [y0, y1) the caller forms them in fp64 and rounds once: right = (-sin az, cos az, 0), up = (-sin el cos az, -sin el sin az, cos el),
+ * scale = min(x1 - x0, y1 - y0) / 2 / radius (the demo's RADIUS is 0.72), ax = scale * right, ay = -scale * up (image rows grow downwards),
+ * cx = (x0 + x1) / 2, cy = (y0 + y1) / 2.  Per joint, in single fp32 operations in this order, none contracted: d = v - root (joint 0 of the same pose);
+ * out_x = (((ax0 * dx) + (ax1 * dy)) + (ax2 * dz)) + cx, out_y likewise with ay and cy.  matplotlib's perspective camera, its axes, ticks and panes are out of
+ * scope.  n = 0 does nothing.  Error 2, before a device or a device pointer is touched: n < 0 or n > 2^40; a null view or a view that is not finite; with
+ * n > 0 a null poses or out. */
+int kasf_pose_panel(const float* poses, int64_t n, const float* view, float* out, void* stream);
 
 /* ---- person boxes -> tracked person boxes (ABI 12): the SORT tracker of demo/lib/sort/sort.py, one launch per tick, no host synchronisation ----
  * state: kasf_sort_state_bytes(streams, slots, max_dets) bytes on the device, 8-byte aligned; ALL ZERO IS AN EMPTY TRACKER, so creating and resetting it (or one

@@ -42,6 +42,9 @@ Public surface mirrors the reference's interface for this path:
                                         `SortTracker`'s ids and slots drive `StreamLifter`-style per-player histories on the device, births and deaths
                                         included; no read-back of the tracker's output, two launches and one forward per tick
   poses_to_world, DEMO_CAMERA_ROTATION  demo/lib/utils.py:55-73, demo/demo.py:242-248 (camera space -> world space, floor, unit scale; `--world`)
+  draw_poses, bgr_to_nv12,              demo/demo.py:91-105,159-191,307-323, demo/lib/hrnet/lib/utils/utilitys.py:24-58 (`plot_on_frame`'s lines and dots over the frame, the
+  poses_to_panel, DrawResult            score threshold, the 3-D plot's projection, and the frame as the NV12 surface an encoder takes, on the device: exact
+                                        integer geometry -- not cv2's rasteriser --, 20-bit fixed-point BGR -> YUV; one launch, also in place)
 """
 from .model import (KASportsFormer, load_model, set_single_stream, is_single_stream, set_deterministic, is_deterministic, set_fused_attention_backward,
                     is_fused_attention_backward)
@@ -63,6 +66,7 @@ from .detect import detections_to_boxes, yolo_heads_to_boxes, DetectResult, YOLO
 from .crop import crop_persons, CropResult
 from .letterbox import letterbox_frames, LetterboxResult
 from .yuv import yuv_to_bgr, nv12_to_bgr, i420_to_bgr
+from .draw import draw_poses, bgr_to_nv12, poses_to_panel, DrawResult
 from .track import SortTracker, TrackResult, TrackState
 from .tracked import TrackedLifter, TrackedTick
 
@@ -72,4 +76,4 @@ __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_strea
            "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample",
            "lift_track", "lift_tracks", "window_plan", "StreamLifter", "coco_to_h36m", "poses_to_world", "DEMO_CAMERA_ROTATION", "heatmaps_to_keypoints",
            "detections_to_boxes", "yolo_heads_to_boxes", "DetectResult", "YOLOV3_ANCHORS", "YOLOV3_MASKS", "crop_persons", "CropResult", "letterbox_frames", "LetterboxResult", "yuv_to_bgr", "nv12_to_bgr", "i420_to_bgr", "SortTracker", "TrackResult", "TrackState",
-           "TrackedLifter", "TrackedTick"]
+           "TrackedLifter", "TrackedTick", "draw_poses", "bgr_to_nv12", "poses_to_panel", "DrawResult"]

@@ -22,6 +22,8 @@ DETECT_MAX_CANDIDATES = 4096           # KASF_DETECT_MAX_CANDIDATES
 LETTERBOX_MAX_SIDE = 4096              # KASF_LETTERBOX_MAX_SIDE: out_w and out_h of kasf_letterbox_frames
 YUV_NV12, YUV_I420 = 0, 1                # KASF_YUV_*: layout of kasf_yuv420_to_bgr
 YUV_BT601, YUV_BT709 = 0, 1              # KASF_YUV_BT*: its matrix
+DRAW_MAX_JOINTS, DRAW_MAX_SEGMENTS, DRAW_MAX_FILLS = 32, 32, 8      # kasf_draw_poses: J, S, R
+DRAW_MAX_THICKNESS, DRAW_MAX_RADIUS = 64, 32
 SORT_MAX = 64                          # KASF_SORT_MAX: slots and max_dets of kasf_sort_update
 SORT_HEADER_BYTES = 64                 # KASF_SORT_HEADER_BYTES
 FLAG_TRAIN, FLAG_RETURN_REP, FLAG_KEEP = 1, 2, 4
@@ -98,6 +100,10 @@ SIGNATURES = {
     "kasf_letterbox_plan": (_i32, [_i32, _i32, _i32, _i32, _pi32, _pi32, _pi32, _pi32]),
     "kasf_letterbox_frames": (_i32, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "kasf_yuv420_to_bgr": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "kasf_draw_poses": (_i32, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _f32,
+                              _vp, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "kasf_bgr_to_nv12": (_i32, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "kasf_pose_panel": (_i32, [_vp, _i64, C.POINTER(_f32), _vp, _vp]),
     "kasf_detect_workspace_bytes": (_i64, [_i32, _i64, _i32]),
     "kasf_detect_boxes": (_i32, [_vp, _i32, _i32, _i32, _i32, _pi32, _i32, _i32, C.POINTER(_f32), _i32, _vp, _f32, _f32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
                                  _i64, _vp]),

@@ -1312,6 +1312,89 @@ int kasf_yuv420_to_bgr(const void* y, const void* c0, const void* c1, int32_t la
     return 0;
 }
 
+// ---- skeletons over the frame and the encoder's surface (kasf.h, kasf_draw_poses / kasf_bgr_to_nv12 / kasf_pose_panel) ----
+int kasf_draw_poses(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, const float* keypoints, int32_t P,
+                    int32_t J, int32_t C, int64_t kp_frame_stride, int64_t kp_person_stride, int64_t kp_joint_stride, int64_t kp_coord_stride,
+                    const uint8_t* valid, int64_t valid_frame_stride, int64_t valid_person_stride, const int32_t* segments, const uint8_t* colors, int32_t S,
+                    const uint8_t* dot_color, int32_t thickness, int32_t dot_radius, float min_score, const int32_t* fills, int32_t R, void* out_bgr,
+                    int64_t out_row_stride, int64_t out_frame_stride, void* out_y, void* out_uv, int64_t y_row_stride, int64_t uv_row_stride,
+                    int64_t y_frame_stride, int64_t uv_frame_stride, int32_t matrix, int32_t full_range, int32_t rgb, void* stream) {
+    static const int kCoef[2][2][8] = {{KASF_RGB2YUV_COEF_BT601_LIMITED, KASF_RGB2YUV_COEF_BT601_FULL}, {KASF_RGB2YUV_COEF_BT709_LIMITED, KASF_RGB2YUV_COEF_BT709_FULL}};
+    if (n_frames < 0) return kasf_set_error(2, "draw_poses: n_frames must be >= 0");
+    if (Hf < 1 || Hf > 32767 || Wf < 1 || Wf > 32767) return kasf_set_error(2, "draw_poses: Hf and Wf must be in [1, 32767]");
+    if (matrix != KASF_YUV_BT601 && matrix != KASF_YUV_BT709) return kasf_set_error(2, "draw_poses: matrix must be KASF_YUV_BT601 or KASF_YUV_BT709");
+    if (!out_bgr && !out_y && !out_uv) return kasf_set_error(2, "draw_poses: out_bgr, or out_y and out_uv, must be given");
+    if (!out_y != !out_uv) return kasf_set_error(2, "draw_poses: out_y and out_uv are one surface: both or neither");
+    const int64_t cw = (Wf + 1) / 2, ch = (Hf + 1) / 2;
+    if (row_stride < (int64_t)3 * Wf) return kasf_set_error(2, "draw_poses: the row stride must be at least 3 * Wf bytes");
+    if (frame_stride < 0) return kasf_set_error(2, "draw_poses: the frame strides must be >= 0");
+    // frame_stride < rows * row_stride, without the product that a huge row stride overflows
+    if (n_frames > 1 && frame_stride / Hf < row_stride) return kasf_set_error(2, "draw_poses: with more than one frame every frame stride must cover its plane (rows * row stride)");
+    if (out_bgr) {
+        if (out_row_stride < (int64_t)3 * Wf) return kasf_set_error(2, "draw_poses: the output row stride must be at least 3 * Wf bytes");
+        if (out_frame_stride < 0) return kasf_set_error(2, "draw_poses: the frame strides must be >= 0");
+        if (n_frames > 1 && out_frame_stride / Hf < out_row_stride)
+            return kasf_set_error(2, "draw_poses: with more than one frame every frame stride must cover its plane (rows * row stride)");
+    }
+    if (out_y) {
+        if (y_row_stride < Wf) return kasf_set_error(2, "draw_poses: the luma row stride must be at least Wf bytes");
+        if (uv_row_stride < 2 * cw) return kasf_set_error(2, "draw_poses: the chroma row stride must be at least 2 * ((Wf + 1) / 2) bytes");
+        if (y_frame_stride < 0 || uv_frame_stride < 0) return kasf_set_error(2, "draw_poses: the frame strides must be >= 0");
+        if (n_frames > 1 && (y_frame_stride / Hf < y_row_stride || uv_frame_stride / ch < uv_row_stride))
+            return kasf_set_error(2, "draw_poses: with more than one frame every frame stride must cover its plane (rows * row stride)");
+    }
+    if (P < 0 || P > (1 << 20)) return kasf_set_error(2, "draw_poses: P must be in [0, 2^20]");
+    if (S < 0 || S > 32) return kasf_set_error(2, "draw_poses: S must be in [0, 32]");
+    if (P > 0 && S > 0) {
+        if (J < 1 || J > 32) return kasf_set_error(2, "draw_poses: J must be in [1, 32]");
+        if (C != 2 && C != 3) return kasf_set_error(2, "draw_poses: C must be 2 (x, y) or 3 (x, y, score)");
+        if (!keypoints || !segments || !colors) return kasf_set_error(2, "null pointer argument");
+    }
+    if (!dot_color) return kasf_set_error(2, "null pointer argument");
+    if (thickness < 1 || thickness > 64) return kasf_set_error(2, "draw_poses: thickness must be in [1, 64]");
+    if (dot_radius < 0 || dot_radius > 32) return kasf_set_error(2, "draw_poses: dot_radius must be in [0, 32]");
+    if (R < 0 || R > 8) return kasf_set_error(2, "draw_poses: R must be in [0, 8]");
+    if (R > 0 && !fills) return kasf_set_error(2, "null pointer argument");
+    if (n_frames == 0) return 0;
+    if (!frames) return kasf_set_error(2, "null pointer argument");
+    KasfDrawLaunch d;
+    d.frames = frames; d.n_frames = n_frames; d.Hf = Hf; d.Wf = Wf; d.row_stride = row_stride; d.frame_stride = frame_stride;
+    d.keypoints = keypoints; d.P = P; d.J = J; d.use_score = (C == 3 && std::isfinite(min_score)) ? 1 : 0;
+    d.kp_frame_stride = kp_frame_stride; d.kp_person_stride = kp_person_stride; d.kp_joint_stride = kp_joint_stride; d.kp_coord_stride = kp_coord_stride;
+    d.valid = valid; d.valid_frame_stride = valid_frame_stride; d.valid_person_stride = valid_person_stride;
+    d.segments = segments; d.colors = colors; d.S = S;
+    for (int c = 0; c < 3; ++c) d.dot_color[c] = dot_color[c];
+    d.thickness = thickness; d.dot_radius = dot_radius; d.min_score = min_score; d.fills = fills; d.R = R;
+    d.out_bgr = out_bgr; d.out_row_stride = out_row_stride; d.out_frame_stride = out_frame_stride;
+    d.out_y = out_y; d.out_uv = out_uv; d.y_row_stride = y_row_stride; d.uv_row_stride = uv_row_stride; d.y_frame_stride = y_frame_stride;
+    d.uv_frame_stride = uv_frame_stride;
+    d.coef = kCoef[matrix][full_range ? 1 : 0]; d.full_range = full_range ? 1 : 0; d.rgb = rgb ? 1 : 0;
+    kasf_launch_draw_poses((hipStream_t)stream, &d);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int kasf_bgr_to_nv12(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, void* out_y, void* out_uv,
+                     int64_t y_row_stride, int64_t uv_row_stride, int64_t y_frame_stride, int64_t uv_frame_stride, int32_t matrix, int32_t full_range, int32_t rgb,
+                     void* stream) {
+    static const uint8_t kNoDot[3] = {0, 0, 0};
+    if (!out_y || !out_uv) return kasf_set_error(2, "null pointer argument");
+    return kasf_draw_poses(frames, n_frames, Hf, Wf, row_stride, frame_stride, nullptr, 0, 0, 0, 0, 0, 0, 0, nullptr, 0, 0, nullptr, nullptr, 0, kNoDot, 1, 0, 0.0f,
+                           nullptr, 0, nullptr, 0, 0, out_y, out_uv, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride, matrix, full_range, rgb, stream);
+}
+
+int kasf_pose_panel(const float* poses, int64_t n, const float* view, float* out, void* stream) {
+    if (n < 0 || n > ((int64_t)1 << 40)) return kasf_set_error(2, "pose_panel: n must be in [0, 2^40]");
+    if (!view) return kasf_set_error(2, "null pointer argument");
+    for (int i = 0; i < 8; ++i)
+        if (!std::isfinite(view[i])) return kasf_set_error(2, "pose_panel: every view coefficient must be finite");
+    if (n == 0) return 0;
+    if (!poses || !out) return kasf_set_error(2, "null pointer argument");
+    kasf_launch_pose_panel((hipStream_t)stream, poses, n, view, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // ---- detector output -> person boxes (kasf.h, kasf_detect_boxes) ----
 static const char* detect_shape_error(int32_t batch, int64_t n_per_image, int32_t max_candidates) {
     if (batch < 0 || batch > 65535) return "detect: batch must be in [0, 65535]";

@@ -227,6 +227,13 @@ void kasf_launch_yuv420_to_bgr(hipStream_t s, const void* y, const void* c0, con
                                int64_t c_row_stride, int64_t y_frame_stride, int64_t c_frame_stride, void* out, int64_t out_row_stride, int64_t out_frame_stride,
                                const int coef[5], int full_range, int rgb);
 
+// ---- k_draw.hip: skeletons over the frame and the encoder's NV12 surface in one launch (kasf.h, kasf_draw_poses / kasf_bgr_to_nv12), and the 3-D panel's
+// projection (kasf_pose_panel): view = the six coefficients and the two offsets as HOST floats passed by value into the launch.  Arguments as checked by the
+// entry points ----
+#include "draw_args.h"
+void kasf_launch_draw_poses(hipStream_t s, const KasfDrawLaunch* d);
+void kasf_launch_pose_panel(hipStream_t s, const float* poses, int64_t n, const float view[8], float* out);
+
 // ---- k_detect.hip: YOLOv3 detector output -> person boxes (kasf.h, kasf_detect_boxes): a selection launch (every candidate's key slot, the box and score slots of the
 // passing ones) and one sort + NMS + output workgroup per image.  Arguments as checked by the entry point; returns nullptr or a message when the launch cannot be made ----
 #define KASF_DETECT_FORM_PREDICTION 0
