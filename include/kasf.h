@@ -32,6 +32,8 @@
  *   kasf_heatmap_keypoints <- get_final_preds (get_max_preds, POST_PROCESS, transform_preds) and box_to_center_scale: what the demo does on the host between
  *                             HRNet's output tensor and the COCO keypoints   demo/lib/hrnet/gen_kpts.py:158-161, demo/lib/hrnet/lib/utils/inference.py:21-82,
  *                             demo/lib/hrnet/lib/utils/transforms.py:50-101, demo/lib/hrnet/lib/utils/utilitys.py:102-135
+ *   kasf_heatmap_flip_keypoints <- the same behind HRNet's flip test: flip_back with the left / right pairs, SHIFT_HEATMAP, the float32 average
+ *                             demo/lib/hrnet/lib/utils/transforms.py:15-30, demo/lib/hrnet/experiments/w48_384x288_adam_lr1e-3.yaml:119-121
  *   kasf_detect_boxes      <- predict_transform, write_results (objectness threshold, class arg-max, persons only, sort, greedy NMS) and the un-letterbox of
  *                             yolo_human_det: what the demo does between the YOLOv3 network's output and the person boxes
  *                             demo/lib/yolov3/util.py:34-81,107-225, demo/lib/yolov3/bbox.py:51-78, demo/lib/yolov3/human_detector.py:116-168
@@ -314,6 +316,30 @@ int kasf_pose_world(const float* poses, int64_t frames, const float* quat4, cons
 #define KASF_LAYOUT_H36M 1
 int kasf_heatmap_keypoints(const void* hm, int32_t dtype, int64_t n, int32_t H, int32_t W, const float* geom, int32_t geom_kind, double aspect, int32_t refine,
                            int32_t out_layout, float* out, float* coco_scratch, void* stream);
+
+/* ---- flip-tested pose-network heatmaps -> keypoints (a symbol ADDED under ABI 12: additive, kasf_version() stays 12; look it up by name) ----
+ * The flip test of a top-down pose network (HRNet's TEST.FLIP_TEST with SHIFT_HEATMAP, w48_384x288_adam_lr1e-3.yaml:119-121; flip_back and its matched_parts,
+ * transforms.py:15-30) merged and decoded in ONE launch: hm [n][17][H][W] is the network's output for the crops, hm_flipped [n][17][H][W] its output for the
+ * mirrored crops (input.flip(3)), both of `dtype` (KASF_DTYPE_F32, _F16 or _BF16; the 16-bit types are widened to fp32 on load, which is exact), contiguous,
+ * only read.  On the fp32 values:
+ *   src_x(x)           = shift ? min(W - x, W - 1) : W - 1 - x
+ *   merged[p][j][y][x] = (hm[p][j][y][x] + hm_flipped[p][partner[j]][y][src_x(x)]) * 0.5f
+ * one fp32 add and one fp32 multiply, not contracted, denormals kept: (output + output_flipped) * 0.5 of float32 numpy arrays.  With `shift`, src_x is
+ * output_flipped[:, :, :, 1:] = output_flipped.clone()[:, :, :, 0:-1] after flip_back: column 0 keeps its unshifted value, every other column takes its left
+ * neighbour's; W = 1 falls under the same formula.  inf + (-inf) is a NaN like any other.  For 16-bit input this is NOT what half-precision arithmetic on the
+ * tensors would give: it is the reference's float32 procedure applied to the exact upcasts.
+ * merged is then decoded exactly as kasf_heatmap_keypoints decodes a map -- first maximum in row-major order, first NaN wins and scores NaN, the "score > 0"
+ * mask, the quarter-pixel refinement with strict bounds and fp32 differences of MERGED neighbours, the crop geometry, the fp64 affine -- into out [n][17][3].
+ * partner: a HOST array of 17 joint indices, read during the call and passed by value into the launch; NULL = the COCO pairs (1,2) (3,4) (5,6) (7,8) (9,10)
+ * (11,12) (13,14) (15,16), joint 0 its own partner.  It must be an involution on 0..16: every value in range and partner[partner[j]] == j.
+ * merged_out: NULL, or [n][17][H][W] fp32 (device, overlapping neither input) that the same launch fills with every merged value; when NULL no store is issued.
+ * geom, geom_kind, aspect, refine, out_layout, out, coco_scratch, stream: exactly as kasf_heatmap_keypoints takes them.  One launch, plus kasf_coco_h36m's for
+ * KASF_LAYOUT_H36M; nothing is allocated.  n = 0 does nothing.  Error 2, before a device or a pointer is touched: every refusal of kasf_heatmap_keypoints, a
+ * null hm_flipped with n > 0, a partner that is no involution on 0..16, merged_out equal to hm or hm_flipped. */
+int kasf_heatmap_flip_keypoints(const void* hm, const void* hm_flipped, int32_t dtype, int64_t n, int32_t H, int32_t W,
+                                const int32_t* partner /* host, 17 entries, NULL = COCO pairs */, int32_t shift,
+                                const float* geom, int32_t geom_kind, double aspect, int32_t refine, int32_t out_layout,
+                                float* out, float* coco_scratch, float* merged_out /* may be NULL */, void* stream);
 
 /* ---- YOLOv3 detector output -> person boxes in frame pixels (ADDED under ABI 12: additive, kasf_version() stays 12; a library without it fails to load on the
  * missing symbol).  Replaces, on the device and without a host synchronisation, what yolo_human_det does behind the detector network (human_detector.py:116-168):

@@ -23,6 +23,9 @@ Public surface mirrors the reference's interface for this path:
                                         device; `layout="coco"` on the three lifts, `--layout coco`)
   heatmaps_to_keypoints                 demo/lib/hrnet/lib/utils/inference.py:21-82, demo/lib/hrnet/gen_kpts.py:158-161 (a top-down pose network's
                                         heatmaps -> COCO-17 or H36M-17 keypoints in image pixels, on the device; `StreamLifter.push_heatmaps`)
+  heatmaps_to_keypoints(flipped=...)    demo/lib/hrnet/lib/utils/transforms.py:15-30, demo/lib/hrnet/experiments/w48_384x288_adam_lr1e-3.yaml:119-121 (the flip test:
+                                        the network's output for the mirrored crops mirrored back, left / right maps swapped, shifted one column,
+                                        averaged with the direct output in float32 and decoded, in one launch; `push_heatmaps(flipped=...)`)
   letterbox_frames, LetterboxResult     demo/lib/yolov3/preprocess.py:9-38, demo/lib/yolov3/human_detector.py:131 (video frames -> the YOLOv3 network's input, on the
                                         device: letterbox with bicubic resampling onto a canvas of 128, channel reversal, planes, / 255; one launch,
                                         reads the decoder's frame in place; its width / height are what `yolo_heads_to_boxes` takes)

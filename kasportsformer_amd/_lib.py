@@ -96,6 +96,7 @@ SIGNATURES = {
     "kasf_coco_h36m": (_i32, [_vp, _i64, _vp, _vp]),
     "kasf_pose_world": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "kasf_heatmap_keypoints": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i32, C.c_double, _i32, _i32, _vp, _vp, _vp]),
+    "kasf_heatmap_flip_keypoints": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _vp, _i32, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp]),
     "kasf_crop_persons": (_i32, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _i32, C.c_double, _i64, _vp, _i32, _i32, _i32, C.POINTER(_f32), _i32, _vp, _vp]),
     "kasf_letterbox_plan": (_i32, [_i32, _i32, _i32, _i32, _pi32, _pi32, _pi32, _pi32]),
     "kasf_letterbox_frames": (_i32, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -1225,6 +1225,37 @@ int kasf_heatmap_keypoints(const void* hm, int32_t dtype, int64_t n, int32_t H, 
     return 0;
 }
 
+// ---- flip-tested pose-network heatmaps -> keypoints (kasf.h, kasf_heatmap_flip_keypoints) ----
+int kasf_heatmap_flip_keypoints(const void* hm, const void* hm_flipped, int32_t dtype, int64_t n, int32_t H, int32_t W, const int32_t* partner, int32_t shift,
+                                const float* geom, int32_t geom_kind, double aspect, int32_t refine, int32_t out_layout, float* out, float* coco_scratch,
+                                float* merged_out, void* stream) {
+    static const int32_t coco_pairs[17] = {0, 2, 1, 4, 3, 6, 5, 8, 7, 10, 9, 12, 11, 14, 13, 16, 15};
+    if (n < 0) return kasf_set_error(2, "heatmap_flip_keypoints: n must be >= 0");
+    if (H < 1 || W < 1) return kasf_set_error(2, "heatmap_flip_keypoints: H and W must be >= 1");
+    if ((int64_t)H * W > ((int64_t)1 << 24)) return kasf_set_error(2, "heatmap_flip_keypoints: H * W must be <= 2^24 (the reference's index arithmetic is fp32)");
+    if (dtype != KASF_F32 && dtype != KASF_F16 && dtype != KASF_BF16) return kasf_set_error(2, "heatmap_flip_keypoints: dtype must be KASF_DTYPE_F32, _F16 or _BF16");
+    if (geom_kind != KASF_GEOM_CENTER_SCALE && geom_kind != KASF_GEOM_BOX) return kasf_set_error(2, "heatmap_flip_keypoints: geom_kind must be KASF_GEOM_CENTER_SCALE or KASF_GEOM_BOX");
+    if (out_layout != KASF_LAYOUT_COCO && out_layout != KASF_LAYOUT_H36M) return kasf_set_error(2, "heatmap_flip_keypoints: out_layout must be KASF_LAYOUT_COCO or KASF_LAYOUT_H36M");
+    if (geom_kind == KASF_GEOM_BOX && !(aspect > 0.0)) return kasf_set_error(2, "heatmap_flip_keypoints: aspect must be > 0 with KASF_GEOM_BOX");
+    const int32_t* pt = partner ? partner : coco_pairs;
+    for (int j = 0; j < 17; ++j)
+        if (pt[j] < 0 || pt[j] > 16) return kasf_set_error(2, "heatmap_flip_keypoints: partner entries must be in [0, 16]");
+    for (int j = 0; j < 17; ++j)
+        if (pt[pt[j]] != j) return kasf_set_error(2, "heatmap_flip_keypoints: partner must be an involution (partner[partner[j]] == j)");
+    if (n == 0) return 0;
+    if (!hm || !hm_flipped || !geom || !out || (out_layout == KASF_LAYOUT_H36M && !coco_scratch)) return kasf_set_error(2, "null pointer argument");
+    if (merged_out && ((const void*)merged_out == hm || (const void*)merged_out == hm_flipped))
+        return kasf_set_error(2, "heatmap_flip_keypoints: merged_out must not overlap hm or hm_flipped");
+    const bool h36m = out_layout == KASF_LAYOUT_H36M;
+    int pv[17];
+    for (int j = 0; j < 17; ++j) pv[j] = pt[j];
+    kasf_launch_heatmap_flip_keypoints((hipStream_t)stream, hm, hm_flipped, dtype, n, H, W, pv, shift ? 1 : 0, geom, geom_kind, aspect, refine ? 1 : 0,
+                                       h36m ? coco_scratch : out, merged_out);
+    if (h36m) kasf_launch_coco_h36m((hipStream_t)stream, coco_scratch, n, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // ---- person boxes -> pose-network inputs (kasf.h, kasf_crop_persons) ----
 int kasf_crop_persons(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, const int32_t* frame_index,
                       const float* geom, int32_t geom_kind, double aspect, int64_t n, void* out, int32_t out_dtype, int32_t out_w, int32_t out_h,

@@ -4,6 +4,7 @@
     kp = heatmaps_to_keypoints(hm, boxes=boxes, aspect=frame_h / frame_w) # the detector's boxes instead of the crop's center / scale
     kp = heatmaps_to_keypoints(hm, center, scale, layout="h36m")          # ... and through coco_to_h36m: what lift_track / lift_tracks take
     poses = lifter.push_heatmaps(hm, center, scale)                       # StreamLifter: decode, then push
+    kp = heatmaps_to_keypoints(hm, center, scale, flipped=hm_of_mirrored_crops)   # the flip test: mirror back, swap left / right, shift, average, decode: one launch
 
 ``heatmaps_to_keypoints`` is ``get_final_preds`` (demo/lib/hrnet/lib/utils/inference.py:21-82: argmax per joint map, the quarter-pixel ``POST_PROCESS``
 step, ``transform_preds`` back to image pixels), which the demo runs on the host on a copy of HRNet's output (demo/lib/hrnet/gen_kpts.py:158-161); HRNet,
@@ -12,6 +13,8 @@ closed form of its three-point affine evaluated in fp64 and rounded once, within
 gives (include/kasf.h, ``kasf_heatmap_keypoints``, states every rule).
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -22,6 +25,13 @@ from .pose import _float32, _stream, check_layout
 _DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 _NP_DTYPES = (np.float32, np.float16)
 MAX_MAP = 1 << 24               # H * W the entry point takes: the reference's index arithmetic is fp32
+COCO_PAIRS = ((1, 2), (3, 4), (5, 6), (7, 8), (9, 10), (11, 12), (13, 14), (15, 16))      # flip_back's matched_parts for COCO-17; joint 0 is its own partner
+
+
+class FlipDecode(NamedTuple):
+    """``heatmaps_to_keypoints(..., flipped=..., merged=...)``: the keypoints [...,17,3] and the fp32 merged maps [...,17,H,W] they were decoded from."""
+    keypoints: torch.Tensor
+    merged: torch.Tensor
 
 
 def _heatmaps(a, who: str) -> torch.Tensor:
@@ -71,8 +81,75 @@ def check_heatmap_args(heatmaps, center, scale, boxes, aspect, who: str):
     return hm, parts, _lib.GEOM_BOX, aspect
 
 
+def partner_table(pairs, who: str) -> np.ndarray:
+    """``pairs=`` of a flip-tested call -> int32 [17], joint j's partner (itself when unpaired): None = ``COCO_PAIRS``; otherwise a sequence of ``(a, b)``
+    with distinct integers in 0..16, every joint in at most one pair -- so the table is an involution, as ``kasf_heatmap_flip_keypoints`` requires."""
+    if pairs is None:
+        pairs = COCO_PAIRS
+    if isinstance(pairs, (str, bytes)) or not hasattr(pairs, "__iter__"):
+        raise TypeError(f"{who}: pairs must be a sequence of (a, b) joint pairs, got {type(pairs).__name__}")
+    table = np.arange(17, dtype=np.int32)
+    for pair in pairs:
+        try:
+            a, b = pair
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: pairs must hold (a, b) joint pairs, got {pair!r}") from None
+        for v in (a, b):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{who}: joint indices in pairs must be integers, got {v!r}")
+            if not 0 <= v <= 16:
+                raise ValueError(f"{who}: joint indices in pairs must be in [0, 16], got {v}")
+        if a == b or table[a] != a or table[b] != b:
+            raise ValueError(f"{who}: every joint may appear in at most one pair, and not with itself: {tuple(pair)!r}")
+        table[a], table[b] = b, a
+    return table
+
+
+def check_flip_args(hm: torch.Tensor, flipped, shift, pairs, who: str):
+    """What the flip test adds to ``check_heatmap_args``, refused without a device -> ``None`` without ``flipped`` (``shift`` / ``pairs`` must then be at
+    their defaults), else ``(hmf, shift, partner)``: the flipped heatmaps as a tensor where they are, of ``hm``'s shape and dtype, and ``partner_table``."""
+    if flipped is None:
+        if shift is not True or pairs is not None:
+            raise ValueError(f"{who}: shift and pairs go with flipped=")
+        return None
+    hmf = _heatmaps(flipped, who)
+    if tuple(hmf.shape) != tuple(hm.shape) or hmf.dtype != hm.dtype:
+        raise ValueError(f"{who}: flipped must have the heatmaps' shape and dtype, {tuple(hm.shape)} {hm.dtype}, got {tuple(hmf.shape)} {hmf.dtype}")
+    if not isinstance(shift, (bool, np.bool_)):
+        raise TypeError(f"{who}: shift must be a bool, got {shift!r}")
+    return hmf, bool(shift), partner_table(pairs, who)
+
+
+def _check_merged(merged, hm: torch.Tensor, flip, who: str):
+    """``merged=`` -> None, True, or the caller's tensor: contiguous CUDA fp32 of the heatmaps' shape."""
+    if merged is None or merged is False:
+        return None
+    if flip is None:
+        raise ValueError(f"{who}: merged goes with flipped=")
+    if merged is True:
+        return True
+    if not isinstance(merged, torch.Tensor):
+        raise TypeError(f"{who}: merged must be True or a CUDA float32 tensor, got {type(merged).__name__}")
+    if merged.dtype != torch.float32:
+        raise TypeError(f"{who}: merged must be float32, got {merged.dtype}")
+    if not merged.is_cuda:
+        raise RuntimeError(f"{who}: merged must be on the GPU, got {merged.device}")
+    if tuple(merged.shape) != tuple(hm.shape) or not merged.is_contiguous():
+        raise ValueError(f"{who}: merged must be contiguous {tuple(hm.shape)}, got {tuple(merged.shape)} with strides {merged.stride()}")
+    return merged
+
+
+def _spans_overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """Do the address ranges that two non-empty tensors of one device span intersect?  (No dereference: sizes and strides only.)"""
+    def span(t):
+        first = t.data_ptr()
+        return first, first + (sum((n - 1) * abs(s) for n, s in zip(t.shape, t.stride())) + 1) * t.element_size()
+    (a0, a1), (b0, b1) = span(a), span(b)
+    return a0 < b1 and b0 < a1
+
+
 def heatmaps_to_keypoints(heatmaps, center=None, scale=None, *, boxes=None, aspect=None, refine: bool = True, layout: str = "coco",
-                          device=None) -> torch.Tensor:
+                          device=None, flipped=None, shift: bool = True, pairs=None, merged=None):
     """Pose-network heatmaps -> keypoints in image pixels: ``heatmaps`` [...,17,H,W], float32, float16 or bfloat16 (the 16-bit types are widened on load,
     exactly), a torch tensor on the GPU -- the normal case: read in place when contiguous (a strided view is packed first), never modified -- or numpy /
     torch on the host, which is uploaded.  Returns CUDA fp32 [...,17,3]: image x, image y, score (the map's maximum; a map that holds a NaN scores NaN).
@@ -85,11 +162,23 @@ def heatmaps_to_keypoints(heatmaps, center=None, scale=None, *, boxes=None, aspe
     ``refine``: the quarter-pixel step towards the higher neighbour (the demo's ``TEST.POST_PROCESS``).  ``layout``: "coco", the network's joint order,
     or "h36m", ``coco_to_h36m`` of that result bit for bit (one more launch).  ``device``: where host input goes (default: the current GPU); GPU input
     stays where it is.  There is no host path: without a GPU the call raises ``RuntimeError``.  Exception types as ``coco_to_h36m``; every refusal comes
-    before any launch."""
+    before any launch.
+
+    The flip test (HRNet's ``FLIP_TEST`` with ``SHIFT_HEATMAP``; one launch, ``kasf_heatmap_flip_keypoints``): ``flipped`` = the network's output for the
+    mirrored crops (``inputs.flip(-1)``), of the heatmaps' shape and dtype, given as ``heatmaps`` may be.  The keypoints are then decoded from
+    ``merged[..., j, y, x] = (heatmaps[..., j, y, x] + flipped[..., partner[j], y, src_x]) * 0.5`` in float32, ``src_x = min(W - x, W - 1)`` with ``shift``
+    (the mirrored map moved one column right, column 0 keeping its value) and ``W - 1 - x`` without.  For 16-bit input this is deliberately not what half
+    arithmetic on the tensors gives: it is the reference's float32 procedure on the exact upcasts.  ``pairs``: the left / right joint pairs ``(a, b)``
+    (default ``COCO_PAIRS``; ``[]`` swaps nothing).  ``merged=True`` also returns the fp32 merged maps [...,17,H,W]; ``merged=tensor`` writes them into the
+    caller's contiguous CUDA float32 tensor of that shape.  With ``merged`` the call returns ``FlipDecode(keypoints, merged)``, otherwise the keypoints alone.
+    ``shift`` / ``pairs`` / ``merged`` without ``flipped`` raise ``ValueError``; without ``flipped`` the call is the plain decode, unchanged."""
     who = "heatmaps_to_keypoints"
     h36m = not check_layout(layout, who)
     hm, parts, kind, aspect = check_heatmap_args(heatmaps, center, scale, boxes, aspect, who)
-    on_gpu = [t.device for t in (hm,) + parts if t.is_cuda]
+    flip = check_flip_args(hm, flipped, shift, pairs, who)
+    merged = _check_merged(merged, hm, flip, who)
+    extra = ((flip[0],) if flip is not None else ()) + ((merged,) if isinstance(merged, torch.Tensor) else ())
+    on_gpu = [t.device for t in (hm,) + parts + extra if t.is_cuda]
     if device is not None:
         dev = torch.device(device)
         if dev.type != "cuda":
@@ -104,20 +193,46 @@ def heatmaps_to_keypoints(heatmaps, center=None, scale=None, *, boxes=None, aspe
         dev = torch.device("cuda", torch.cuda.current_device())
     if any(d != dev for d in on_gpu):
         raise RuntimeError(f"{who}: input on {[str(d) for d in on_gpu]}, asked for {dev}")
-    return decode(hm.to(dev), tuple(t.to(dev) for t in parts), kind, aspect, refine, h36m)
+    if flip is None:
+        return decode(hm.to(dev), tuple(t.to(dev) for t in parts), kind, aspect, refine, h36m)
+    if isinstance(merged, torch.Tensor) and any(t.is_cuda and t.numel() and _spans_overlap(t, merged) for t in (hm, flip[0])):
+        raise ValueError(f"{who}: merged must not overlap heatmaps or flipped")
+    flip = (flip[0].to(dev),) + flip[1:]
+    if merged is None:
+        return decode(hm.to(dev), tuple(t.to(dev) for t in parts), kind, aspect, refine, h36m, flip)
+    return FlipDecode(*decode(hm.to(dev), tuple(t.to(dev) for t in parts), kind, aspect, refine, h36m, flip, merged))
 
 
-def decode(hm: torch.Tensor, parts, kind: int, aspect: float, refine: bool, h36m: bool) -> torch.Tensor:
-    """``kasf_heatmap_keypoints`` on checked CUDA tensors of one device (what ``heatmaps_to_keypoints`` and ``StreamLifter.push_heatmaps`` end in)."""
+def decode(hm: torch.Tensor, parts, kind: int, aspect: float, refine: bool, h36m: bool, flip=None, merged=None):
+    """``kasf_heatmap_keypoints`` on checked CUDA tensors of one device (what ``heatmaps_to_keypoints`` and ``StreamLifter.push_heatmaps`` end in); with
+    ``flip`` = ``(hmf, shift, partner)`` of ``check_flip_args``, ``kasf_heatmap_flip_keypoints``, and with ``merged`` (True, or the checked tensor to
+    fill) -> ``(keypoints, merged maps)``."""
     lead, (H, W) = tuple(hm.shape[:-3]), hm.shape[-2:]
     hm = hm.contiguous()                                         # the same tensor when it already is
     geom = (torch.cat(parts, dim=-1) if len(parts) == 2 else parts[0]).contiguous()
     out = torch.empty(lead + (17, 3), dtype=torch.float32, device=hm.device)
     n = out.numel() // 51
+    if flip is None:
+        if n:
+            scratch = torch.empty_like(out) if h36m else None
+            with torch.cuda.device(hm.device):
+                _lib.check(_lib.load().kasf_heatmap_keypoints(hm.data_ptr(), _DTYPES[hm.dtype], n, int(H), int(W), geom.data_ptr(), kind, aspect,
+                                                              int(bool(refine)), _lib.LAYOUT_H36M if h36m else _lib.LAYOUT_COCO, out.data_ptr(),
+                                                              scratch.data_ptr() if h36m else None, _stream()))
+        return out
+    hmf, shift, partner = flip
+    partner = np.ascontiguousarray(partner, dtype=np.int32)      # host memory, read during the call
+    if partner.shape != (17,):
+        raise ValueError(f"heatmap decode: the partner table must have 17 entries, got shape {partner.shape}")
+    hmf = hmf.contiguous()
+    if merged is True:
+        merged = torch.empty(tuple(hm.shape), dtype=torch.float32, device=hm.device)
     if n:
         scratch = torch.empty_like(out) if h36m else None
         with torch.cuda.device(hm.device):
-            _lib.check(_lib.load().kasf_heatmap_keypoints(hm.data_ptr(), _DTYPES[hm.dtype], n, int(H), int(W), geom.data_ptr(), kind, aspect,
-                                                          int(bool(refine)), _lib.LAYOUT_H36M if h36m else _lib.LAYOUT_COCO, out.data_ptr(),
-                                                          scratch.data_ptr() if h36m else None, _stream()))
-    return out
+            _lib.check(_lib.load().kasf_heatmap_flip_keypoints(hm.data_ptr(), hmf.data_ptr(), _DTYPES[hm.dtype], n, int(H), int(W), partner.ctypes.data,
+                                                               int(shift), geom.data_ptr(), kind, aspect, int(bool(refine)),
+                                                               _lib.LAYOUT_H36M if h36m else _lib.LAYOUT_COCO, out.data_ptr(),
+                                                               scratch.data_ptr() if h36m else None, merged.data_ptr() if merged is not None else None,
+                                                               _stream()))
+    return out if merged is None else (out, merged)
