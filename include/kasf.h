@@ -16,6 +16,9 @@
  *   kasf_forward           <- KASportsFormer.forward              model/KASportsFormer.py:320-347
  *   kasf_backward          <- torch.autograd of the above         train_and_evaluate_sp.py:241  (loss.backward())
  *   kasf_loss3             <- mpjpe + 0.5 n_mpjpe + 20 velocity   utils/loss_calc.py:6-27, train_and_evaluate_sp.py:212-222
+ *   kasf_loss7             <- the complete seven-term loss: the three above + lambda_limb_len_var loss_limb_var_calc + lambda_limb_len loss_limb_len_calc
+ *                             + lambda_limb_cos_simi loss_cos_simi_calc + lambda_limb_cos_simi_velocity loss_cos_simi_velocity_calc
+ *                             utils/loss_calc.py:30-94, train_and_evaluate_sp.py:14-15,216-220, every yaml under configs/, lines 29-35
  *   kasf_adamw_step        <- optim.AdamW(...).step()             train_and_evaluate_sp.py:270-272,243
  *   kasf_gather_clips      <- Dataset.__getitem__ + DataLoader collate data/reader/sp_dataset.py:45-92
  *   kasf_joint_flip        <- joint_flip                            utils/utilities.py:128-135
@@ -169,6 +172,28 @@ int kasf_backward(const kasf_model* m, const float* params, const void* packed, 
  * scratch: per-clip sums, added in a fixed order so that the result is bit-reproducible); dpred = grad_scale * dTotal/dpred */
 int kasf_loss3(const float* pred, const float* target, float* dpred, float* losses, int64_t losses_floats, int32_t batch, int32_t n_frames,
                float lambda_n_mpjpe, float lambda_velocity, float grad_scale, void* stream);
+
+/* The reference's complete loss (train_and_evaluate_sp.py:216-220, `loss_total_complete`) and its gradient, one launch per call plus the fixed-order finish.
+ * `lambdas`: six HOST floats {n_mpjpe, velocity, limb_len_var, limb_len, limb_cos_simi, limb_cos_simi_velocity}, the yaml keys lambda_n_mpjpe,
+ * lambda_mpjpe_velocity, lambda_limb_len_var, lambda_limb_len, lambda_limb_cos_simi, lambda_limb_cos_simi_velocity (every yaml under configs/, lines 29-35), read before return.
+ * On return losses[0..7] = {total, mpjpe, n_mpjpe, velocity, limb_len_var, limb_len, cos_simi, cos_simi_velocity}; all seven parts are computed whatever the
+ * lambdas are (the reference logs them).  Behind them the per-clip sums, losses[8 + 8 * b + k] for part k + 1 (k = 7 unused), added in a fixed order:
+ * `losses_floats` >= 8 + 8 * batch (error 5 otherwise); batch, n_frames >= 1 and n_frames <= KASF_LOSS7_MAX_FRAMES (error 2).  dpred = grad_scale * dTotal/dpred.
+ *   limbs    l_k = x[a_k] - x[b_k] for the 16 pairs of get_limb_lens (utils/loss_calc.py:33-41), len_k = |l_k|
+ *   angles   the 18 limb pairs (i, j) of get_limb_cos_simi (loss_calc.py:69-78): c = (l_i / max(|l_i|, 1e-8)) . (l_j / max(|l_j|, 1e-8)) (torch 2.x
+ *            cosine_similarity), theta = acos(clamp(c, -1 + 1e-7, 1 - 1e-7)), the two bounds rounded to fp32
+ *   limb_len_var       mean over (B, 16) of the unbiased variance over t of len_pred; 0 when n_frames <= 1            loss_calc.py:45-51
+ *   limb_len           mean over (B, T, 16) of |len_pred - len_target|                                               loss_calc.py:54-58
+ *   cos_simi           mean over (B, T, 18) of |theta_pred - theta_target|                                           loss_calc.py:80-83
+ *   cos_simi_velocity  mean over (B, T - 1, 18) of |(theta_p[t+1] - theta_p[t]) - (theta_y[t+1] - theta_y[t])|; 0 when n_frames <= 1   loss_calc.py:86-94
+ * Gradients follow torch: sign(0) = 0 for the L1 terms, nothing through clamp outside its closed range, nothing through a norm at the zero vector (a zero-length
+ * limb gives theta = pi / 2 and a finite gradient).  fp32, no atomics, every sum in a fixed order: values and dpred are bit-reproducible from run to run, and a
+ * clip's dpred rows and per-clip sums do not depend on the other clips of the batch beyond `batch` itself.  The three old terms are computed exactly as
+ * kasf_loss3 computes them and a term whose lambda is 0.f adds nothing to dpred: with the four new lambdas zero, dpred and losses[0..3] are kasf_loss3's bits. */
+#define KASF_LOSS7_MAX_FRAMES 360
+int kasf_loss7(const float* pred, const float* target, float* dpred, float* losses, int64_t losses_floats, int32_t batch, int32_t n_frames,
+               const float* lambdas /* host, 6 floats: n_mpjpe, velocity, limb_len_var, limb_len, limb_cos_simi, limb_cos_simi_velocity */, float grad_scale,
+               void* stream);
 
 /* torch.optim.AdamW step over n contiguous fp32 elements (n multiple of 4); step_index starts at 1 */
 int kasf_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2, float eps,

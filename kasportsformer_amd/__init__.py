@@ -3,6 +3,9 @@
 Public surface mirrors the reference's interface for this path:
   KASportsFormer, load_model            model/KASportsFormer.py:290, model/model_tools.py:79
   loss3, mpjpe_loss / ...               utils/loss_calc.py:6-27 (+ the train-step combination)
+  loss7, LOSS7_NAMES                    utils/loss_calc.py:30-94, train_and_evaluate_sp.py:14-15,216-220 (the complete seven-term loss the yaml's six lambdas
+                                        describe -- limb-length variance, limb length, limb angles, angle velocity on top of the three -- and its
+                                        gradient in one launch; `train_one_epoch(lambda_limb_len=...)`)
   FusedAdamW                            optim.AdamW as used in train_and_evaluate_sp.py:270-272
   DataParallel                          nn.DataParallel replacement: one process per GPU, RCCL all-reduce
   joint_flip, predict_flip_tta,         utils/utilities.py:128-135, train_and_evaluate_sp.py:27-149, utils/error_calc.py:5-48
@@ -51,7 +54,7 @@ Public surface mirrors the reference's interface for this path:
 """
 from .model import (KASportsFormer, load_model, set_single_stream, is_single_stream, set_deterministic, is_deterministic, set_fused_attention_backward,
                     is_fused_attention_backward)
-from .functional import loss3
+from .functional import loss3, loss7, LOSS7_NAMES
 from .optim import FusedAdamW
 from .parallel import DataParallel
 from .data import PackedClips, DeviceClipLoader, pack_clip_directory, read_clip_file, shard_indices
@@ -73,7 +76,7 @@ from .draw import draw_poses, bgr_to_nv12, poses_to_panel, DrawResult
 from .track import SortTracker, TrackResult, TrackState
 from .tracked import TrackedLifter, TrackedTick
 
-__all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_stream", "set_deterministic", "is_deterministic", "set_fused_attention_backward", "is_fused_attention_backward", "loss3", "FusedAdamW", "DataParallel", "joint_flip", "predict_flip_tta", "clip_metrics", "Evaluator",
+__all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_stream", "set_deterministic", "is_deterministic", "set_fused_attention_backward", "is_fused_attention_backward", "loss3", "loss7", "LOSS7_NAMES", "FusedAdamW", "DataParallel", "joint_flip", "predict_flip_tta", "clip_metrics", "Evaluator",
            "evaluate_one_epoch", "PackedClips", "DeviceClipLoader", "pack_clip_directory", "read_clip_file", "shard_indices",
            "checkpoint_save", "checkpoint_load", "strip_module_prefix", "adamw_state_dict", "load_adamw_state_dict", "warmup_lr", "apply_warmup", "ReduceLROnPlateau", "train_one_epoch",
            "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample",

@@ -28,6 +28,7 @@ SORT_MAX = 64                          # KASF_SORT_MAX: slots and max_dets of ka
 SORT_HEADER_BYTES = 64                 # KASF_SORT_HEADER_BYTES
 FLAG_TRAIN, FLAG_RETURN_REP, FLAG_KEEP = 1, 2, 4
 EVAL_COLS = 22
+LOSS7_MAX_FRAMES = 360               # KASF_LOSS7_MAX_FRAMES: n_frames of kasf_loss7
 MISC_EMBED_BWD, MISC_REFUSION_BWD, MISC_GATE_BWD, MISC_HEAD_BWD = 0, 1, 2, 3      # KASF_MISC_*: ops of kasf_op_misc_scratch_floats
 GCN_STAT_WORDS = 4 * 512 * 5     # KASF_GCN_STAT_WORDS: int64 words of one BatchNorm statistics buffer of kasf_op_gcn_fwd / kasf_op_gcn_bwd
 ABI_VERSION = 12        # kasf_version() of the library these prototypes describe (a stale in-tree .so is refused)
@@ -76,6 +77,7 @@ SIGNATURES = {
     "kasf_forward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "kasf_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "kasf_loss3": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _vp]),
+    "kasf_loss7": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(_f32), _f32, _vp]),
     "kasf_adamw_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp]),
     "kasf_gather_clips": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "kasf_joint_flip": (_i32, [_vp, _vp, _i64, _vp]),

@@ -984,6 +984,18 @@ int kasf_loss3(const float* pred, const float* target, float* dpred, float* loss
     return 0;
 }
 
+int kasf_loss7(const float* pred, const float* target, float* dpred, float* losses, int64_t losses_floats, int32_t batch, int32_t n_frames,
+               const float* lambdas, float grad_scale, void* stream) {
+    if (!pred || !target || !dpred || !losses || !lambdas) return kasf_set_error(2, "null pointer argument");
+    if (batch < 1 || n_frames < 1) return kasf_set_error(2, "loss7: batch and n_frames must be positive");
+    if (n_frames > KASF_LOSS7_MAX_FRAMES) return kasf_set_error(2, "loss7: n_frames above KASF_LOSS7_MAX_FRAMES (a clip's angles are held in 64 KB of LDS)");
+    if (losses_floats < 8 + 8 * (int64_t)batch) return kasf_set_error(5, "loss7: `losses` must hold 8 + 8 * batch floats (the per-clip sums live behind the result)");
+    static_assert(KASF_LOSS7_MAX_FRAMES * 174 + 2048 <= 65536, "k_loss7's LDS at the largest clip");
+    kasf_launch_loss7((hipStream_t)stream, pred, target, dpred, losses, batch, n_frames, lambdas, grad_scale);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 int kasf_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2, float eps,
                     float weight_decay, int32_t step_index, float grad_scale, void* stream) {
     if (!params || !grads || !exp_avg || !exp_avg_sq) return kasf_set_error(2, "null pointer argument");

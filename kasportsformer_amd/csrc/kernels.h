@@ -160,6 +160,10 @@ void kasf_launch_add3(int dt, hipStream_t s, void* dst, const void* a, const voi
 void kasf_launch_finalize_ls(hipStream_t s, float* dW, const float* W, const float* bias, const float* ls, float* db, float* dls, int N, int K);
 void kasf_launch_loss3(hipStream_t s, const float* pred, const float* tgt, float* dpred, float* losses, int B, int T, float lambda_n, float lambda_v,
                        float grad_scale);
+// ---- k_loss.hip: the seven-term loss (kasf.h, kasf_loss7); lambdas = six HOST floats passed by value into the launches; dynamic LDS = kasf_loss7_lds_bytes(T),
+// which the entry point keeps below 64 KB (T <= KASF_LOSS7_MAX_FRAMES) ----
+int64_t kasf_loss7_lds_bytes(int T);
+void kasf_launch_loss7(hipStream_t s, const float* pred, const float* tgt, float* dpred, float* losses, int B, int T, const float* lambdas, float grad_scale);
 void kasf_launch_adamw(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float wd,
                        float bc1, float bc2, float grad_scale);
 
