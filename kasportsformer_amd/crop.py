@@ -22,11 +22,9 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import _lib
-from .heatmap import _DTYPES
-from .pose import _float32, _stream
+from . import _args, _lib
 
-MAX_SIDE = 32767                # Hf, Wf, out_w, out_h the entry point takes
+MAX_SIDE = _args.MAX_SIDE       # Hf, Wf, out_w, out_h the entry point takes
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
 
@@ -34,25 +32,6 @@ class CropResult(NamedTuple):
     inputs: torch.Tensor       # CUDA [P, 3, out_h, out_w] of ``dtype``: what the pose network takes
     center: torch.Tensor       # CUDA fp32 [P, 2]: given, or box_to_center_scale of the box
     scale: torch.Tensor        # CUDA fp32 [P, 2]: with ``center``, what heatmaps_to_keypoints takes for the heatmaps of these crops
-
-
-def _frames(a, who: str) -> torch.Tensor:
-    """uint8 frames [Hf,Wf,3] or [F,Hf,Wf,3], numpy (shared, not copied) or torch, on the host or a GPU, as a detached tensor where they are."""
-    if isinstance(a, np.ndarray):
-        if a.dtype != np.uint8:
-            raise TypeError(f"{who}: frame must be uint8, got {a.dtype}")
-        t = torch.from_numpy(a if all(s >= 0 for s in a.strides) else np.ascontiguousarray(a))     # a padded pitch is kept
-    elif isinstance(a, torch.Tensor):
-        if a.dtype != torch.uint8:
-            raise TypeError(f"{who}: frame must be uint8, got {a.dtype}")
-        if a.device.type not in ("cpu", "cuda"):
-            raise RuntimeError(f"{who}: frame on unsupported device {a.device}")
-        t = a.detach()
-    else:
-        raise TypeError(f"{who}: frame must be a numpy array or a torch tensor, got {type(a).__name__}")
-    if t.dim() not in (3, 4) or t.shape[-1] != 3 or not 1 <= t.shape[-2] <= MAX_SIDE or not 1 <= t.shape[-3] <= MAX_SIDE or (t.dim() == 4 and t.shape[0] < 1):
-        raise ValueError(f"{who}: expected frame [Hf,Wf,3] or [F,Hf,Wf,3] with F >= 1 and Hf, Wf in [1, {MAX_SIDE}], got {tuple(t.shape)}")
-    return t
 
 
 def _triple(value, who: str, name: str, nonzero: bool) -> np.ndarray:
@@ -70,14 +49,14 @@ def _triple(value, who: str, name: str, nonzero: bool) -> np.ndarray:
 
 def check_crop_args(frame, boxes, center, scale, size, aspect, mean, std, dtype, frame_index, who: str):
     """Everything ``crop_persons`` can refuse without a device -> ``(frames, geom parts, kind, aspect, (out_w, out_h), mean_std [6] float32, frame_index or None)``."""
-    fr = _frames(frame, who)
+    fr = _args.frames(frame, who)
     Hf, Wf = int(fr.shape[-3]), int(fr.shape[-2])
     if boxes is None:
         if center is None or scale is None:
             raise ValueError(f"{who}: give boxes [P,4], or center and scale [P,2]")
         if aspect is not None:
             raise ValueError(f"{who}: aspect goes with boxes, not with center / scale")
-        parts = (_float32(center, who, "center"), _float32(scale, who, "scale"))
+        parts = (_args.as_tensor(center, who, "center", _args.FLOAT32), _args.as_tensor(scale, who, "scale", _args.FLOAT32))
         for name, t in zip(("center", "scale"), parts):
             if t.dim() != 2 or t.shape[1] != 2 or t.shape[0] != parts[0].shape[0]:
                 raise ValueError(f"{who}: expected center and scale [P,2], got {name} {tuple(t.shape)}")
@@ -85,7 +64,7 @@ def check_crop_args(frame, boxes, center, scale, size, aspect, mean, std, dtype,
     else:
         if center is not None or scale is not None:
             raise ValueError(f"{who}: give boxes, or center and scale, not both")
-        parts = (_float32(boxes, who, "boxes"),)
+        parts = (_args.as_tensor(boxes, who, "boxes", _args.FLOAT32),)
         if parts[0].dim() != 2 or parts[0].shape[1] != 4:
             raise ValueError(f"{who}: expected boxes [P,4] = x1, y1, x2, y2, got {tuple(parts[0].shape)}")
         aspect = Hf / Wf if aspect is None else float(aspect)        # the demo's: image.shape[0], image.shape[1] as model width, height (utilitys.py:151)
@@ -99,7 +78,7 @@ def check_crop_args(frame, boxes, center, scale, size, aspect, mean, std, dtype,
         raise TypeError(f"{who}: size must be (width, height), got {size!r}") from None
     if not (1 <= out_w <= MAX_SIDE and 1 <= out_h <= MAX_SIDE):
         raise ValueError(f"{who}: size = (width, height) must be in [1, {MAX_SIDE}], got {size!r}")
-    if dtype not in _DTYPES:
+    if dtype not in _args.DTYPES:
         raise TypeError(f"{who}: dtype must be torch.float32, torch.float16 or torch.bfloat16, got {dtype!r}")
     mean_std = np.concatenate((_triple(mean, who, "mean", False), _triple(std, who, "std", True)))
     if fr.dim() == 3:
@@ -145,21 +124,7 @@ def crop_persons(frame, boxes=None, *, center=None, scale=None, size=(288, 384),
     path: without a GPU the call raises ``RuntimeError``.  Exception types as ``heatmaps_to_keypoints``; every refusal comes before any launch."""
     who = "crop_persons"
     fr, parts, kind, aspect, (out_w, out_h), mean_std, fi = check_crop_args(frame, boxes, center, scale, size, aspect, mean, std, dtype, frame_index, who)
-    on_gpu = [t.device for t in (fr,) + parts + ((fi,) if fi is not None else ()) if t.is_cuda]
-    if device is not None:
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"{who}: device must be a GPU, got {dev}; kasportsformer_amd has no CPU path")
-    elif on_gpu:
-        dev = on_gpu[0]
-    elif torch.cuda.is_available():
-        dev = torch.device("cuda", torch.cuda.current_device())
-    else:
-        raise RuntimeError(f"{who}: no GPU available; kasportsformer_amd has no CPU path")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if any(d != dev for d in on_gpu):
-        raise RuntimeError(f"{who}: input on {[str(d) for d in on_gpu]}, asked for {dev}")
+    dev = _args.resolve_device((fr,) + parts + (fi,), device, who)
     return crop(fr.to(dev), tuple(t.to(dev) for t in parts), kind, aspect, out_w, out_h, mean_std, bool(swap_rb), dtype, None if fi is None else fi.to(dev))
 
 
@@ -177,6 +142,6 @@ def crop(fr: torch.Tensor, parts, kind: int, aspect: float, out_w: int, out_h: i
         mean_std = np.ascontiguousarray(mean_std, dtype=np.float32)
         with torch.cuda.device(fr.device):
             _lib.check(_lib.load().kasf_crop_persons(fr.data_ptr(), n_frames, Hf, Wf, int(fr.stride(-3)), frame_stride, None if fi is None else fi.data_ptr(),
-                                                     geom.data_ptr(), kind, float(aspect), P, out.data_ptr(), _DTYPES[dtype], out_w, out_h,
-                                                     mean_std.ctypes.data_as(C.POINTER(C.c_float)), int(swap_rb), cs.data_ptr(), _stream()))
+                                                     geom.data_ptr(), kind, float(aspect), P, out.data_ptr(), _args.DTYPES[dtype], out_w, out_h,
+                                                     mean_std.ctypes.data_as(C.POINTER(C.c_float)), int(swap_rb), cs.data_ptr(), _args.stream()))
     return CropResult(out, cs[:, :2], cs[:, 2:])

@@ -1219,15 +1219,21 @@ int kasf_pose_world(const float* poses, int64_t frames, const float* quat4, cons
 }
 
 // ---- pose-network heatmaps -> keypoints (kasf.h, kasf_heatmap_keypoints) ----
+// what the plain and the flip-tested entry point refuse alike, in this order; who = the entry point's name in its messages
+static int heatmap_refusal(const char* who, int64_t n, int32_t H, int32_t W, int32_t dtype, int32_t geom_kind, int32_t out_layout, double aspect) {
+    const char* why = nullptr;
+    if (n < 0) why = "n must be >= 0";
+    else if (H < 1 || W < 1) why = "H and W must be >= 1";
+    else if ((int64_t)H * W > ((int64_t)1 << 24)) why = "H * W must be <= 2^24 (the reference's index arithmetic is fp32)";
+    else if (dtype != KASF_F32 && dtype != KASF_F16 && dtype != KASF_BF16) why = "dtype must be KASF_DTYPE_F32, _F16 or _BF16";
+    else if (geom_kind != KASF_GEOM_CENTER_SCALE && geom_kind != KASF_GEOM_BOX) why = "geom_kind must be KASF_GEOM_CENTER_SCALE or KASF_GEOM_BOX";
+    else if (out_layout != KASF_LAYOUT_COCO && out_layout != KASF_LAYOUT_H36M) why = "out_layout must be KASF_LAYOUT_COCO or KASF_LAYOUT_H36M";
+    else if (geom_kind == KASF_GEOM_BOX && !(aspect > 0.0)) why = "aspect must be > 0 with KASF_GEOM_BOX";
+    return why ? kasf_set_error(2, (std::string(who) + ": " + why).c_str()) : 0;
+}
 int kasf_heatmap_keypoints(const void* hm, int32_t dtype, int64_t n, int32_t H, int32_t W, const float* geom, int32_t geom_kind, double aspect, int32_t refine,
                            int32_t out_layout, float* out, float* coco_scratch, void* stream) {
-    if (n < 0) return kasf_set_error(2, "heatmap_keypoints: n must be >= 0");
-    if (H < 1 || W < 1) return kasf_set_error(2, "heatmap_keypoints: H and W must be >= 1");
-    if ((int64_t)H * W > ((int64_t)1 << 24)) return kasf_set_error(2, "heatmap_keypoints: H * W must be <= 2^24 (the reference's index arithmetic is fp32)");
-    if (dtype != KASF_F32 && dtype != KASF_F16 && dtype != KASF_BF16) return kasf_set_error(2, "heatmap_keypoints: dtype must be KASF_DTYPE_F32, _F16 or _BF16");
-    if (geom_kind != KASF_GEOM_CENTER_SCALE && geom_kind != KASF_GEOM_BOX) return kasf_set_error(2, "heatmap_keypoints: geom_kind must be KASF_GEOM_CENTER_SCALE or KASF_GEOM_BOX");
-    if (out_layout != KASF_LAYOUT_COCO && out_layout != KASF_LAYOUT_H36M) return kasf_set_error(2, "heatmap_keypoints: out_layout must be KASF_LAYOUT_COCO or KASF_LAYOUT_H36M");
-    if (geom_kind == KASF_GEOM_BOX && !(aspect > 0.0)) return kasf_set_error(2, "heatmap_keypoints: aspect must be > 0 with KASF_GEOM_BOX");
+    if (heatmap_refusal("heatmap_keypoints", n, H, W, dtype, geom_kind, out_layout, aspect)) return 2;
     if (n == 0) return 0;
     if (!hm || !geom || !out || (out_layout == KASF_LAYOUT_H36M && !coco_scratch)) return kasf_set_error(2, "null pointer argument");
     const bool h36m = out_layout == KASF_LAYOUT_H36M;
@@ -1242,13 +1248,7 @@ int kasf_heatmap_flip_keypoints(const void* hm, const void* hm_flipped, int32_t 
                                 const float* geom, int32_t geom_kind, double aspect, int32_t refine, int32_t out_layout, float* out, float* coco_scratch,
                                 float* merged_out, void* stream) {
     static const int32_t coco_pairs[17] = {0, 2, 1, 4, 3, 6, 5, 8, 7, 10, 9, 12, 11, 14, 13, 16, 15};
-    if (n < 0) return kasf_set_error(2, "heatmap_flip_keypoints: n must be >= 0");
-    if (H < 1 || W < 1) return kasf_set_error(2, "heatmap_flip_keypoints: H and W must be >= 1");
-    if ((int64_t)H * W > ((int64_t)1 << 24)) return kasf_set_error(2, "heatmap_flip_keypoints: H * W must be <= 2^24 (the reference's index arithmetic is fp32)");
-    if (dtype != KASF_F32 && dtype != KASF_F16 && dtype != KASF_BF16) return kasf_set_error(2, "heatmap_flip_keypoints: dtype must be KASF_DTYPE_F32, _F16 or _BF16");
-    if (geom_kind != KASF_GEOM_CENTER_SCALE && geom_kind != KASF_GEOM_BOX) return kasf_set_error(2, "heatmap_flip_keypoints: geom_kind must be KASF_GEOM_CENTER_SCALE or KASF_GEOM_BOX");
-    if (out_layout != KASF_LAYOUT_COCO && out_layout != KASF_LAYOUT_H36M) return kasf_set_error(2, "heatmap_flip_keypoints: out_layout must be KASF_LAYOUT_COCO or KASF_LAYOUT_H36M");
-    if (geom_kind == KASF_GEOM_BOX && !(aspect > 0.0)) return kasf_set_error(2, "heatmap_flip_keypoints: aspect must be > 0 with KASF_GEOM_BOX");
+    if (heatmap_refusal("heatmap_flip_keypoints", n, H, W, dtype, geom_kind, out_layout, aspect)) return 2;
     const int32_t* pt = partner ? partner : coco_pairs;
     for (int j = 0; j < 17; ++j)
         if (pt[j] < 0 || pt[j] > 16) return kasf_set_error(2, "heatmap_flip_keypoints: partner entries must be in [0, 16]");

@@ -214,7 +214,7 @@ void kasf_launch_pose_world(hipStream_t s, const float* poses, int64_t frames, c
 void kasf_launch_heatmap_keypoints(hipStream_t s, const void* hm, int dtype, int64_t n, int H, int W, const float* geom, int geom_kind, double aspect,
                                    int refine, float* out);
 
-// ---- k_heatmap_flip.hip: the flip test in front of that decode (kasf.h, kasf_heatmap_flip_keypoints): hm and hmf [n,17,H,W] of one dtype, partner = 17 HOST ints (a
+// ---- k_heatmap.hip as well: the flip test in front of that decode (kasf.h, kasf_heatmap_flip_keypoints): hm and hmf [n,17,H,W] of one dtype, partner = 17 HOST ints (a
 // checked involution on 0..16) passed by value into the launch, merged_out [n,17,H,W] fp32 or null; everything else as kasf_launch_heatmap_keypoints ----
 void kasf_launch_heatmap_flip_keypoints(hipStream_t s, const void* hm, const void* hmf, int dtype, int64_t n, int H, int W, const int* partner, int shift,
                                         const float* geom, int geom_kind, double aspect, int refine, float* out, float* merged_out);

@@ -20,9 +20,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import _lib
-from .heatmap import _DTYPES, _NP_DTYPES
-from .pose import _stream
+from . import _args, _lib
 
 # the nine (width, height) anchor pairs of the public YOLOv3 configuration, in pixels of the network input, smallest first
 YOLOV3_ANCHORS = ((10, 13), (16, 30), (33, 23), (30, 61), (62, 45), (59, 119), (116, 90), (156, 198), (373, 326))
@@ -36,20 +34,6 @@ class DetectResult(NamedTuple):
     count: torch.Tensor        # CUDA int32 [B]: rows written for each image
     candidates: torch.Tensor   # CUDA int32 [B]: candidates that passed the threshold and the class filter, before NMS and before any cap
     index: torch.Tensor        # CUDA int32 [B, max_boxes]: candidate index of each row (position in the reference's concatenated prediction), -1 past count
-
-
-def _tensor(a, who: str, what: str) -> torch.Tensor:
-    if isinstance(a, np.ndarray):
-        if a.dtype not in _NP_DTYPES:
-            raise TypeError(f"{who}: {what} must be float32, float16 or bfloat16, got {a.dtype}")
-        return torch.from_numpy(np.ascontiguousarray(a))
-    if isinstance(a, torch.Tensor):
-        if a.dtype not in _DTYPES:
-            raise TypeError(f"{who}: {what} must be float32, float16 or bfloat16, got {a.dtype}")
-        if a.device.type not in ("cpu", "cuda"):
-            raise RuntimeError(f"{who}: {what} on unsupported device {a.device}")
-        return a.detach()
-    raise TypeError(f"{who}: {what} must be a numpy array or a torch tensor, got {type(a).__name__}")
 
 
 def _frame(value, B: int, who: str, name: str):
@@ -76,7 +60,7 @@ def check_detect_args(src, form: int, width, height, inp_dim, confidence, nms, c
                       anchors=None, masks=None, num_classes=None):
     """Everything the two calls can refuse without a device -> ``(tensors, B, grids, A, C, anchors [n_src*A*2] float32 or None, width, height)``."""
     if form == _lib.DETECT_PREDICTION:
-        t = _tensor(src, who, "prediction")
+        t = _args.as_tensor(src, who, "prediction", _args.DTYPES)
         if t.dim() != 3 or t.shape[2] < 6 or t.shape[1] < 1:
             raise ValueError(f"{who}: expected prediction [B,N,5+C] with N >= 1 and C >= 1, got {tuple(t.shape)}")
         tensors, B, grids, A, Cn, anc = [t], int(t.shape[0]), [int(t.shape[1])], 1, int(t.shape[2]) - 5, None
@@ -86,7 +70,7 @@ def check_detect_args(src, form: int, width, height, inp_dim, confidence, nms, c
             raise TypeError(f"{who}: heads must be a sequence of tensors, one per detection layer")
         if not 1 <= len(src) <= 4:
             raise ValueError(f"{who}: 1 to 4 heads, got {len(src)}")
-        tensors = [_tensor(h, who, f"heads[{k}]") for k, h in enumerate(src)]
+        tensors = [_args.as_tensor(h, who, f"heads[{k}]", _args.DTYPES) for k, h in enumerate(src)]
         if len({t.dtype for t in tensors}) != 1:
             raise TypeError(f"{who}: all heads must have one dtype, got {[str(t.dtype) for t in tensors]}")
         Cn = int(num_classes)
@@ -133,21 +117,7 @@ def check_detect_args(src, form: int, width, height, inp_dim, confidence, nms, c
 def _run(src, form, width, height, inp_dim, confidence, nms, class_id, max_boxes, max_candidates, device, who, **heads_kw) -> DetectResult:
     tensors, B, grids, A, Cn, anc, w, h = check_detect_args(src, form, width, height, inp_dim, confidence, nms, class_id, max_boxes, max_candidates, who,
                                                             **heads_kw)
-    on_gpu = [t.device for t in tensors + [w, h] if t.is_cuda]
-    if device is not None:
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"{who}: device must be a GPU, got {dev}; kasportsformer_amd has no CPU path")
-    elif on_gpu:
-        dev = on_gpu[0]
-    elif torch.cuda.is_available():
-        dev = torch.device("cuda", torch.cuda.current_device())
-    else:
-        raise RuntimeError(f"{who}: no GPU available; kasportsformer_amd has no CPU path")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if any(d != dev for d in on_gpu):
-        raise RuntimeError(f"{who}: input on {[str(d) for d in on_gpu]}, asked for {dev}")
+    dev = _args.resolve_device(tensors + [w, h], device, who)
     max_boxes, max_candidates = int(max_boxes), int(max_candidates)
     tensors = [t.to(dev).contiguous() for t in tensors]          # the same tensor when it is on the device and contiguous
     frame_wh = torch.stack((w.to(dev), h.to(dev)), dim=1).contiguous()
@@ -165,9 +135,9 @@ def _run(src, form, width, height, inp_dim, confidence, nms, class_id, max_boxes
         grid = (C.c_int32 * len(grids))(*grids)
         anchors = anc.ctypes.data_as(C.POINTER(C.c_float)) if anc is not None else None
         with torch.cuda.device(dev):
-            _lib.check(lib.kasf_detect_boxes(ptrs, len(tensors), form, _DTYPES[tensors[0].dtype], B, grid, A, Cn, anchors, int(inp_dim), frame_wh.data_ptr(),
+            _lib.check(lib.kasf_detect_boxes(ptrs, len(tensors), form, _args.DTYPES[tensors[0].dtype], B, grid, A, Cn, anchors, int(inp_dim), frame_wh.data_ptr(),
                                              float(confidence), float(nms), int(class_id), max_candidates, max_boxes, boxes.data_ptr(), index.data_ptr(),
-                                             count.data_ptr(), ws.data_ptr(), nbytes, _stream()))
+                                             count.data_ptr(), ws.data_ptr(), nbytes, _args.stream()))
     return DetectResult(boxes, count[:, 0], count[:, 1], index)
 
 

@@ -25,9 +25,9 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _lib
-from .pose import _stream
-from .yuv import MATRICES, MAX_SIDE, _bytes, _device, _step
+from . import _args, _lib
+from ._args import pitched, step
+from .yuv import MATRICES
 
 # the 16 bones of the H36M tree as (child, parent) joint pairs: the model's own bone table (csrc/k_misc.hip, model/KASportsFormer.py:46-47)
 H36M_SEGMENTS = tuple(zip((0, 1, 2, 0, 4, 5, 0, 7, 8, 9, 8, 11, 12, 8, 14, 15), range(1, 17)))
@@ -88,21 +88,6 @@ def _color3(v, who: str, name: str):
     return (C.c_uint8 * 3)(*(int(x) for x in a))
 
 
-def _int_in(v, lo: int, hi: int, who: str, name: str) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise TypeError(f"{who}: {name} must be an int, got {type(v).__name__}")
-    if not lo <= v <= hi:
-        raise ValueError(f"{who}: {name} must be in [{lo}, {hi}], got {v}")
-    return int(v)
-
-
-def _pitched(t: torch.Tensor, inner: int) -> bool:
-    """Can the kernel address t [F,rows,cols,inner] through a row and a frame stride: a row's bytes contiguous, rows and frames not overlapping?"""
-    rows, cols = int(t.shape[1]), int(t.shape[2])
-    return (t.stride(3) == 1 and (cols == 1 or t.stride(2) == inner) and (rows == 1 or t.stride(1) >= cols * inner) and
-            (t.shape[0] == 1 or t.stride(0) >= rows * _step(t, 1, cols * inner)))
-
-
 def _out_plane(t, shape, who: str, name: str) -> torch.Tensor:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{who}: {name} must be a torch tensor, got {type(t).__name__}")
@@ -119,9 +104,7 @@ def check_draw_args(frame, keypoints, valid, segments, colors, dot_color, thickn
     """Everything ``draw_poses`` can refuse without a device -> a dict of checked pieces (tensors where they are, tables as numpy or CUDA tensors)."""
     if matrix not in MATRICES:
         raise ValueError(f"{who}: matrix must be 'bt601' or 'bt709', got {matrix!r}")
-    fr = _bytes(frame, who, "frame")
-    if fr.dim() not in (3, 4) or fr.shape[-1] != 3 or not 1 <= fr.shape[-2] <= MAX_SIDE or not 1 <= fr.shape[-3] <= MAX_SIDE or (fr.dim() == 4 and fr.shape[0] < 1):
-        raise ValueError(f"{who}: expected frame [Hf,Wf,3] or [F,Hf,Wf,3] with F >= 1 and Hf, Wf in [1, {MAX_SIDE}], got {tuple(fr.shape)}")
+    fr = _args.frames(frame, who)
     batched = fr.dim() == 4
     lead = tuple(fr.shape[:-3])
     Hf, Wf = int(fr.shape[-3]), int(fr.shape[-2])
@@ -164,8 +147,7 @@ def check_draw_args(frame, keypoints, valid, segments, colors, dot_color, thickn
     o = None
     if out is not None and out is not False:
         o = _out_plane(out, lead + (Hf, Wf, 3), who, "out")
-        o4 = o if batched else o[None]
-        if not _pitched(o4, 3):
+        if not pitched(o if batched else o[None], 3):
             raise ValueError(f"{who}: out is written in place: its innermost two dimensions must be contiguous, its rows at least 3 * Wf bytes apart and its frames "
                              f"must not overlap, got strides {tuple(o.stride())}")
     sy = suv = None
@@ -175,8 +157,7 @@ def check_draw_args(frame, keypoints, valid, segments, colors, dot_color, thickn
             raise ValueError(f"{who}: surface must be True, False or the pair (y, uv)")
         sy = _out_plane(surface[0], lead + (Hf, Wf), who, "surface y")
         suv = _out_plane(surface[1], lead + (ch, cw, 2), who, "surface uv")
-        y4, uv4 = (sy if batched else sy[None])[..., None], suv if batched else suv[None]
-        if not _pitched(y4, 1) or not _pitched(uv4, 2):
+        if not pitched(sy if batched else sy[None], 1) or not pitched(suv if batched else suv[None], 2):
             raise ValueError(f"{who}: the surface is written in place: each plane's rows must be contiguous and at least a row apart, its frames must not overlap, "
                              f"got strides {tuple(sy.stride())} and {tuple(suv.stride())}")
     elif not isinstance(surface, (bool, np.bool_)):
@@ -184,8 +165,8 @@ def check_draw_args(frame, keypoints, valid, segments, colors, dot_color, thickn
     if out is False and not surface:
         raise ValueError(f"{who}: out=False leaves nothing to write without surface=True or surface=(y, uv)")
     return dict(frame=fr if batched else fr[None], kp=None if kp is None else (kp if batched else kp[None]), valid=None if va is None else (va if batched else va[None]),
-                seg=seg, col=col, fills=fl, dot=_color3(dot_color, who, "dot_color"), t=_int_in(thickness, 1, _lib.DRAW_MAX_THICKNESS, who, "thickness"),
-                r=_int_in(dot_radius, 0, _lib.DRAW_MAX_RADIUS, who, "dot_radius"), min_score=float("nan") if min_score is None else float(min_score),
+                seg=seg, col=col, fills=fl, dot=_color3(dot_color, who, "dot_color"), t=_args.index_in(thickness, who, "thickness", 1, _lib.DRAW_MAX_THICKNESS),
+                r=_args.index_in(dot_radius, who, "dot_radius", 0, _lib.DRAW_MAX_RADIUS), min_score=float("nan") if min_score is None else float(min_score),
                 out=None if o is None else (o if batched else o[None]), want_out=out is not False,
                 y=None if sy is None else (sy if batched else sy[None]), uv=None if suv is None else (suv if batched else suv[None]), want_surface=bool(surface),
                 matrix=MATRICES[matrix], batched=batched)
@@ -212,10 +193,10 @@ def draw_poses(frame, keypoints, valid=None, *, segments=None, colors=None, dot_
     Exception types as ``yuv_to_bgr``; every refusal comes before any launch."""
     who = "draw_poses"
     a = check_draw_args(frame, keypoints, valid, segments, colors, dot_color, thickness, dot_radius, min_score, fills, out, surface, matrix, who)
-    dev = _device((a["frame"], a["kp"], a["valid"], a["out"], a["y"], a["uv"]) + tuple(t for t in (a["seg"], a["col"], a["fills"]) if isinstance(t, torch.Tensor)),
-                  device, who)
+    tables = tuple(t for t in (a["seg"], a["col"], a["fills"]) if isinstance(t, torch.Tensor))
+    dev = _args.resolve_device((a["frame"], a["kp"], a["valid"], a["out"], a["y"], a["uv"]) + tables, device, who)
     fr = a["frame"].to(dev)
-    if not _pitched(fr, 3):
+    if not pitched(fr, 3):
         fr = fr.contiguous()
     res = paint(fr, None if a["kp"] is None else a["kp"].to(dev, torch.float32), None if a["valid"] is None else a["valid"].to(dev), a, bool(full_range), bool(rgb))
     if not a["batched"]:
@@ -242,13 +223,13 @@ def paint(fr: torch.Tensor, kp, valid, a: dict, full_range: bool, rgb: bool) -> 
     fs = (lambda t: int(t.stride(0)) if F > 1 else 0)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().kasf_draw_poses(
-            fr.data_ptr(), F, Hf, Wf, _step(fr, 1, 3 * Wf), fs(fr),
+            fr.data_ptr(), F, Hf, Wf, step(fr, 1, 3 * Wf), fs(fr),
             None if kp is None or P == 0 else kp.data_ptr(), P, J, Cc, *((0, 0, 0, 0) if kp is None else (int(s) for s in kp.stride())),
             None if valid is None or P == 0 else valid.data_ptr(), *((0, 0) if valid is None else (int(s) for s in valid.stride())),
             seg.data_ptr() if S else None, col.data_ptr() if S else None, S, a["dot"], a["t"], a["r"], a["min_score"], fl.data_ptr() if R else None, R,
-            None if out is None else out.data_ptr(), 0 if out is None else _step(out, 1, 3 * Wf), 0 if out is None else fs(out),
-            None if y is None else y.data_ptr(), None if uv is None else uv.data_ptr(), 0 if y is None else _step(y, 1, Wf), 0 if uv is None else _step(uv, 1, 2 * cw),
-            0 if y is None else fs(y), 0 if uv is None else fs(uv), a["matrix"], int(full_range), int(rgb), _stream()))
+            None if out is None else out.data_ptr(), 0 if out is None else step(out, 1, 3 * Wf), 0 if out is None else fs(out),
+            None if y is None else y.data_ptr(), None if uv is None else uv.data_ptr(), 0 if y is None else step(y, 1, Wf), 0 if uv is None else step(uv, 1, 2 * cw),
+            0 if y is None else fs(y), 0 if uv is None else fs(uv), a["matrix"], int(full_range), int(rgb), _args.stream()))
     return DrawResult(out, y, uv)
 
 
@@ -257,9 +238,9 @@ def bgr_to_nv12(frame, *, surface=True, matrix: str = "bt601", full_range: bool 
     given as ``surface`` (views into an encoder's pitched surface).  The inverse of ``yuv_to_bgr(y, uv)`` with the same ``matrix`` / ``full_range`` / ``rgb``:
     one chroma sample per 2 x 2 quad from the quad's mean.  ``kasf_bgr_to_nv12``: the ``draw_poses`` launch with nothing to paint."""
     a = check_draw_args(frame, None, None, (), (), (0, 0, 0), 1, 0, None, None, False, surface, matrix, "bgr_to_nv12")
-    dev = _device((a["frame"], a["y"], a["uv"]), device, "bgr_to_nv12")
+    dev = _args.resolve_device((a["frame"], a["y"], a["uv"]), device, "bgr_to_nv12")
     fr = a["frame"].to(dev)
-    if not _pitched(fr, 3):
+    if not pitched(fr, 3):
         fr = fr.contiguous()
     F, Hf, Wf = (int(s) for s in fr.shape[:3])
     y, uv = a["y"], a["uv"]
@@ -268,8 +249,8 @@ def bgr_to_nv12(frame, *, surface=True, matrix: str = "bt601", full_range: bool 
         uv = torch.empty((F, (Hf + 1) // 2, (Wf + 1) // 2, 2), dtype=torch.uint8, device=dev)
     fs = (lambda t: int(t.stride(0)) if F > 1 else 0)
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().kasf_bgr_to_nv12(fr.data_ptr(), F, Hf, Wf, _step(fr, 1, 3 * Wf), fs(fr), y.data_ptr(), uv.data_ptr(), _step(y, 1, Wf),
-                                                _step(uv, 1, 2 * ((Wf + 1) // 2)), fs(y), fs(uv), a["matrix"], int(full_range), int(rgb), _stream()))
+        _lib.check(_lib.load().kasf_bgr_to_nv12(fr.data_ptr(), F, Hf, Wf, step(fr, 1, 3 * Wf), fs(fr), y.data_ptr(), uv.data_ptr(), step(y, 1, Wf),
+                                                step(uv, 1, 2 * ((Wf + 1) // 2)), fs(y), fs(uv), a["matrix"], int(full_range), int(rgb), _args.stream()))
     if a["y"] is not None:
         return surface[0], surface[1]
     return (y, uv) if a["batched"] else (y[0], uv[0])
@@ -307,9 +288,9 @@ def poses_to_panel(world, rect, elev: float = 5.0, azim: float = 5.0, radius: fl
         raise TypeError(f"{who}: world must be floating point, got {world.dtype}")
     if world.dim() < 2 or tuple(world.shape[-2:]) != (17, 3):
         raise ValueError(f"{who}: expected world [...,17,3], got {tuple(world.shape)}")
-    dev = _device((world.detach(),), device, who)
+    dev = _args.resolve_device((world.detach(),), device, who)
     w = world.detach().to(dev, torch.float32).contiguous()
     out = torch.empty(tuple(w.shape[:-1]) + (2,), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().kasf_pose_panel(w.data_ptr(), w.numel() // 51, view.ctypes.data_as(C.POINTER(C.c_float)), out.data_ptr(), _stream()))
+        _lib.check(_lib.load().kasf_pose_panel(w.data_ptr(), w.numel() // 51, view.ctypes.data_as(C.POINTER(C.c_float)), out.data_ptr(), _args.stream()))
     return out

@@ -12,16 +12,11 @@ GPU only: there is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 
 import numpy as np
 import torch
 
-from . import _lib
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from . import _args, _lib
 
 
 def _poses(x: torch.Tensor, what: str) -> torch.Tensor:
@@ -37,7 +32,7 @@ def joint_flip(joint_data: torch.Tensor, deep_copy: bool = True) -> torch.Tensor
     into ``joint_data`` (the reference's in-place mode) and returns it."""
     src = _poses(joint_data, "joint_flip")
     out = torch.empty_like(src)
-    _lib.check(_lib.load().kasf_joint_flip(src.data_ptr(), out.data_ptr(), src.numel() // 51, _stream()))
+    _lib.check(_lib.load().kasf_joint_flip(src.data_ptr(), out.data_ptr(), src.numel() // 51, _args.stream()))
     if not deep_copy:
         joint_data.copy_(out)
         return joint_data
@@ -54,18 +49,18 @@ def predict_flip_tta(model, joint_input: torch.Tensor, flip: bool = True) -> tor
         if flip:
             both = torch.empty((2 * B,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
             both[:B].copy_(x)
-            _lib.check(lib.kasf_joint_flip(x.data_ptr(), both[B:].data_ptr(), x.numel() // 51, _stream()))
+            _lib.check(lib.kasf_joint_flip(x.data_ptr(), both[B:].data_ptr(), x.numel() // 51, _args.stream()))
             if model.training:                       # batch statistics would couple the two views: keep them separate
                 p, pf = model(both[:B]), model(both[B:])
             else:
                 pp = model(both)
                 p, pf = pp[:B], pp[B:]
             out = torch.empty_like(p)
-            _lib.check(lib.kasf_tta_merge(p.data_ptr(), pf.data_ptr(), out.data_ptr(), p.numel() // 51, _stream()))
+            _lib.check(lib.kasf_tta_merge(p.data_ptr(), pf.data_ptr(), out.data_ptr(), p.numel() // 51, _args.stream()))
         else:
             p = model(x)
             out = torch.empty_like(p)
-            _lib.check(lib.kasf_tta_merge(p.data_ptr(), None, out.data_ptr(), p.numel() // 51, _stream()))
+            _lib.check(lib.kasf_tta_merge(p.data_ptr(), None, out.data_ptr(), p.numel() // 51, _args.stream()))
     return out
 
 
@@ -92,7 +87,7 @@ def clip_metrics(pred: torch.Tensor, label_scaled: torch.Tensor, factor: torch.T
         assert action_sums.dtype == torch.float64 and action_sums.is_contiguous() and action_sums.shape[1] == _lib.EVAL_COLS
         a_ptr, s_ptr, n_act = action_ids.data_ptr(), action_sums.data_ptr(), action_sums.shape[0]
     _lib.check(_lib.load().kasf_eval_metrics(pred.data_ptr(), label_scaled.data_ptr(), factor.data_ptr(), res.data_ptr(), a_ptr, B, T, n_act,
-                                             mp.data_ptr(), pm.data_ptr(), ac.data_ptr(), jp.data_ptr(), s_ptr, _stream()))
+                                             mp.data_ptr(), pm.data_ptr(), ac.data_ptr(), jp.data_ptr(), s_ptr, _args.stream()))
     return mp, jp, ac, pm
 
 

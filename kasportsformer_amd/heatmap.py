@@ -19,11 +19,9 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import _lib
-from .pose import _float32, _stream, check_layout
+from . import _args, _lib
+from .pose import check_layout
 
-_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
-_NP_DTYPES = (np.float32, np.float16)
 MAX_MAP = 1 << 24               # H * W the entry point takes: the reference's index arithmetic is fp32
 COCO_PAIRS = ((1, 2), (3, 4), (5, 6), (7, 8), (9, 10), (11, 12), (13, 14), (15, 16))      # flip_back's matched_parts for COCO-17; joint 0 is its own partner
 
@@ -34,25 +32,10 @@ class FlipDecode(NamedTuple):
     merged: torch.Tensor
 
 
-def _heatmaps(a, who: str) -> torch.Tensor:
-    """float32 / float16 / bfloat16 heatmaps, numpy (shared, not copied) or torch, on the host or a GPU, as a detached tensor where they are."""
-    if isinstance(a, np.ndarray):
-        if a.dtype not in _NP_DTYPES:
-            raise TypeError(f"{who}: heatmaps must be float32, float16 or bfloat16, got {a.dtype}")
-        return torch.from_numpy(np.ascontiguousarray(a))
-    if isinstance(a, torch.Tensor):
-        if a.dtype not in _DTYPES:
-            raise TypeError(f"{who}: heatmaps must be float32, float16 or bfloat16, got {a.dtype}")
-        if a.device.type not in ("cpu", "cuda"):
-            raise RuntimeError(f"{who}: heatmaps on unsupported device {a.device}")
-        return a.detach()
-    raise TypeError(f"{who}: heatmaps must be a numpy array or a torch tensor, got {type(a).__name__}")
-
-
 def check_heatmap_args(heatmaps, center, scale, boxes, aspect, who: str):
     """Everything ``heatmaps_to_keypoints`` can refuse without a device -> ``(hm, geom parts, kind, aspect)``: ``hm`` [...,17,H,W] and the one or two
     geometry tensors [...,2] / [...,4], as tensors where they are."""
-    hm = _heatmaps(heatmaps, who)
+    hm = _args.as_tensor(heatmaps, who, "heatmaps", _args.DTYPES)
     if hm.dim() < 3 or hm.shape[-3] != 17 or hm.shape[-2] < 1 or hm.shape[-1] < 1:
         raise ValueError(f"{who}: expected heatmaps [...,17,H,W] with H, W >= 1, got {tuple(hm.shape)}")
     if hm.shape[-2] * hm.shape[-1] > MAX_MAP:
@@ -63,7 +46,7 @@ def check_heatmap_args(heatmaps, center, scale, boxes, aspect, who: str):
             raise ValueError(f"{who}: give center and scale [...,2], or boxes [...,4] with aspect")
         if aspect is not None:
             raise ValueError(f"{who}: aspect goes with boxes, not with center / scale")
-        parts = (_float32(center, who, "center"), _float32(scale, who, "scale"))
+        parts = (_args.as_tensor(center, who, "center", _args.FLOAT32), _args.as_tensor(scale, who, "scale", _args.FLOAT32))
         for name, t in zip(("center", "scale"), parts):
             if tuple(t.shape) != lead + (2,):
                 raise ValueError(f"{who}: expected {name} {list(lead) + [2]} for heatmaps {tuple(hm.shape)}, got {tuple(t.shape)}")
@@ -75,7 +58,7 @@ def check_heatmap_args(heatmaps, center, scale, boxes, aspect, who: str):
     aspect = float(aspect)
     if not aspect > 0.0 or not np.isfinite(aspect):
         raise ValueError(f"{who}: aspect must be a positive finite number, got {aspect!r}")
-    parts = (_float32(boxes, who, "boxes"),)
+    parts = (_args.as_tensor(boxes, who, "boxes", _args.FLOAT32),)
     if tuple(parts[0].shape) != lead + (4,):
         raise ValueError(f"{who}: expected boxes {list(lead) + [4]} for heatmaps {tuple(hm.shape)}, got {tuple(parts[0].shape)}")
     return hm, parts, _lib.GEOM_BOX, aspect
@@ -112,7 +95,7 @@ def check_flip_args(hm: torch.Tensor, flipped, shift, pairs, who: str):
         if shift is not True or pairs is not None:
             raise ValueError(f"{who}: shift and pairs go with flipped=")
         return None
-    hmf = _heatmaps(flipped, who)
+    hmf = _args.as_tensor(flipped, who, "heatmaps", _args.DTYPES)
     if tuple(hmf.shape) != tuple(hm.shape) or hmf.dtype != hm.dtype:
         raise ValueError(f"{who}: flipped must have the heatmaps' shape and dtype, {tuple(hm.shape)} {hm.dtype}, got {tuple(hmf.shape)} {hmf.dtype}")
     if not isinstance(shift, (bool, np.bool_)):
@@ -178,21 +161,7 @@ def heatmaps_to_keypoints(heatmaps, center=None, scale=None, *, boxes=None, aspe
     flip = check_flip_args(hm, flipped, shift, pairs, who)
     merged = _check_merged(merged, hm, flip, who)
     extra = ((flip[0],) if flip is not None else ()) + ((merged,) if isinstance(merged, torch.Tensor) else ())
-    on_gpu = [t.device for t in (hm,) + parts + extra if t.is_cuda]
-    if device is not None:
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"{who}: device must be a GPU, got {dev}; kasportsformer_amd has no CPU path")
-    elif on_gpu:
-        dev = on_gpu[0]
-    elif torch.cuda.is_available():
-        dev = torch.device("cuda", torch.cuda.current_device())
-    else:
-        raise RuntimeError(f"{who}: no GPU available; kasportsformer_amd has no CPU path")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if any(d != dev for d in on_gpu):
-        raise RuntimeError(f"{who}: input on {[str(d) for d in on_gpu]}, asked for {dev}")
+    dev = _args.resolve_device((hm,) + parts + extra, device, who)
     if flip is None:
         return decode(hm.to(dev), tuple(t.to(dev) for t in parts), kind, aspect, refine, h36m)
     if isinstance(merged, torch.Tensor) and any(t.is_cuda and t.numel() and _spans_overlap(t, merged) for t in (hm, flip[0])):
@@ -216,9 +185,9 @@ def decode(hm: torch.Tensor, parts, kind: int, aspect: float, refine: bool, h36m
         if n:
             scratch = torch.empty_like(out) if h36m else None
             with torch.cuda.device(hm.device):
-                _lib.check(_lib.load().kasf_heatmap_keypoints(hm.data_ptr(), _DTYPES[hm.dtype], n, int(H), int(W), geom.data_ptr(), kind, aspect,
+                _lib.check(_lib.load().kasf_heatmap_keypoints(hm.data_ptr(), _args.DTYPES[hm.dtype], n, int(H), int(W), geom.data_ptr(), kind, aspect,
                                                               int(bool(refine)), _lib.LAYOUT_H36M if h36m else _lib.LAYOUT_COCO, out.data_ptr(),
-                                                              scratch.data_ptr() if h36m else None, _stream()))
+                                                              scratch.data_ptr() if h36m else None, _args.stream()))
         return out
     hmf, shift, partner = flip
     partner = np.ascontiguousarray(partner, dtype=np.int32)      # host memory, read during the call
@@ -230,9 +199,9 @@ def decode(hm: torch.Tensor, parts, kind: int, aspect: float, refine: bool, h36m
     if n:
         scratch = torch.empty_like(out) if h36m else None
         with torch.cuda.device(hm.device):
-            _lib.check(_lib.load().kasf_heatmap_flip_keypoints(hm.data_ptr(), hmf.data_ptr(), _DTYPES[hm.dtype], n, int(H), int(W), partner.ctypes.data,
+            _lib.check(_lib.load().kasf_heatmap_flip_keypoints(hm.data_ptr(), hmf.data_ptr(), _args.DTYPES[hm.dtype], n, int(H), int(W), partner.ctypes.data,
                                                                int(shift), geom.data_ptr(), kind, aspect, int(bool(refine)),
                                                                _lib.LAYOUT_H36M if h36m else _lib.LAYOUT_COCO, out.data_ptr(),
                                                                scratch.data_ptr() if h36m else None, merged.data_ptr() if merged is not None else None,
-                                                               _stream()))
+                                                               _args.stream()))
     return out if merged is None else (out, merged)

@@ -20,10 +20,7 @@ from typing import NamedTuple, Tuple
 
 import torch
 
-from . import _lib
-from .crop import _frames
-from .heatmap import _DTYPES
-from .pose import _stream
+from . import _args, _lib
 
 MAX_SIDE = _lib.LETTERBOX_MAX_SIDE      # out_w, out_h the entry point takes
 
@@ -48,7 +45,7 @@ def letterbox_plan(width: int, height: int, out_w: int, out_h: int, who: str = "
 
 def check_letterbox_args(frame, inp_dim, pad, dtype, who: str):
     """Everything ``letterbox_frames`` can refuse without a device -> ``(frames, (out_w, out_h), pad, (new_w, new_h), (pad_x, pad_y))``."""
-    fr = _frames(frame, who)
+    fr = _args.frames(frame, who)
     if isinstance(inp_dim, bool):
         raise TypeError(f"{who}: inp_dim must be an int or (width, height), got {inp_dim!r}")
     try:
@@ -60,15 +57,8 @@ def check_letterbox_args(frame, inp_dim, pad, dtype, who: str):
             raise TypeError(f"{who}: inp_dim must be an int or (width, height), got {inp_dim!r}") from None
     if not (1 <= out_w <= MAX_SIDE and 1 <= out_h <= MAX_SIDE):
         raise ValueError(f"{who}: inp_dim = (width, height) must be in [1, {MAX_SIDE}], got {inp_dim!r}")
-    if isinstance(pad, bool):
-        raise TypeError(f"{who}: pad must be an int, got {pad!r}")
-    try:
-        pad = operator.index(pad)
-    except TypeError:
-        raise TypeError(f"{who}: pad must be an int, got {type(pad).__name__}") from None
-    if not 0 <= pad <= 255:
-        raise ValueError(f"{who}: pad must be in [0, 255], got {pad}")
-    if dtype not in _DTYPES:
+    pad = _args.index_in(pad, who, "pad", 0, 255, any_index=True)
+    if dtype not in _args.DTYPES:
         raise TypeError(f"{who}: dtype must be torch.float32, torch.float16 or torch.bfloat16, got {dtype!r}")
     size, offset = letterbox_plan(int(fr.shape[-2]), int(fr.shape[-3]), out_w, out_h, who)
     return fr, (out_w, out_h), pad, size, offset
@@ -92,20 +82,7 @@ def letterbox_frames(frame, inp_dim=416, *, pad: int = 128, swap_rb: bool = True
     call raises ``RuntimeError``.  Exception types as ``crop_persons``; every refusal comes before any launch."""
     who = "letterbox_frames"
     fr, (out_w, out_h), pad, size, offset = check_letterbox_args(frame, inp_dim, pad, dtype, who)
-    if device is not None:
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"{who}: device must be a GPU, got {dev}; kasportsformer_amd has no CPU path")
-    elif fr.is_cuda:
-        dev = fr.device
-    elif torch.cuda.is_available():
-        dev = torch.device("cuda", torch.cuda.current_device())
-    else:
-        raise RuntimeError(f"{who}: no GPU available; kasportsformer_amd has no CPU path")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if fr.is_cuda and fr.device != dev:
-        raise RuntimeError(f"{who}: input on {fr.device}, asked for {dev}")
+    dev = _args.resolve_device((fr,), device, who)
     inputs = letterbox(fr.to(dev), out_w, out_h, pad, bool(swap_rb), dtype)
     return LetterboxResult(inputs, int(fr.shape[-2]), int(fr.shape[-3]), size, offset)
 
@@ -120,6 +97,6 @@ def letterbox(fr: torch.Tensor, out_w: int, out_h: int, pad: int, swap_rb: bool,
         frame_stride = 0
     out = torch.empty((n_frames, 3, out_h, out_w), dtype=dtype, device=fr.device)
     with torch.cuda.device(fr.device):
-        _lib.check(_lib.load().kasf_letterbox_frames(fr.data_ptr(), n_frames, Hf, Wf, int(fr.stride(-3)), frame_stride, out.data_ptr(), _DTYPES[dtype], out_w,
-                                                     out_h, pad, int(swap_rb), _stream()))
+        _lib.check(_lib.load().kasf_letterbox_frames(fr.data_ptr(), n_frames, Hf, Wf, int(fr.stride(-3)), frame_stride, out.data_ptr(), _args.DTYPES[dtype], out_w,
+                                                     out_h, pad, int(swap_rb), _args.stream()))
     return out

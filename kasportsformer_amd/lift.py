@@ -25,14 +25,13 @@ the forward together (``kasf_lift_windows_ragged`` / ``kasf_lift_stitch_ragged``
 from __future__ import annotations
 
 import argparse
-import ctypes as C
 import io
 import pickle
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 from .pose import check_layout, convert_frames, poses_to_world
 
 
@@ -88,10 +87,6 @@ def ragged_plan(lengths, T: int, stride: int | None = None):
         if r is not None:
             resample[p], first_pos[p, :len(fp)] = r, fp
     return win_first, resample, first_pos
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _model_device(model, who: str = "lift_track") -> torch.device:
@@ -157,11 +152,11 @@ def lift_track(model, keypoints, width, height, *, stride=None, flip: bool = Tru
             kp4 = convert_frames(kp4)
         x = torch.empty((halves * PW, T, 17, 3), dtype=torch.float32, device=device)
         _lib.check(lib.kasf_lift_windows(kp4.data_ptr(), P, n, float(width), float(height), T, stride,
-                                         r_dev.data_ptr() if r_dev is not None else None, int(flip), x.data_ptr(), _stream()))
+                                         r_dev.data_ptr() if r_dev is not None else None, int(flip), x.data_ptr(), _args.stream()))
         pred = _forward_windows(model, x, PW, halves, int(max_windows))
         poses = torch.empty((P, n, 17, 3), dtype=torch.float32, device=device)
         _lib.check(lib.kasf_lift_stitch(pred.data_ptr(), int(flip), P, n, T, stride, fp_dev.data_ptr() if fp_dev is not None else None,
-                                        poses.data_ptr(), _stream()))
+                                        poses.data_ptr(), _args.stream()))
     return poses.view(lead + (17, 3))
 
 
@@ -280,10 +275,10 @@ def lift_tracks(model, tracks, width, height, *, stride=None, flip: bool = True,
                 packed = convert_frames(packed)
             x = torch.empty((halves * windows, T, 17, 3), dtype=torch.float32, device=device)
             _lib.check(lib.kasf_lift_windows_ragged(packed.data_ptr(), off_d.data_ptr(), wf_d.data_ptr(), P, frames, windows, w_d.data_ptr(),
-                                                    h_d.data_ptr(), T, stride, r_d.data_ptr(), int(flip), x.data_ptr(), _stream()))
+                                                    h_d.data_ptr(), T, stride, r_d.data_ptr(), int(flip), x.data_ptr(), _args.stream()))
             pred = _forward_windows(model, x, windows, halves, int(max_windows))
             _lib.check(lib.kasf_lift_stitch_ragged(pred.data_ptr(), int(flip), off_d.data_ptr(), wf_d.data_ptr(), P, frames, windows, T, stride,
-                                                   fp_d.data_ptr(), poses.data_ptr(), _stream()))
+                                                   fp_d.data_ptr(), poses.data_ptr(), _args.stream()))
     if offsets is not None:
         return poses
     return [poses[a:b] for a, b in zip(off[:-1].tolist(), off[1:].tolist())]

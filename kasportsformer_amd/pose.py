@@ -13,12 +13,10 @@ frame of zeros converts to a frame of zeros.  ``layout="coco"`` on ``lift_track`
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 LAYOUTS = ("h36m", "coco")
 # demo/demo.py:243: the camera rotation the demo views every clip with, a unit quaternion (w, x, y, z)
@@ -32,32 +30,13 @@ def check_layout(layout, who: str) -> bool:
     return layout == "coco"
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _float32(a, who: str, what: str) -> torch.Tensor:
-    """A float32 numpy array (shared, not copied) or torch tensor, on the host or a GPU, as a detached tensor where it is."""
-    if isinstance(a, np.ndarray):
-        if a.dtype != np.float32:
-            raise TypeError(f"{who}: {what} must be float32, got {a.dtype}")
-        return torch.from_numpy(np.ascontiguousarray(a))
-    if isinstance(a, torch.Tensor):
-        if a.dtype != torch.float32:
-            raise TypeError(f"{who}: {what} must be float32, got {a.dtype}")
-        if a.device.type not in ("cpu", "cuda"):
-            raise RuntimeError(f"{who}: {what} on unsupported device {a.device}")
-        return a.detach()
-    raise TypeError(f"{who}: {what} must be a numpy array or a torch tensor, got {type(a).__name__}")
-
-
 def convert_frames(frames: torch.Tensor) -> torch.Tensor:
     """``kasf_coco_h36m`` on a contiguous CUDA fp32 [...,17,3] tensor: a new tensor of its shape (what the lift surfaces call with ``layout="coco"``)."""
     out = torch.empty_like(frames)
     n = frames.numel() // 51
     if n:
         with torch.cuda.device(frames.device):
-            _lib.check(_lib.load().kasf_coco_h36m(frames.data_ptr(), n, out.data_ptr(), _stream()))
+            _lib.check(_lib.load().kasf_coco_h36m(frames.data_ptr(), n, out.data_ptr(), _args.stream()))
     return out
 
 
@@ -68,30 +47,16 @@ def coco_to_h36m(keypoints, scores=None, device=None) -> torch.Tensor:
     of zeros stays a frame of zeros (the reference drops an all-zero person).  ``device``: where host input goes (default: the current GPU); GPU input
     stays where it is.  There is no host path: without a GPU the call raises ``RuntimeError``.  Exception types as ``lift_tracks``."""
     who = "coco_to_h36m"
-    kp = _float32(keypoints, who, "keypoints")
+    kp = _args.as_tensor(keypoints, who, "keypoints", _args.FLOAT32)
     if scores is None:
         if kp.dim() < 2 or tuple(kp.shape[-2:]) != (17, 3):
             raise ValueError(f"{who}: expected keypoints [...,17,3] (or [...,17,2] with scores [...,17]), got {tuple(kp.shape)}")
         sc = None
     else:
-        sc = _float32(scores, who, "scores")
+        sc = _args.as_tensor(scores, who, "scores", _args.FLOAT32)
         if kp.dim() < 2 or tuple(kp.shape[-2:]) != (17, 2) or tuple(sc.shape) != tuple(kp.shape[:-1]):
             raise ValueError(f"{who}: expected keypoints [...,17,2] and scores [...,17], got {tuple(kp.shape)} and {tuple(sc.shape)}")
-    on_gpu = [t.device for t in (kp, sc) if t is not None and t.is_cuda]
-    if device is not None:
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"{who}: device must be a GPU, got {dev}; kasportsformer_amd has no CPU path")
-    elif on_gpu:
-        dev = on_gpu[0]
-    elif torch.cuda.is_available():
-        dev = torch.device("cuda", torch.cuda.current_device())
-    else:
-        raise RuntimeError(f"{who}: no GPU available; kasportsformer_amd has no CPU path")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if any(d != dev for d in on_gpu):
-        raise RuntimeError(f"{who}: input on {on_gpu[0]}, asked for {dev}")
+    dev = _args.resolve_device((kp, sc), device, who)
     if sc is None:
         frames = kp.to(dev).contiguous()                     # a copy when it comes from the host; on the device the kernel only reads it
     else:
@@ -131,5 +96,5 @@ def poses_to_world(poses, rotation=DEMO_CAMERA_ROTATION, translation=0.0, floor:
     if n:
         with torch.cuda.device(src.device):
             _lib.check(_lib.load().kasf_pose_world(src.data_ptr(), n, q.ctypes.data, t.ctypes.data, int(bool(floor)), int(bool(unit)), out.data_ptr(),
-                                                   _stream()))
+                                                   _args.stream()))
     return out

@@ -20,10 +20,10 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 from .heatmap import check_flip_args, check_heatmap_args, decode
 from .pose import check_layout, convert_frames
-from .lift import _as_tensor, _forward_windows, _model_device, _per_row, _stream, _upload, window_plan
+from .lift import _as_tensor, _forward_windows, _model_device, _per_row, _upload, window_plan
 
 
 def stream_tables(T: int):
@@ -117,11 +117,11 @@ class StreamLifter:
         slots_p = ids_d.data_ptr() if ids_d is not None else None
         x = torch.empty((halves * K, T, 17, 3), dtype=torch.float32, device=self.device)
         _lib.check(lib.kasf_stream_windows(self._ring.data_ptr(), self._count.data_ptr(), slots_p, K, S, T, self._width.data_ptr(),
-                                           self._height.data_ptr(), self._r_tab.data_ptr(), int(self.flip), x.data_ptr(), _stream()))
+                                           self._height.data_ptr(), self._r_tab.data_ptr(), int(self.flip), x.data_ptr(), _args.stream()))
         pred = _forward_windows(self.model, x, K, halves, K)
         out = torch.empty((K, n_out, 17, 3), dtype=torch.float32, device=self.device)
         _lib.check(lib.kasf_stream_emit(pred.data_ptr(), int(self.flip), self._count.data_ptr(), slots_p, K, S, T, self._fp_tab.data_ptr(), back, n_out,
-                                        out.data_ptr(), _stream()))
+                                        out.data_ptr(), _args.stream()))
         return out
 
     def push(self, keypoints, slots=None) -> torch.Tensor:
@@ -141,7 +141,7 @@ class StreamLifter:
             if self._coco:
                 frames = convert_frames(frames)
             _lib.check(self._lib.kasf_stream_push(frames.data_ptr(), ids_d.data_ptr() if ids_d is not None else None, K, self.slots, self.T,
-                                                  self._ring.data_ptr(), self._count.data_ptr(), _stream()))
+                                                  self._ring.data_ptr(), self._count.data_ptr(), _args.stream()))
             if ids is None:
                 self._counts += 1
             else:

@@ -20,8 +20,8 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import _lib
-from .pose import _float32, _stream
+from . import _args, _lib
+from ._args import index_in
 
 MAX_SLOTS = MAX_DETS = _lib.SORT_MAX        # a track and a detection each take one lane of a wavefront
 MAX_STREAMS, MAX_PERSONS = 65535, 65535
@@ -53,21 +53,13 @@ class TrackState(NamedTuple):
     ticks: torch.Tensor          # CUDA int32 [B]: the reference's frame_count
 
 
-def _int(value, who: str, name: str, lo: int, hi: int) -> int:
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
-        raise TypeError(f"{who}: {name} must be an integer, got {type(value).__name__}")
-    if not lo <= int(value) <= hi:
-        raise ValueError(f"{who}: {name} must be in [{lo}, {hi}], got {value}")
-    return int(value)
-
-
 def check_tracker_args(streams, slots, max_age, min_hits, iou_threshold, num_person, who: str = "SortTracker"):
     """Everything the constructor can refuse without a device."""
-    streams = _int(streams, who, "streams", 1, MAX_STREAMS)
-    slots = _int(slots, who, "slots", 1, MAX_SLOTS)
-    max_age = _int(max_age, who, "max_age", 0, 2 ** 31 - 1)
-    min_hits = _int(min_hits, who, "min_hits", 0, 2 ** 31 - 1)
-    num_person = _int(num_person, who, "num_person", 1, MAX_PERSONS)
+    streams = index_in(streams, who, "streams", 1, MAX_STREAMS)
+    slots = index_in(slots, who, "slots", 1, MAX_SLOTS)
+    max_age = index_in(max_age, who, "max_age", 0, 2 ** 31 - 1)
+    min_hits = index_in(min_hits, who, "min_hits", 0, 2 ** 31 - 1)
+    num_person = index_in(num_person, who, "num_person", 1, MAX_PERSONS)
     try:
         iou_threshold = float(iou_threshold)
     except (TypeError, ValueError):
@@ -79,7 +71,7 @@ def check_tracker_args(streams, slots, max_age, min_hits, iou_threshold, num_per
 
 def check_update_args(boxes, count, streams: int, who: str = "SortTracker.update"):
     """Everything ``update`` can refuse without a device -> ``(boxes [B,n,>=4] float32 tensor where it is, count [B] int32 tensor or None)``."""
-    t = _float32(boxes, who, "boxes")
+    t = _args.as_tensor(boxes, who, "boxes", _args.FLOAT32)
     if t.dim() == 2:
         t = t[None]
     if t.dim() != 3 or t.shape[2] < 4:
@@ -128,17 +120,7 @@ class SortTracker:
         (self.streams, self.slots, self.max_age, self.min_hits, self.iou_threshold, self.num_person) = check_tracker_args(
             streams, slots, max_age, min_hits, iou_threshold, num_person, who)
         self.hold_last = bool(hold_last)
-        if device is not None:
-            dev = torch.device(device)
-            if dev.type != "cuda":
-                raise RuntimeError(f"{who}: device must be a GPU, got {dev}; kasportsformer_amd has no CPU path")
-        elif torch.cuda.is_available():
-            dev = torch.device("cuda", torch.cuda.current_device())
-        else:
-            raise RuntimeError(f"{who}: no GPU available; kasportsformer_amd has no CPU path")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device = dev
+        self.device = dev = _args.resolve_device((), device, who)
         nbytes = _lib.load().kasf_sort_state_bytes(self.streams, self.slots, MAX_DETS)
         if nbytes < 0:
             _lib.check(2)
@@ -187,7 +169,7 @@ class SortTracker:
                 self._state.data_ptr(), B, S, MAX_DETS, t.data_ptr() if n else None, n, int(t.stride(0)) if n else 0, int(t.stride(1)) if n else 4,
                 None if c is None else c.data_ptr(), self.max_age, self.min_hits, self.iou_threshold, NP, int(self.hold_last), out_boxes.data_ptr(),
                 ints[0].data_ptr(), ints[1].data_ptr(), ints[2].data_ptr(), per[0].data_ptr(), per[1].data_ptr(), persons.data_ptr(), per[2].data_ptr(),
-                _stream()))
+                _args.stream()))
         return TrackResult(out_boxes, ints[0], ints[1], ints[2], per[0], per[1], persons, per[2])
 
     def state(self) -> TrackState:

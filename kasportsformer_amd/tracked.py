@@ -32,12 +32,13 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
+from ._args import index_in
 from .heatmap import check_flip_args, check_heatmap_args
-from .lift import _as_tensor, _forward_windows, _model_device, _per_row, _stream, _upload
+from .lift import _as_tensor, _forward_windows, _model_device, _per_row, _upload
 from .pose import check_layout, convert_frames
 from .stream import _checked_tables, _decode_on
-from .track import MAX_PERSONS, MAX_SLOTS, MAX_STREAMS, _int
+from .track import MAX_PERSONS, MAX_SLOTS, MAX_STREAMS
 
 ROWS = ("persons", "tracks")
 
@@ -58,10 +59,10 @@ def check_tracked_args(T, width, height, streams, track_slots, rows, num_person,
     T = int(T)
     if T < 1:
         raise ValueError(f"{who}: the model's n_frames must be >= 1, got {T}")
-    streams = _int(streams, who, "streams", 1, MAX_STREAMS)
-    track_slots = _int(track_slots, who, "track_slots", 1, MAX_SLOTS)
-    num_person = _int(num_person, who, "num_person", 1, MAX_PERSONS)
-    lag = _int(lag, who, "lag", 0, T - 1)
+    streams = index_in(streams, who, "streams", 1, MAX_STREAMS)
+    track_slots = index_in(track_slots, who, "track_slots", 1, MAX_SLOTS)
+    num_person = index_in(num_person, who, "num_person", 1, MAX_PERSONS)
+    lag = index_in(lag, who, "lag", 0, T - 1)
     w32, h32 = _per_row(width, streams, "width", who, "stream"), _per_row(height, streams, "height", who, "stream")
     R = num_person if rows == "persons" else track_slots
     return T, w32, h32, streams, track_slots, (_lib.ROWS_PERSONS if rows == "persons" else _lib.ROWS_TRACKS), R, lag, coco
@@ -161,7 +162,7 @@ class TrackedLifter:
             _lib.check(lib.kasf_stream_track_front(frames.data_ptr(), ids.data_ptr(), slot.data_ptr(), born.data_ptr(), count_b.data_ptr(), B, self.track_slots,
                                                    self._rows_mode, R, T, self._ring.data_ptr(), self._count.data_ptr(), self._owner.data_ptr(),
                                                    self._width.data_ptr(), self._height.data_ptr(), self._r_tab.data_ptr(), int(self.flip), x.data_ptr(),
-                                                   row_slot.data_ptr(), _stream()))
+                                                   row_slot.data_ptr(), _args.stream()))
             pred = _forward_windows(self.model, x, n, halves, n)
             poses = torch.empty((B, R, 17, 3), dtype=torch.float32, device=dev)
             valid = torch.empty((B, R), dtype=torch.bool, device=dev)
@@ -169,7 +170,7 @@ class TrackedLifter:
             frames_out = torch.empty((B, R), dtype=torch.int64, device=dev)
             _lib.check(lib.kasf_stream_track_emit(pred.data_ptr(), int(self.flip), self._count.data_ptr(), self._owner.data_ptr(), row_slot.data_ptr(), n, T,
                                                   self._fp_tab.data_ptr(), self.lag, poses.data_ptr(), valid.data_ptr(), ids_out.data_ptr(),
-                                                  frames_out.data_ptr(), _stream()))
+                                                  frames_out.data_ptr(), _args.stream()))
         return TrackedTick(poses, valid, ids_out, frames_out)
 
     def push_heatmaps(self, heatmaps, center=None, scale=None, track=None, *, boxes=None, aspect=None, refine: bool = True, flipped=None,

@@ -16,32 +16,14 @@ here: equality with a particular cv2 / FFmpeg build is NOT verified.
 """
 from __future__ import annotations
 
-import operator
-
-import numpy as np
 import torch
 
-from . import _lib
-from .pose import _stream
+from . import _args, _lib
+from ._args import pitched, step
 
-MAX_SIDE = 32767                # Hf, Wf the entry point takes
+MAX_SIDE = _args.MAX_SIDE       # Hf, Wf the entry point takes
 LAYOUTS = {"nv12": _lib.YUV_NV12, "i420": _lib.YUV_I420}
 MATRICES = {"bt601": _lib.YUV_BT601, "bt709": _lib.YUV_BT709}
-
-
-def _bytes(a, who: str, name: str) -> torch.Tensor:
-    """A uint8 array, numpy (shared, not copied) or torch, on the host or a GPU, as a detached tensor where it is."""
-    if isinstance(a, np.ndarray):
-        if a.dtype != np.uint8:
-            raise TypeError(f"{who}: {name} must be uint8, got {a.dtype}")
-        return torch.from_numpy(a if all(s >= 0 for s in a.strides) else np.ascontiguousarray(a))     # a padded pitch is kept
-    if isinstance(a, torch.Tensor):
-        if a.dtype != torch.uint8:
-            raise TypeError(f"{who}: {name} must be uint8, got {a.dtype}")
-        if a.device.type not in ("cpu", "cuda"):
-            raise RuntimeError(f"{who}: {name} on unsupported device {a.device}")
-        return a.detach()
-    raise TypeError(f"{who}: {name} must be a numpy array or a torch tensor, got {type(a).__name__}")
 
 
 def check_yuv_args(y, u_or_uv, v, layout, matrix, out, who: str):
@@ -56,8 +38,8 @@ def check_yuv_args(y, u_or_uv, v, layout, matrix, out, who: str):
         raise ValueError(f"{who}: layout 'nv12' takes the interleaved UV plane alone, not a separate v")
     if not nv12 and v is None:
         raise ValueError(f"{who}: layout 'i420' takes the U plane and the V plane")
-    yt = _bytes(y, who, "y")
-    planes = [_bytes(u_or_uv, who, "uv" if nv12 else "u")] + ([] if nv12 else [_bytes(v, who, "v")])
+    named = ((y, "y"), (u_or_uv, "uv")) if nv12 else ((y, "y"), (u_or_uv, "u"), (v, "v"))
+    yt, *planes = (_args.as_tensor(p, who, name, _args.UINT8, keep_pitch=True) for p, name in named)
     if yt.dim() not in (2, 3) or not 1 <= yt.shape[-1] <= MAX_SIDE or not 1 <= yt.shape[-2] <= MAX_SIDE or (yt.dim() == 3 and yt.shape[0] < 1):
         raise ValueError(f"{who}: expected y [Hf,Wf] or [F,Hf,Wf] with F >= 1 and Hf, Wf in [1, {MAX_SIDE}], got {tuple(yt.shape)}")
     batched = yt.dim() == 3
@@ -76,49 +58,13 @@ def check_yuv_args(y, u_or_uv, v, layout, matrix, out, who: str):
             raise ValueError(f"{who}: y {tuple(yt.shape)} goes with out {lead + (Hf, Wf, 3)}, got {tuple(out.shape)}")
         if not out.is_cuda:
             raise RuntimeError(f"{who}: out must be on a GPU, got {out.device}; kasportsformer_amd has no CPU path")
-        if (out.stride(-1) != 1 or (Wf > 1 and out.stride(-2) != 3) or (Hf > 1 and out.stride(-3) < 3 * Wf) or
-                (batched and out.shape[0] > 1 and out.stride(0) < Hf * _step(out, -3, 3 * Wf))):
+        if not pitched(out if batched else out[None], 3):
             raise ValueError(f"{who}: out is written in place: its innermost two dimensions must be contiguous, its rows at least 3 * Wf bytes apart and its "
                              f"frames must not overlap, got strides {tuple(out.stride())}")
         out = out.detach()
     if not batched:
         yt, planes, out = yt[None], [p[None] for p in planes], None if out is None else out[None]
     return yt, planes[0], None if nv12 else planes[1], LAYOUTS[layout], MATRICES[matrix], out, batched
-
-
-def _step(p: torch.Tensor, dim: int, least: int) -> int:
-    """The stride of dimension dim in bytes; a dimension of one element has no stride to speak of, so the least legal one stands in for it."""
-    return int(p.stride(dim)) if p.shape[dim] > 1 else max(int(p.stride(dim)), least)
-
-
-def _in_place(p: torch.Tensor, inner: int) -> bool:
-    """Can the kernel read plane p [F,rows,cols] (inner = 1) or [F,rows,cols,2] (inner = 2) through its strides: a row's bytes contiguous, rows and frames
-    not overlapping?  (Dimensions of one element are not looked at.)"""
-    if inner == 2 and p.stride(-1) != 1:
-        return False
-    col, row = (-1, -2) if inner == 1 else (-2, -3)
-    row_bytes = int(p.shape[col]) * inner
-    return ((p.shape[col] == 1 or p.stride(col) == inner) and (p.shape[row] == 1 or p.stride(row) >= row_bytes) and
-            (p.shape[0] == 1 or p.stride(0) >= int(p.shape[row]) * _step(p, row, row_bytes)))
-
-
-def _device(tensors, device, who: str) -> torch.device:
-    on_gpu = [t.device for t in tensors if t is not None and t.is_cuda]
-    if device is not None:
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"{who}: device must be a GPU, got {dev}; kasportsformer_amd has no CPU path")
-    elif on_gpu:
-        dev = on_gpu[0]
-    elif torch.cuda.is_available():
-        dev = torch.device("cuda", torch.cuda.current_device())
-    else:
-        raise RuntimeError(f"{who}: no GPU available; kasportsformer_amd has no CPU path")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if any(d != dev for d in on_gpu):
-        raise RuntimeError(f"{who}: input or out on {sorted({str(d) for d in on_gpu})}, asked for {dev}")
-    return dev
 
 
 def yuv_to_bgr(y, u_or_uv, v=None, *, layout: str = "nv12", matrix: str = "bt601", full_range: bool = False, rgb: bool = False, out=None,
@@ -140,7 +86,7 @@ def yuv_to_bgr(y, u_or_uv, v=None, *, layout: str = "nv12", matrix: str = "bt601
     raises ``RuntimeError``.  Exception types as ``crop_persons``; every refusal comes before any launch."""
     who = "yuv_to_bgr"
     yt, c0, c1, lay, mat, o, batched = check_yuv_args(y, u_or_uv, v, layout, matrix, out, who)
-    dev = _device((yt, c0, c1, o), device, who)
+    dev = _args.resolve_device((yt, c0, c1, o), device, who)
     res = convert(yt.to(dev), c0.to(dev), None if c1 is None else c1.to(dev), lay, mat, bool(full_range), bool(rgb), o)
     return out if out is not None else (res if batched else res[0])
 
@@ -148,47 +94,38 @@ def yuv_to_bgr(y, u_or_uv, v=None, *, layout: str = "nv12", matrix: str = "bt601
 def convert(y: torch.Tensor, c0: torch.Tensor, c1, layout: int, matrix: int, full_range: bool, rgb: bool, out) -> torch.Tensor:
     """``kasf_yuv420_to_bgr`` on checked CUDA planes of one device: y [F,Hf,Wf], c0 [F,ch,cw,2] or c0, c1 [F,ch,cw]; out [F,Hf,Wf,3] or None."""
     F, Hf, Wf = (int(s) for s in y.shape)
-    if not _in_place(y, 1):
+    if not pitched(y, 1):
         y = y.contiguous()
     if c1 is None:
-        if not _in_place(c0, 2):
+        if not pitched(c0, 2):
             c0 = c0.contiguous()
-        c_row, c_frame = _step(c0, -3, 2 * int(c0.shape[-2])), int(c0.stride(0))
+        c_row, c_frame = step(c0, -3, 2 * int(c0.shape[-2])), int(c0.stride(0))
     else:
-        if not (_in_place(c0, 1) and _in_place(c1, 1) and (c0.shape[-2] == 1 or c0.stride(-2) == c1.stride(-2)) and (F == 1 or c0.stride(0) == c1.stride(0))):
+        if not (pitched(c0, 1) and pitched(c1, 1) and (c0.shape[-2] == 1 or c0.stride(-2) == c1.stride(-2)) and (F == 1 or c0.stride(0) == c1.stride(0))):
             c0, c1 = c0.contiguous(), c1.contiguous()                       # the entry point takes one row stride and one frame stride for both planes
-        c_row, c_frame = _step(c0, -2, int(c0.shape[-1])), int(c0.stride(0))
+        c_row, c_frame = step(c0, -2, int(c0.shape[-1])), int(c0.stride(0))
     if out is None:
         out = torch.empty((F, Hf, Wf, 3), dtype=torch.uint8, device=y.device)
     y_frame, o_frame = int(y.stride(0)), int(out.stride(0))
     if F == 1:
         y_frame = c_frame = o_frame = 0
     with torch.cuda.device(y.device):
-        _lib.check(_lib.load().kasf_yuv420_to_bgr(y.data_ptr(), c0.data_ptr(), None if c1 is None else c1.data_ptr(), layout, F, Hf, Wf, _step(y, -2, Wf),
-                                                  c_row, y_frame, c_frame, out.data_ptr(), _step(out, -3, 3 * Wf), o_frame, matrix, int(full_range), int(rgb),
-                                                  _stream()))
+        _lib.check(_lib.load().kasf_yuv420_to_bgr(y.data_ptr(), c0.data_ptr(), None if c1 is None else c1.data_ptr(), layout, F, Hf, Wf, step(y, -2, Wf),
+                                                  c_row, y_frame, c_frame, out.data_ptr(), step(out, -3, 3 * Wf), o_frame, matrix, int(full_range), int(rgb),
+                                                  _args.stream()))
     return out
-
-
-def _index(v, who: str, name: str) -> int:
-    if isinstance(v, bool):
-        raise TypeError(f"{who}: {name} must be an int, got {v!r}")
-    try:
-        return operator.index(v)
-    except TypeError:
-        raise TypeError(f"{who}: {name} must be an int, got {type(v).__name__}") from None
 
 
 def surface_planes(surface, height, width, chroma_row, layout: str, who: str):
     """The planes inside a decoder's single allocation, as views (no device needed): ``surface`` uint8 [rows, pitch] or [F, rows, pitch] -> ``(y, uv)`` for
     "nv12", ``(y, u, v)`` for "i420"."""
-    s = _bytes(surface, who, "surface")
+    s = _args.as_tensor(surface, who, "surface", _args.UINT8, keep_pitch=True)
     if s.dim() not in (2, 3) or s.shape[-1] < 1 or s.shape[-2] < 1 or (s.dim() == 3 and s.shape[0] < 1):
         raise ValueError(f"{who}: expected surface [rows, pitch] or [F, rows, pitch], got {tuple(s.shape)}")
     rows, pitch = int(s.shape[-2]), int(s.shape[-1])
-    Hf = rows * 2 // 3 if height is None else _index(height, who, "height")
-    Wf = pitch if width is None else _index(width, who, "width")
-    cr = Hf if chroma_row is None else _index(chroma_row, who, "chroma_row")
+    Hf = rows * 2 // 3 if height is None else _args.index_in(height, who, "height", any_index=True)
+    Wf = pitch if width is None else _args.index_in(width, who, "width", any_index=True)
+    cr = Hf if chroma_row is None else _args.index_in(chroma_row, who, "chroma_row", any_index=True)
     ch, cw = (Hf + 1) // 2, (Wf + 1) // 2
     if not (1 <= Hf <= MAX_SIDE and 1 <= Wf <= MAX_SIDE):
         raise ValueError(f"{who}: height and width must be in [1, {MAX_SIDE}], got {Hf} x {Wf}")

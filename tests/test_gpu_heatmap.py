@@ -3,7 +3,7 @@ tests/test_heatmap_cpu.py, which that file ties to the reference's own outputs. 
 is exact (torch.equal; where a NaN is expected, equal NaN positions and equal values elsewhere).  Nothing here provokes a fault: refusals are tested through
 the error code.
 
-The kernel's mapping (csrc/k_heatmap.hip), which the tie tests place their maxima by: one wavefront per map; a map is read as vectors of VW values (16 bytes:
+The kernel's mapping (k_heatmap_keypoints in csrc/k_heatmap.hip, which the flip-tested kernel shares its helpers with), which the tie tests place their maxima by: one wavefront per map; a map is read as vectors of VW values (16 bytes:
 VW = 4 for fp32, 8 for fp16 / bf16; VW = 1 on the element-wise path, taken when the array does not start on a 16-byte boundary or a map is not a multiple of 16
 bytes); vector v is read by lane v % 64 in that lane's pass v // 64, and value k of it is map index v * VW + k."""
 import numpy as np

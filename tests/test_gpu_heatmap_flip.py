@@ -3,7 +3,7 @@ numpy restatement of tests/test_heatmap_flip_cpu.py, which that file ties to the
 operations, so every comparison is exact (torch.equal; where a NaN is expected, equal NaN positions and equal values elsewhere).  Nothing here provokes a
 fault: refusals are tested through the error code.
 
-The kernel's mapping (csrc/k_heatmap_flip.hip), which the tie tests place their maxima by: one wavefront per merged map; the DIRECT map is read as vectors of
+The kernel's mapping (k_heatmap_flip_keypoints in csrc/k_heatmap.hip), which the tie tests place their maxima by: one wavefront per merged map; the DIRECT map is read as vectors of
 VW values (16 bytes: VW = 4 for fp32, 8 for fp16 / bf16; VW = 1 on the element-wise path, taken when either array does not start on a 16-byte boundary or a map
 is not a multiple of 16 bytes); vector v is read by lane v % 64 in that lane's pass v // 64, and value k of it is merged map index v * VW + k = row y, column
 x + k.  Its flipped operand is element y * W + src_x(x + k) of the partner map: when W is a multiple of VW, slot VW - 1 - k (no shift) or VW - k (shift) of the

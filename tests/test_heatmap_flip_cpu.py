@@ -331,10 +331,10 @@ class RecordingLib:
 
 
 def test_without_flipped_the_old_entry_is_called_and_with_it_the_new_one(monkeypatch):
-    from kasportsformer_amd import _lib, heatmap
+    from kasportsformer_amd import _args, _lib, heatmap
     lib = RecordingLib()
     monkeypatch.setattr(_lib, "load", lambda: lib)
-    monkeypatch.setattr(heatmap, "_stream", lambda: None)
+    monkeypatch.setattr(_args, "stream", lambda: None)
     monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())
     hm, hmf = torch.zeros((2, 17, 5, 3)), torch.ones((2, 17, 5, 3))
     parts = (torch.zeros((2, 2)), torch.ones((2, 2)))

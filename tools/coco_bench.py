@@ -28,7 +28,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import kasportsformer_amd as K  # noqa: E402
 from kasportsformer_amd import _lib  # noqa: E402
-from kasportsformer_amd.lift import _stream, window_plan  # noqa: E402
+from kasportsformer_amd._args import stream  # noqa: E402
+from kasportsformer_amd.lift import window_plan  # noqa: E402
 from tests.test_coco_world_cpu import coco_h36m_np  # noqa: E402
 
 PLAYERS = (22, 30, 1800)                # lift_tracks_bench.py's preset: tracks, shortest, longest (frames)
@@ -118,10 +119,10 @@ def main():
         r = window_plan(frames, T)[2]
         r_d = torch.from_numpy(r).cuda() if r is not None else None
         launches = {
-            "coco_h36m": (408, lambda: lib.kasf_coco_h36m(src.data_ptr(), frames, dst.data_ptr(), _stream())),
-            "pose_world_floor_unit": (408, lambda: lib.kasf_pose_world(src.data_ptr(), frames, q.ctypes.data, None, 1, 1, dst.data_ptr(), _stream())),
+            "coco_h36m": (408, lambda: lib.kasf_coco_h36m(src.data_ptr(), frames, dst.data_ptr(), stream())),
+            "pose_world_floor_unit": (408, lambda: lib.kasf_pose_world(src.data_ptr(), frames, q.ctypes.data, None, 1, 1, dst.data_ptr(), stream())),
             "lift_windows_flip (yardstick)": (612, lambda: lib.kasf_lift_windows(src.data_ptr(), 1, frames, float(W_PX), float(H_PX), T, T,
-                                                                               r_d.data_ptr() if r_d is not None else None, 1, x.data_ptr(), _stream())),
+                                                                               r_d.data_ptr() if r_d is not None else None, 1, x.data_ptr(), stream())),
         }
         for name, (bytes_per_frame, launch) in launches.items():
             _lib.check(launch())

@@ -30,7 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import kasportsformer_amd as K  # noqa: E402
 from kasportsformer_amd import _lib  # noqa: E402
 from kasportsformer_amd.lift import window_plan  # noqa: E402
-from kasportsformer_amd.pose import _stream  # noqa: E402
+from kasportsformer_amd._args import stream  # noqa: E402
 from tests.test_crop_cpu import MEAN, STD, crop_persons_np  # noqa: E402
 
 HF, WF, OUT_W, OUT_H = 1080, 1920, 288, 384
@@ -96,7 +96,7 @@ def main():
 
             def launch():
                 return lib.kasf_crop_persons(frame.data_ptr(), 1, HF, WF, 3 * WF, 0, None, boxes.data_ptr(), _lib.GEOM_BOX, HF / WF, n, out.data_ptr(), code,
-                                             OUT_W, OUT_H, ms_arr, 1, cs.data_ptr(), _stream())
+                                             OUT_W, OUT_H, ms_arr, 1, cs.data_ptr(), stream())
             med, best = _per_launch(launch, args.reps, args.kernel_iters)
             nbytes = out.numel() * out.element_size()
             crop[f"{name} @ n={n}"] = {"us": round(med * 1e3, 2), "min_us": round(best * 1e3, 2), "output_MB": round(nbytes / 1e6, 2),
@@ -134,7 +134,7 @@ def main():
     geom = torch.cat((torch.rand((nh, 2), device="cuda") * 1000, 1 + torch.rand((nh, 2), device="cuda")), dim=-1).contiguous()
     kp = torch.empty((nh, 17, 3), device="cuda")
     med, best = _per_launch(lambda: lib.kasf_heatmap_keypoints(hm.data_ptr(), _lib.DTYPE_F32, nh, H, W, geom.data_ptr(), _lib.GEOM_CENTER_SCALE, 1.0, 1,
-                                                               _lib.LAYOUT_COCO, kp.data_ptr(), None, _stream()), args.reps, args.kernel_iters)
+                                                               _lib.LAYOUT_COCO, kp.data_ptr(), None, stream()), args.reps, args.kernel_iters)
     nbytes = hm.numel() * 4 + geom.numel() * 4 + kp.numel() * 4
     yard["heatmap_keypoints fp32 @ n=1024"] = {"us": round(med * 1e3, 2), "min_us": round(best * 1e3, 2), "GB_per_s": round(nbytes / med / 1e6, 1)}
     del hm
@@ -144,7 +144,7 @@ def main():
     r = window_plan(frames, T)[2]
     r_d = torch.from_numpy(r).cuda() if r is not None else None
     med, best = _per_launch(lambda: lib.kasf_lift_windows(src.data_ptr(), 1, frames, 1280.0, 720.0, T, T, r_d.data_ptr() if r_d is not None else None, 1,
-                                                          x.data_ptr(), _stream()), args.reps, args.kernel_iters)
+                                                          x.data_ptr(), stream()), args.reps, args.kernel_iters)
     yard["lift_windows flip @ 1000000 frames"] = {"us": round(med * 1e3, 2), "min_us": round(best * 1e3, 2), "GB_per_s": round(612 * frames / med / 1e6, 1)}
     res["yardsticks"] = yard
     line = json.dumps(res)

@@ -28,7 +28,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import kasportsformer_amd as K  # noqa: E402
 from kasportsformer_amd import _lib  # noqa: E402
-from kasportsformer_amd.pose import _stream  # noqa: E402
+from kasportsformer_amd._args import stream  # noqa: E402
 from tests.test_detect_cpu import detect_decode_np  # noqa: E402
 
 INP, GRIDS, A, NC, W_PX, H_PX, CONF, NMS = 416, (13, 26, 52), 3, 80, 1280, 720, 0.30, 0.4
@@ -118,7 +118,7 @@ def main():
 
             def launch():
                 return lib.kasf_detect_boxes(ptrs, len(tensors), form, code, B, grid, A, NC, anchors.ctypes.data_as(C.POINTER(C.c_float)), INP, wh.data_ptr(),
-                                             CONF, NMS, 0, 1024, 32, boxes.data_ptr(), index.data_ptr(), count.data_ptr(), ws.data_ptr(), nbytes, _stream())
+                                             CONF, NMS, 0, 1024, 32, boxes.data_ptr(), index.data_ptr(), count.data_ptr(), ws.data_ptr(), nbytes, stream())
             for _ in range(3):
                 _lib.check(launch())
             reps = []

@@ -72,7 +72,7 @@ def step_kernel(args):
     import numpy as np
     import torch
     from kasportsformer_amd import _lib, draw
-    from kasportsformer_amd.pose import _stream
+    from kasportsformer_amd._args import stream
     lib = _lib.load()
     NF = 16
     frames = torch.from_numpy(np.random.default_rng(args.seed).integers(0, 256, size=(NF, HF, WF, 3), dtype=np.uint8)).cuda()
@@ -93,7 +93,7 @@ def step_kernel(args):
                 launch = (lambda o=o, s=s, P=P, kp=kp: lib.kasf_draw_poses(
                     frames.data_ptr(), n, HF, WF, 3 * WF, 3 * HF * WF, kp.data_ptr() if P else None, P, 17, 3, *kp.stride(), None, 0, 0, seg.data_ptr(),
                     col.data_ptr(), 16, dot, 2, 2, 0.25, None, 0, None if o is None else o.data_ptr(), 3 * WF, 3 * HF * WF, y.data_ptr() if s else None,
-                    uv.data_ptr() if s else None, WF, WF, HF * WF, HF * WF // 2, _lib.YUV_BT601, 0, 0, _stream()))
+                    uv.data_ptr() if s else None, WF, WF, HF * WF, HF * WF // 2, _lib.YUV_BT601, 0, 0, stream()))
                 med, best = _per_launch(launch, args.reps, args.kernel_iters)
                 per_px = 3.0 + (3.0 if o is not None and what != "in place" else 0.0) + (1.5 if s else 0.0)
                 nbytes = n * HF * WF * per_px
@@ -103,7 +103,7 @@ def step_kernel(args):
                                                 **({"note": "in place only painted blocks are stored; the GB/s counts the read alone"} if what == "in place" else {})}
         # the yardstick, on the surfaces just written
         med, best = _per_launch(lambda: lib.kasf_yuv420_to_bgr(y.data_ptr(), uv.data_ptr(), None, _lib.YUV_NV12, n, HF, WF, WF, WF, HF * WF, HF * WF // 2, out.data_ptr(),
-                                                               3 * WF, 3 * HF * WF, _lib.YUV_BT601, 0, 0, _stream()), args.reps, args.kernel_iters)
+                                                               3 * WF, 3 * HF * WF, _lib.YUV_BT601, 0, 0, stream()), args.reps, args.kernel_iters)
         nbytes = n * HF * WF * 4.5
         us[(n, "yardstick")] = med * 1e3
         res[f"yardstick yuv420_to_bgr nv12 @ F={n}"] = {"us": round(med * 1e3, 2), "min_us": round(best * 1e3, 2), "read_plus_written_MB": round(nbytes / 1e6, 2),

@@ -28,7 +28,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import kasportsformer_amd as K  # noqa: E402
 from kasportsformer_amd import _lib  # noqa: E402
-from kasportsformer_amd.pose import _stream  # noqa: E402
+from kasportsformer_amd._args import stream  # noqa: E402
 from tests.test_heatmap_cpu import heatmap_decode_np  # noqa: E402
 
 T, W_PX, H_PX, H, W = 27, 1280, 720, 96, 72
@@ -95,7 +95,7 @@ def main():
             for lname, layout in layouts:
                 def launch():
                     return lib.kasf_heatmap_keypoints(hm.data_ptr(), code, n, H, W, geom.data_ptr(), _lib.GEOM_CENTER_SCALE, 1.0, 1, layout, out.data_ptr(),
-                                                      scratch.data_ptr(), _stream())
+                                                      scratch.data_ptr(), stream())
                 for _ in range(3):
                     _lib.check(launch())
                 reps = []

@@ -52,11 +52,11 @@ def step_dtype(args, name):
     import numpy as np
     import torch
     from kasportsformer_amd import _lib
-    from kasportsformer_amd.heatmap import _DTYPES, partner_table
-    from kasportsformer_amd.pose import _stream
+    from kasportsformer_amd._args import DTYPES, stream
+    from kasportsformer_amd.heatmap import partner_table
     lib = _lib.load()
     dtype = {"fp32": torch.float32, "fp16": torch.float16}[name]
-    code, size = _DTYPES[dtype], torch.empty((), dtype=dtype).element_size()
+    code, size = DTYPES[dtype], torch.empty((), dtype=dtype).element_size()
     partner = partner_table(None, "heatmap_flip_bench")
     partner_d = torch.from_numpy(partner.astype(np.int64)).cuda()
     res = {"device": torch.cuda.get_device_name(0)}
@@ -69,11 +69,11 @@ def step_dtype(args, name):
 
         def flip(store=None):
             _lib.check(lib.kasf_heatmap_flip_keypoints(hm.data_ptr(), hmf.data_ptr(), code, n, H, W, partner.ctypes.data, 1, geom.data_ptr(), _lib.GEOM_CENTER_SCALE,
-                                                       1.0, 1, _lib.LAYOUT_COCO, out.data_ptr(), None, store, _stream()))
+                                                       1.0, 1, _lib.LAYOUT_COCO, out.data_ptr(), None, store, stream()))
 
         def decode(t, o):
-            _lib.check(lib.kasf_heatmap_keypoints(t.data_ptr(), _DTYPES[t.dtype], n, H, W, geom.data_ptr(), _lib.GEOM_CENTER_SCALE, 1.0, 1, _lib.LAYOUT_COCO,
-                                                  o.data_ptr(), None, _stream()))
+            _lib.check(lib.kasf_heatmap_keypoints(t.data_ptr(), DTYPES[t.dtype], n, H, W, geom.data_ptr(), _lib.GEOM_CENTER_SCALE, 1.0, 1, _lib.LAYOUT_COCO,
+                                                  o.data_ptr(), None, stream()))
 
         def yardstick():
             decode(hm, out2)

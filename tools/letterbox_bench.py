@@ -64,7 +64,7 @@ def _per_launch(launch, reps, iters):
 def step_kernel(args):
     import torch
     from kasportsformer_amd import _lib
-    from kasportsformer_amd.pose import _stream
+    from kasportsformer_amd._args import stream
     lib = _lib.load()
     frames = torch.from_numpy(_frames(args.seed, 16)).cuda()
     res = {"device": torch.cuda.get_device_name(0)}
@@ -72,7 +72,7 @@ def step_kernel(args):
         for name, dt, code in (("fp32", torch.float32, _lib.DTYPE_F32), ("fp16", torch.float16, _lib.DTYPE_F16)):
             out = torch.empty((n, 3, DIM, DIM), dtype=dt, device="cuda")
             med, best = _per_launch(lambda: lib.kasf_letterbox_frames(frames.data_ptr(), n, HF, WF, 3 * WF, HF * WF * 3, out.data_ptr(), code, DIM, DIM, 128, 1,
-                                                                      _stream()), args.reps, args.kernel_iters)
+                                                                      stream()), args.reps, args.kernel_iters)
             nbytes = out.numel() * out.element_size()
             res[f"{name} @ F={n}"] = {"us": round(med * 1e3, 2), "min_us": round(best * 1e3, 2), "output_MB": round(nbytes / 1e6, 2),
                                       "output_GB_per_s": round(nbytes / med / 1e6, 1)}
@@ -108,7 +108,7 @@ def step_yardstick(args):
     import numpy as np
     import torch
     from kasportsformer_amd import _lib
-    from kasportsformer_amd.pose import _stream
+    from kasportsformer_amd._args import stream
     from tests.test_crop_cpu import MEAN, STD
     lib = _lib.load()
     g = np.random.default_rng(args.seed)
@@ -124,7 +124,7 @@ def step_yardstick(args):
     for name, dt, code in (("fp32", torch.float32, _lib.DTYPE_F32), ("fp16", torch.float16, _lib.DTYPE_F16)):
         out = torch.empty((n, 3, out_h, out_w), dtype=dt, device="cuda")
         med, best = _per_launch(lambda: lib.kasf_crop_persons(frame.data_ptr(), 1, HF, WF, 3 * WF, 0, None, boxes.data_ptr(), _lib.GEOM_BOX, HF / WF, n,
-                                                              out.data_ptr(), code, out_w, out_h, ms_arr, 1, cs.data_ptr(), _stream()), args.reps, args.kernel_iters)
+                                                              out.data_ptr(), code, out_w, out_h, ms_arr, 1, cs.data_ptr(), stream()), args.reps, args.kernel_iters)
         nbytes = out.numel() * out.element_size()
         res[f"crop_persons {name} @ n={n}"] = {"us": round(med * 1e3, 2), "min_us": round(best * 1e3, 2), "output_MB": round(nbytes / 1e6, 2),
                                                "output_GB_per_s": round(nbytes / med / 1e6, 1)}

@@ -19,7 +19,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import kasportsformer_amd as K  # noqa: E402
 from kasportsformer_amd import _lib  # noqa: E402
-from kasportsformer_amd.lift import _stream, window_plan  # noqa: E402
+from kasportsformer_amd._args import stream  # noqa: E402
+from kasportsformer_amd.lift import window_plan  # noqa: E402
 
 
 def main():
@@ -50,11 +51,11 @@ def main():
         for _ in range(args.reps):
             ev[0].record()
             _lib.check(lib.kasf_lift_windows(track.data_ptr(), 1, n, float(W_PX), float(H_PX), T, T, r_dev.data_ptr() if r_dev is not None else None, 1,
-                                             x.data_ptr(), _stream()))
+                                             x.data_ptr(), stream()))
             ev[1].record()
             pred = model(x)
             ev[2].record()
-            _lib.check(lib.kasf_lift_stitch(pred.data_ptr(), 1, 1, n, T, T, fp_dev.data_ptr() if fp_dev is not None else None, poses.data_ptr(), _stream()))
+            _lib.check(lib.kasf_lift_stitch(pred.data_ptr(), 1, 1, n, T, T, fp_dev.data_ptr() if fp_dev is not None else None, poses.data_ptr(), stream()))
             ev[3].record()
             K.lift_track(model, track, W_PX, H_PX)
             ev[4].record()

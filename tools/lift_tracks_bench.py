@@ -25,7 +25,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import kasportsformer_amd as K  # noqa: E402
 from kasportsformer_amd import _lib  # noqa: E402
-from kasportsformer_amd.lift import _stream, ragged_plan  # noqa: E402
+from kasportsformer_amd._args import stream  # noqa: E402
+from kasportsformer_amd.lift import ragged_plan  # noqa: E402
 
 PRESETS = {"players": (22, 30, 1800), "short": (200, 20, 60)}     # tracks, shortest, longest (frames)
 
@@ -87,9 +88,9 @@ def main():
     poses = torch.empty((frames, 17, 3), device="cuda")
     launches = {
         "windows_ragged": lambda: lib.kasf_lift_windows_ragged(packed.data_ptr(), off_d.data_ptr(), wf_d.data_ptr(), P, frames, windows, w_d.data_ptr(),
-                                                               h_d.data_ptr(), T, T, r_d.data_ptr(), 1, x.data_ptr(), _stream()),
+                                                               h_d.data_ptr(), T, T, r_d.data_ptr(), 1, x.data_ptr(), stream()),
         "stitch_ragged": lambda: lib.kasf_lift_stitch_ragged(pred.data_ptr(), 1, off_d.data_ptr(), wf_d.data_ptr(), P, frames, windows, T, T,
-                                                             fp_d.data_ptr(), poses.data_ptr(), _stream()),
+                                                             fp_d.data_ptr(), poses.data_ptr(), stream()),
     }
     for name, launch in launches.items():
         _lib.check(launch())

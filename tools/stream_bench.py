@@ -26,7 +26,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import kasportsformer_amd as K  # noqa: E402
 from kasportsformer_amd import _lib  # noqa: E402
-from kasportsformer_amd.lift import _stream  # noqa: E402
+from kasportsformer_amd._args import stream  # noqa: E402
 
 PRESETS = {"players": 22, "one": 1}     # slots
 
@@ -97,11 +97,11 @@ def main():
     out = torch.empty((S, 1, 17, 3), device="cuda")
     ring, count = lifter._ring.clone(), lifter._count.clone()
     launches = {
-        "stream_push": lambda: lib.kasf_stream_push(frame.data_ptr(), None, S, S, T, ring.data_ptr(), count.data_ptr(), _stream()),
+        "stream_push": lambda: lib.kasf_stream_push(frame.data_ptr(), None, S, S, T, ring.data_ptr(), count.data_ptr(), stream()),
         "stream_windows": lambda: lib.kasf_stream_windows(ring.data_ptr(), count.data_ptr(), None, S, S, T, lifter._width.data_ptr(),
-                                                          lifter._height.data_ptr(), lifter._r_tab.data_ptr(), 1, x.data_ptr(), _stream()),
+                                                          lifter._height.data_ptr(), lifter._r_tab.data_ptr(), 1, x.data_ptr(), stream()),
         "stream_emit": lambda: lib.kasf_stream_emit(pred.data_ptr(), 1, count.data_ptr(), None, S, S, T, lifter._fp_tab.data_ptr(), 0, 1,
-                                                    out.data_ptr(), _stream()),
+                                                    out.data_ptr(), stream()),
     }
     kernel_ms = {}
     for name, launch in launches.items():

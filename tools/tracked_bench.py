@@ -24,7 +24,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import kasportsformer_amd as K  # noqa: E402
 from kasportsformer_amd import _lib  # noqa: E402
-from kasportsformer_amd.lift import _stream  # noqa: E402
+from kasportsformer_amd._args import stream  # noqa: E402
 
 T, W_PX, H_PX, SLOTS = 27, 1280, 720, 32
 
@@ -113,10 +113,10 @@ def run(P, args):
         "stream_track_front": lambda: lib.kasf_stream_track_front(frame.data_ptr(), r.ids.data_ptr(), r.slot.data_ptr(), r.born.data_ptr(), r.count.data_ptr(), 1,
                                                                   SLOTS, 0, P, T, ring.data_ptr(), cnt.data_ptr(), owner.data_ptr(), tracked._width.data_ptr(),
                                                                   tracked._height.data_ptr(), tracked._r_tab.data_ptr(), 1, x.data_ptr(), row_slot.data_ptr(),
-                                                                  _stream()),
-        "stream_push": lambda: lib.kasf_stream_push(frame.data_ptr(), ids_d.data_ptr(), P, SLOTS, T, ring_p.data_ptr(), cnt_p.data_ptr(), _stream()),
+                                                                  stream()),
+        "stream_push": lambda: lib.kasf_stream_push(frame.data_ptr(), ids_d.data_ptr(), P, SLOTS, T, ring_p.data_ptr(), cnt_p.data_ptr(), stream()),
         "stream_windows": lambda: lib.kasf_stream_windows(ring_p.data_ptr(), cnt_p.data_ptr(), ids_d.data_ptr(), P, SLOTS, T, plain._width.data_ptr(),
-                                                          plain._height.data_ptr(), plain._r_tab.data_ptr(), 1, x.data_ptr(), _stream()),
+                                                          plain._height.data_ptr(), plain._r_tab.data_ptr(), 1, x.data_ptr(), stream()),
     }
     kernel_ms = {}
     for name, launch in launches.items():

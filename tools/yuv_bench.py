@@ -63,7 +63,7 @@ def step_kernel(args):
     import numpy as np
     import torch
     from kasportsformer_amd import _lib
-    from kasportsformer_amd.pose import _stream
+    from kasportsformer_amd._args import stream
     from tests.test_crop_cpu import MEAN, STD
     lib = _lib.load()
     nv12 = torch.from_numpy(_surfaces(args.seed, 16)).cuda()                                   # [16, ROWS, PITCH]
@@ -76,9 +76,9 @@ def step_kernel(args):
     for n in (1, 16):
         calls = {
             "nv12": lambda: lib.kasf_yuv420_to_bgr(nv12.data_ptr(), nv12.data_ptr() + CHROMA_ROW * PITCH, None, _lib.YUV_NV12, n, HF, WF, PITCH, PITCH, surface,
-                                                   surface, frames.data_ptr(), 3 * WF, 3 * HF * WF, _lib.YUV_BT601, 0, 0, _stream()),
+                                                   surface, frames.data_ptr(), 3 * WF, 3 * HF * WF, _lib.YUV_BT601, 0, 0, stream()),
             "i420": lambda: lib.kasf_yuv420_to_bgr(y.data_ptr(), u.data_ptr(), v.data_ptr(), _lib.YUV_I420, n, HF, WF, WF, WF // 2, HF * WF, HF * WF // 4,
-                                                   frames.data_ptr(), 3 * WF, 3 * HF * WF, _lib.YUV_BT601, 0, 0, _stream()),
+                                                   frames.data_ptr(), 3 * WF, 3 * HF * WF, _lib.YUV_BT601, 0, 0, stream()),
         }
         for name, launch in calls.items():
             med, best = _per_launch(launch, args.reps, args.kernel_iters)
@@ -88,7 +88,7 @@ def step_kernel(args):
     # the yardsticks, on the frames just written
     out = torch.empty((16, 3, DIM, DIM), dtype=torch.float32, device="cuda")
     med, best = _per_launch(lambda: lib.kasf_letterbox_frames(frames.data_ptr(), 16, HF, WF, 3 * WF, HF * WF * 3, out.data_ptr(), _lib.DTYPE_F32, DIM, DIM, 128, 1,
-                                                              _stream()), args.reps, args.kernel_iters)
+                                                              stream()), args.reps, args.kernel_iters)
     nbytes = out.numel() * 4
     res["yardstick letterbox_frames fp32 @ F=16"] = {"us": round(med * 1e3, 2), "min_us": round(best * 1e3, 2), "output_MB": round(nbytes / 1e6, 2),
                                                      "output_GB_per_s": round(nbytes / med / 1e6, 1)}
@@ -102,7 +102,7 @@ def step_kernel(args):
     crops = torch.empty((P, 3, out_h, out_w), dtype=torch.float32, device="cuda")
     ms_arr = (C.c_float * 6)(*MEAN, *STD)
     med, best = _per_launch(lambda: lib.kasf_crop_persons(frames.data_ptr(), 1, HF, WF, 3 * WF, 0, None, boxes.data_ptr(), _lib.GEOM_BOX, HF / WF, P,
-                                                          crops.data_ptr(), _lib.DTYPE_F32, out_w, out_h, ms_arr, 1, cs.data_ptr(), _stream()), args.reps,
+                                                          crops.data_ptr(), _lib.DTYPE_F32, out_w, out_h, ms_arr, 1, cs.data_ptr(), stream()), args.reps,
                             args.kernel_iters)
     nbytes = crops.numel() * 4
     res[f"yardstick crop_persons fp32 @ n={P}"] = {"us": round(med * 1e3, 2), "min_us": round(best * 1e3, 2), "output_MB": round(nbytes / 1e6, 2),
