@@ -1,7 +1,7 @@
 // The window arithmetic every lifting kernel shares (k_lift.hip, k_stream_track.hip; the joint table also k_eval.hip): one definition of the window count, the
 // left/right joint table, the clip value, the flip-TTA merge and the mean over the windows that cover a frame.  "Every pose is lift_track of the current
 // window" holds bit for bit between the batch, ragged, stream and tracked forms because all of them compute through these functions.
-// Plain C++: HIP device code in the library, g++ behind the stand-in kernels.h of tests/tracked_host/ (which defines __device__ / __constant__) in the CPU tests.
+// Plain C++: HIP device code in the library, g++ behind the stand-in hip/hip_runtime.h of tests/host_emul/ (which defines __device__ / __constant__) in the CPU tests.
 #pragma once
 #include <stdint.h>
 

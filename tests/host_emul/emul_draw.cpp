@@ -1,11 +1,5 @@
-// csrc/k_draw.hip compiled for the host (tests/test_draw_host_cpu.py): the kernel source is included as it is, behind the stand-in kernels.h of this directory.
+// csrc/k_draw.hip compiled for the host (tests/test_draw_host_cpu.py).
 #include "kernels.h"
-thread_local Idx threadIdx, blockIdx, gridDim;
-std::barrier<>* g_bar;
-int g_launches;
-unsigned char g_pred[1024];
-void kasf_launch_draw_poses(hipStream_t s, const KasfDrawLaunch* d);
-void kasf_launch_pose_panel(hipStream_t s, const float* poses, int64_t n, const float view[8], float* out);
 #include "k_draw.hip"
 // -> the number of launches made (the entry point promises one)
 extern "C" int emul_draw_poses(const KasfDrawLaunch* d) {

@@ -1,11 +1,5 @@
-// csrc/k_letterbox.hip compiled for the host (tests/test_letterbox_host_cpu.py): the kernel source is included as it is, behind the stand-in kernels.h of this directory.
+// csrc/k_letterbox.hip compiled for the host (tests/test_letterbox_host_cpu.py).
 #include "kernels.h"
-thread_local Idx threadIdx, blockIdx, gridDim;
-std::barrier<>* g_bar;
-unsigned char* g_lds;
-int g_lds_overrun;
-void kasf_launch_letterbox(hipStream_t s, const void* frames, int n_frames, int Hf, int Wf, int64_t row_stride, int64_t frame_stride, void* out, int out_dtype,
-                           int out_w, int out_h, int new_w, int new_h, int pad_x, int pad_y, int pad_value, int swap_rb);
 #include "k_letterbox.hip"
 extern "C" int emul_letterbox(const void* frames, int n_frames, int Hf, int Wf, int64_t row_stride, int64_t frame_stride, void* out, int out_dtype, int out_w,
                               int out_h, int new_w, int new_h, int pad_x, int pad_y, int pad_value, int swap_rb) {

@@ -1,9 +1,5 @@
-// csrc/k_lift.hip compiled for the host (tests/test_lift_host_cpu.py): the kernel source is included as it is, behind the stand-in kernels.h of this directory.
+// csrc/k_lift.hip compiled for the host (tests/test_lift_host_cpu.py).
 #include "kernels.h"
-thread_local Idx threadIdx, blockIdx, gridDim;
-thread_local int g_phase;
-std::barrier<>* g_bar;
-std::atomic<int> g_or[2];
 #include "k_lift.hip"
 extern "C" {
 void emul_lift_windows(const float* track, int P, int64_t n, float width, float height, int T, int stride, const int* resample, int flip, float* x) {

@@ -1,12 +1,7 @@
-// csrc/k_loss.hip compiled for the host (tests/test_loss_host_cpu.py): the kernel source is included as it is, behind the stand-in kernels.h / common.h of this
-// directory.  k_loss3.inc is written by the test: the k_loss3 / k_loss3_finish / kasf_launch_loss3 text of csrc/k_misc.hip cut out as it is, with its dynamic-LDS
-// declaration replaced by the stand-in's, for the bit comparison of the three old terms.
+// csrc/k_loss.hip compiled for the host (tests/test_loss_host_cpu.py): a copy of the kernel in the build directory, so that its #include "common.h" finds the
+// stand-in of this directory.  k_loss3.inc is written by the test: the k_loss3 / k_loss3_finish / kasf_launch_loss3 text of csrc/k_misc.hip cut out as it is,
+// with its dynamic-LDS declaration replaced by the stand-in's, for the bit comparison of the three old terms.
 #include "kernels.h"
-thread_local Idx threadIdx, blockIdx;
-std::barrier<>* g_bar;
-int g_launches;
-float g_slot[1024];
-float* g_dyn_lds;
 #include "k_loss.hip"
 #include "k_loss3.inc"
 extern "C" int emul_loss7(const float* pred, const float* tgt, float* dpred, float* losses, int B, int T, const float* lambdas, float grad_scale) {

@@ -1,14 +1,5 @@
-// csrc/k_stream_track.hip compiled for the host (tests/test_tracked_host_cpu.py): the kernel source is included as it is, behind the stand-in kernels.h of this directory.
+// csrc/k_stream_track.hip compiled for the host (tests/test_tracked_host_cpu.py).
 #include "kernels.h"
-thread_local Idx threadIdx, blockIdx, gridDim;
-thread_local int g_phase;
-std::barrier<>* g_bar;
-std::atomic<int> g_or[2];
-void kasf_launch_stream_track_front(hipStream_t s, const float* frames, const int* ids, const int* slot, const int* born, const int* count_b, int B, int S_t,
-                                    int rows_mode, int R, int T, float* ring, int64_t* count, int* owner, const float* width, const float* height,
-                                    const int* resample_tab, int flip, float* x, int* row_slot);
-void kasf_launch_stream_track_emit(hipStream_t s, const float* pred, int flip, const int64_t* count, const int* owner, const int* row_slot, int64_t n_rows, int T,
-                                   const int* first_pos_tab, int back, float* out, unsigned char* valid, int* ids_out, int64_t* frames_out);
 #include "k_stream_track.hip"
 extern "C" void emul_front(const float* frames, const int* ids, const int* slot, const int* born, const int* count_b, int B, int S_t, int rows_mode, int R, int T,
                            float* ring, int64_t* count, int* owner, const float* width, const float* height, const int* resample_tab, int flip, float* x,

@@ -1,11 +1,5 @@
-// csrc/k_yuv.hip compiled for the host (tests/test_yuv_host_cpu.py): the kernel source is included as it is, behind the stand-in kernels.h of this directory.
+// csrc/k_yuv.hip compiled for the host (tests/test_yuv_host_cpu.py).
 #include "kernels.h"
-thread_local Idx threadIdx, blockIdx, gridDim;
-std::barrier<>* g_bar;
-int g_lds_asked, g_launches;
-void kasf_launch_yuv420_to_bgr(hipStream_t s, const void* y, const void* c0, const void* c1, int nv12, int n_frames, int Hf, int Wf, int64_t y_row_stride,
-                               int64_t c_row_stride, int64_t y_frame_stride, int64_t c_frame_stride, void* out, int64_t out_row_stride, int64_t out_frame_stride,
-                               const int coef[5], int full_range, int rgb);
 #include "k_yuv.hip"
 // -> the number of launches made (the entry point promises one), or -1 if one of them asked for LDS
 extern "C" int emul_yuv420_to_bgr(const void* y, const void* c0, const void* c1, int nv12, int n_frames, int Hf, int Wf, int64_t y_row_stride, int64_t c_row_stride,

@@ -1,4 +1,4 @@
-"""csrc/k_draw.hip without a GPU: the kernel's own source compiled for the host with g++ behind a lockstep emulation of a workgroup (tests/draw_host/: one
+"""csrc/k_draw.hip without a GPU: the kernel's own source compiled for the host with g++ behind a lockstep emulation of a workgroup (tests/host_emul/: one
 host thread per GPU thread, the blocks of the grid one after the other, __ballot modelled per wavefront of 64) and held to the numpy restatements of
 include/kasf.h's rules (tests/test_draw_cpu.py: draw_poses_np, bgr_to_nv12_np, pose_panel_np), exactly.  It shows the kernel's logic -- binning, in-order
 compaction, the backward walk over chunks, the per-pixel painted bits -- and its indexing: the frame, the output and both planes of the surface sit behind padded
@@ -11,17 +11,13 @@ behind odd pitches: bytes everywhere; `pitch` keeps the bases on the grid and ma
 import ctypes as C
 import functools
 import itertools
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.host_emul import PAD, SENTINEL, Plane, build, up
 from tests.test_draw_cpu import CASES, COMBOS, LIST, TABLES, TILE_H, TILE_W, bgr_to_nv12_np, expected, noise_frames, pose_panel_np, primitives_through_tile
-from tests.test_yuv_host_cpu import PAD, SENTINEL, Plane, up
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUTPUTS = ("bgr", "surface", "both", "inplace", "inplace+surface")
 
 
@@ -38,20 +34,7 @@ class Launch(C.Structure):                                       # csrc/draw_arg
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    d = tmp_path_factory.mktemp("draw_host")
-    for f in ("kernels.h", "emul.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "draw_host", f), d)
-    for f in ("k_draw.hip", "draw_args.h"):
-        shutil.copy(os.path.join(ROOT, "kasportsformer_amd", "csrc", f), d)                         # its #include "kernels.h" now finds the stand-in
-    r = subprocess.run([gxx, "-std=c++20", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-x", "c++", "-I.", "emul.cpp", "-o", "libemul.so", "-lpthread"],
-                       cwd=d, capture_output=True, text=True)
-    if r.returncode != 0 and "barrier" in r.stderr and "No such file" in r.stderr:
-        pytest.skip("this g++ has no C++20 <barrier>")
-    assert r.returncode == 0, r.stderr
-    lib = C.CDLL(str(d / "libemul.so"))
+    lib = build(tmp_path_factory, "draw_host", "emul_draw.cpp")
     lib.emul_draw_poses.restype = C.c_int
     lib.emul_draw_poses.argtypes = [C.POINTER(Launch)]
     lib.emul_pose_panel.restype = C.c_int

@@ -1,39 +1,24 @@
 """csrc/k_letterbox.hip without a GPU: the kernel's own source compiled for the host with g++ behind a lockstep emulation of a workgroup
-(tests/letterbox_host/: one host thread per GPU thread, a barrier at every __syncthreads, the dynamic LDS a buffer of exactly the bytes the launch asks for)
+(tests/host_emul/: one host thread per GPU thread, a barrier at every __syncthreads, the dynamic LDS a buffer of exactly the bytes the launch asks for)
 and held to the numpy restatement of include/kasf.h's rules (tests/test_letterbox_cpu.py, letterbox_np), exactly.  It shows the kernel's logic, its indexing
 (canaries around the output, the frame and the LDS) and its integer / fp32 / fp64 operation order; what only the device can show stays with
 tests/test_gpu_letterbox.py."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from tests.host_emul import build
 from tests.test_letterbox_cpu import ODD_SIZES, fixture, fixture_frame, letterbox_np, noise_frame, plan_np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CANARY = 0x5A
 DTYPES = {"fp32": (0, 4, torch.float32), "bf16": (1, 2, torch.bfloat16), "fp16": (2, 2, torch.float16)}
 
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    d = tmp_path_factory.mktemp("letterbox_host")
-    for f in ("kernels.h", "emul.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "letterbox_host", f), d)
-    shutil.copy(os.path.join(ROOT, "kasportsformer_amd", "csrc", "k_letterbox.hip"), d)        # its #include "kernels.h" now finds the stand-in
-    r = subprocess.run([gxx, "-std=c++20", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-x", "c++", "-I.", "emul.cpp", "-o", "libemul.so", "-lpthread"],
-                       cwd=d, capture_output=True, text=True)
-    if r.returncode != 0 and "barrier" in r.stderr and "No such file" in r.stderr:
-        pytest.skip("this g++ has no C++20 <barrier>")
-    assert r.returncode == 0, r.stderr
-    lib = C.CDLL(str(d / "libemul.so"))
+    lib = build(tmp_path_factory, "letterbox_host", "emul_letterbox.cpp")
     lib.emul_letterbox.restype = C.c_int
     lib.emul_letterbox.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p] + [C.c_int] * 9
     return lib

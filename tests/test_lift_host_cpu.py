@@ -1,19 +1,16 @@
 """csrc/k_lift.hip without a GPU: the kernels' own source (and csrc/lift_math.h, where their arithmetic lives) compiled for the host with g++ behind
-tests/tracked_host/'s lockstep emulation of a workgroup, and the seven launches held bit for bit to the numpy / torch restatements of tests/lift_ref.py.
+tests/host_emul/'s lockstep emulation of a workgroup, and the seven launches held bit for bit to the numpy / torch restatements of tests/lift_ref.py.
 It shows the kernels' logic, their indexing (canaries around every output) and their fp32 / fp64 operation order; what only the device can show stays
 with tests/test_gpu_lift.py, test_gpu_lift_tracks.py and test_gpu_stream.py.  T = 5: the smallest clip length at which every branch of the plan exists."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from tests.host_emul import build
 from tests.lift_ref import H_PX, W_PX, _clip_np, _emit_t, _flip_np, _frames, _ring_state, _stitch_t, _track, _windows_np, _windows_stream_np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T = 5
 RES = [(1280, 720), (1920, 1080), (3840, 2160), (1000, 1000), (1437, 913), (640, 480), (800, 600)]
 CANARY = np.float32(12345.5)
@@ -27,20 +24,7 @@ ARGS = {"emul_lift_windows": [P_, I, L, F, F, I, I, P_, I, P_], "emul_lift_stitc
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    d = tmp_path_factory.mktemp("lift_host")
-    for f in ("kernels.h", "emul_lift.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "tracked_host", f), d)
-    for f in ("k_lift.hip", "lift_math.h"):                                                     # the kernel's #include "kernels.h" now finds the stand-in
-        shutil.copy(os.path.join(ROOT, "kasportsformer_amd", "csrc", f), d)
-    r = subprocess.run([gxx, "-std=c++20", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-x", "c++", "-I.", "emul_lift.cpp", "-o", "libemul_lift.so", "-lpthread"],
-                       cwd=d, capture_output=True, text=True)
-    if r.returncode != 0 and "barrier" in r.stderr and "No such file" in r.stderr:
-        pytest.skip("this g++ has no C++20 <barrier>")
-    assert r.returncode == 0, r.stderr
-    lib = C.CDLL(str(d / "libemul_lift.so"))
+    lib = build(tmp_path_factory, "lift_host", "emul_lift.cpp")
     for name, args in ARGS.items():
         getattr(lib, name).argtypes, getattr(lib, name).restype = args, None
     return lib

@@ -1,5 +1,5 @@
 """csrc/k_loss.hip without a GPU: the kernel's own source compiled for the host with g++ (-ffp-contract=off) behind a lockstep emulation of its workgroups
-(tests/loss_host/: one host thread per GPU thread, a barrier at every __syncthreads and around every shuffle) and held to the fixture the reference's own
+(tests/host_emul/: one host thread per GPU thread, a barrier at every __syncthreads and around every shuffle) and held to the fixture the reference's own
 utils/loss_calc.py wrote (tests/golden/loss7.npz), with the project's bars for loss3 (tests/test_gpu_ops.py: parts 1e-5, gradient rel_err 1e-4).  It shows the
 kernel's logic, its tables and its summation orders; what only the device can show (its acosf, sqrtf and divide, the real shuffles, LDS) stays with
 tests/test_gpu_loss7.py.  Every fixture shape but (300, 3): 300 workgroups of 256 host threads add nothing the others do not show.  The k_loss3 text of
@@ -8,17 +8,15 @@ csrc/k_misc.hip is cut out as it is and compiled beside it for the bit compariso
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import loss_ref
+from tests.host_emul import CSRC, build, vp
 from tests.loss_ref import COLLINEAR_CLIP, TIE_CLIP, ZERO_LIMB_CLIP, case_inputs, rel_err
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "kasportsformer_amd", "csrc")
 F32 = np.float32
 
 
@@ -33,24 +31,7 @@ def loss3_text():
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    d = tmp_path_factory.mktemp("loss_host")
-    for f in ("kernels.h", "common.h", "emul.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "loss_host", f), d)
-    shutil.copy(os.path.join(CSRC, "k_loss.hip"), d)            # its #include "kernels.h" / "common.h" now find the stand-ins
-    (d / "k_loss3.inc").write_text(loss3_text())
-    r = subprocess.run([gxx, "-std=c++20", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-x", "c++", "-I.", "emul.cpp", "-o", "libemul.so", "-lpthread"],
-                       cwd=d, capture_output=True, text=True)
-    if r.returncode != 0 and "barrier" in r.stderr and "No such file" in r.stderr:
-        pytest.skip("this g++ has no C++20 <barrier>")
-    assert r.returncode == 0, r.stderr
-    return C.CDLL(str(d / "libemul.so"))
-
-
-def vp(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return build(tmp_path_factory, "loss_host", "emul_loss.cpp", copy=("k_loss.hip",), generate={"k_loss3.inc": loss3_text()})
 
 
 def run7(lib, pred, target, lambdas, grad_scale=1.0):

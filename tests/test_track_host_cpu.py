@@ -1,44 +1,25 @@
-"""csrc/k_track.hip without a GPU: the kernel's own source compiled for the host with g++ behind a lockstep emulation of the wavefront (tests/track_host/:
+"""csrc/k_track.hip without a GPU: the kernel's own source compiled for the host with g++ behind a lockstep emulation of the wavefront (tests/host_emul/:
 64 threads, a barrier at every shuffle, ballot and __syncthreads) and held to ``sort_update_np`` with the checks of tests/test_gpu_track.py -- every discrete
 output and counter exact, x, P and boxes to 1e-12.  It shows the kernel's logic and its fp64 operation order; what only the device can show (its divide and
 square root, the real shuffles, LDS) stays with tests/test_gpu_track.py.  The first ticks of each case, to stay quick: 64 threads meet at ~10,000 barriers a tick.
 """
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.host_emul import build, vp
 from tests.test_gpu_track import check_tick
 from tests.test_track_cpu import CASES, pad, run_np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TICKS = {"greedy": 3, "overflow": 16, "max_age2": 14, "birth_death": 13, "bad_rows": 8, "hold_on": 10, "hold_off": 10, "demo": 12, "default": 20, "full64": 3}
 
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    d = tmp_path_factory.mktemp("track_host")
-    for f in ("kernels.h", "emul.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "track_host", f), d)
-    shutil.copy(os.path.join(ROOT, "kasportsformer_amd", "csrc", "k_track.hip"), d)       # its #include "kernels.h" now finds the stand-in
-    r = subprocess.run([gxx, "-std=c++20", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-x", "c++", "-I.", "emul.cpp", "-o", "libemul.so", "-lpthread"],
-                       cwd=d, capture_output=True, text=True)
-    if r.returncode != 0 and "barrier" in r.stderr and "No such file" in r.stderr:
-        pytest.skip("this g++ has no C++20 <barrier>")
-    assert r.returncode == 0, r.stderr
-    lib = C.CDLL(str(d / "libemul.so"))
+    lib = build(tmp_path_factory, "track_host", "emul_track.cpp")
     lib.emul_state_bytes.restype = C.c_int64
     return lib
-
-
-def vp(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 class HostTracker:

@@ -1,18 +1,15 @@
 """csrc/k_stream_track.hip without a GPU: the kernels' own source compiled for the host with g++ behind a lockstep emulation of a workgroup
-(tests/tracked_host/: one host thread per GPU thread, a barrier at every __syncthreads / __syncthreads_or) and held to the numpy restatement of the tick rule
+(tests/host_emul/: one host thread per GPU thread, a barrier at every __syncthreads / __syncthreads_or) and held to the numpy restatement of the tick rule
 (tests/tracked_ref.py) and to numpy restatements of the clip and merge arithmetic, exactly.  It shows the kernels' logic, their indexing (canaries around every
 array) and their fp32 / fp64 operation order; what only the device can show stays with tests/test_gpu_tracked.py.  T = 5 and a short run: 256 threads per row."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.host_emul import build, vp
 from tests.tracked_ref import Cases, frames_for, new_state, script, tracked_front_np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLIP_SRC = [0, 4, 5, 6, 1, 2, 3, 7, 8, 9, 10, 14, 15, 16, 11, 12, 13]
 B, S_T = 2, 4
 RES = [(1280, 720), (1437, 913)]
@@ -21,24 +18,7 @@ CANARY = np.float32(12345.5)
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    d = tmp_path_factory.mktemp("tracked_host")
-    for f in ("kernels.h", "emul.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "tracked_host", f), d)
-    for f in ("k_stream_track.hip", "lift_math.h"):                                             # the kernel's #include "kernels.h" now finds the stand-in
-        shutil.copy(os.path.join(ROOT, "kasportsformer_amd", "csrc", f), d)
-    r = subprocess.run([gxx, "-std=c++20", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-x", "c++", "-I.", "emul.cpp", "-o", "libemul.so", "-lpthread"],
-                       cwd=d, capture_output=True, text=True)
-    if r.returncode != 0 and "barrier" in r.stderr and "No such file" in r.stderr:
-        pytest.skip("this g++ has no C++20 <barrier>")
-    assert r.returncode == 0, r.stderr
-    return C.CDLL(str(d / "libemul.so"))
-
-
-def vp(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return build(tmp_path_factory, "tracked_host", "emul_tracked.cpp")
 
 
 def clips_np(ring, count, slots, T, flip):

@@ -1,4 +1,4 @@
-"""csrc/k_yuv.hip without a GPU: the kernel's own source compiled for the host with g++ behind a lockstep emulation of a workgroup (tests/yuv_host/: one
+"""csrc/k_yuv.hip without a GPU: the kernel's own source compiled for the host with g++ behind a lockstep emulation of a workgroup (tests/host_emul/: one
 host thread per GPU thread, the blocks of the grid one after the other) and held to the numpy restatement of include/kasf.h's rules
 (tests/test_yuv_cpu.py, yuv_to_bgr_np), exactly.  It shows the kernel's logic and its indexing -- every plane and the output sit behind padded pitches with
 canaries around the buffers and a sentinel in every row's padding, and the inputs must come back unchanged --; what only the device can show stays with
@@ -9,67 +9,22 @@ strides that are multiples of 8, which takes the vector form for the whole 2 x 8
 bases at odd addresses behind odd pitches, which takes quads for everything; `pitch` keeps the bases on the grid and makes one pitch odd."""
 import ctypes as C
 import itertools
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.host_emul import PAD, SENTINEL, Plane, build, up
 from tests.test_yuv_cpu import SIZES, TABLES, interleave, noise_planes, yuv_to_bgr_np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CANARY, PAD, SENTINEL = 0x5A, 0xEE, 0xC3
 COMBOS = [(m, fr, rgb) for (m, fr) in sorted(TABLES) for rgb in (False, True)]            # the four tables, rgb off / on
 
 
 @pytest.fixture(scope="module")
 def emul(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    d = tmp_path_factory.mktemp("yuv_host")
-    for f in ("kernels.h", "emul.cpp"):
-        shutil.copy(os.path.join(ROOT, "tests", "yuv_host", f), d)
-    shutil.copy(os.path.join(ROOT, "kasportsformer_amd", "csrc", "k_yuv.hip"), d)               # its #include "kernels.h" now finds the stand-in
-    r = subprocess.run([gxx, "-std=c++20", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-x", "c++", "-I.", "emul.cpp", "-o", "libemul.so", "-lpthread"],
-                       cwd=d, capture_output=True, text=True)
-    if r.returncode != 0 and "barrier" in r.stderr and "No such file" in r.stderr:
-        pytest.skip("this g++ has no C++20 <barrier>")
-    assert r.returncode == 0, r.stderr
-    lib = C.CDLL(str(d / "libemul.so"))
+    lib = build(tmp_path_factory, "yuv_host", "emul_yuv.cpp")
     lib.emul_yuv420_to_bgr.restype = C.c_int
     lib.emul_yuv420_to_bgr.argtypes = ([C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_int64] * 4 + [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_int), C.c_int, C.c_int])
     return lib
-
-
-class Plane:
-    """F x rows x row_bytes behind a pitch and a frame stride, `offset` bytes past a multiple of 16, `fill` in the padding, 64 canary bytes on either side."""
-
-    def __init__(self, F, rows, row_bytes, pitch, frame_stride, offset, fill, data=None):
-        self.n = (F - 1) * frame_stride + (rows - 1) * pitch + row_bytes
-        self.buf = np.full(self.n + 160, CANARY, np.uint8)
-        self.start = 64 + (-(self.buf.ctypes.data + 64) % 16) + offset
-        self.buf[self.start:self.start + self.n] = fill
-        self.view = np.lib.stride_tricks.as_strided(self.buf[self.start:], shape=(F, rows, row_bytes), strides=(frame_stride, pitch, 1))
-        if data is not None:
-            self.view[:] = data.reshape(F, rows, row_bytes)
-        self.keep = self.buf.copy()
-        self.ptr, self.pitch, self.frame_stride = self.buf.ctypes.data + self.start, pitch, frame_stride
-
-    def unchanged(self):
-        return np.array_equal(self.buf, self.keep)
-
-    def only_payload_changed(self):
-        """Everything but the rows' payload -- canaries, row padding, the gaps between frames -- is as it was."""
-        now = self.buf.copy()
-        for b in (now, self.keep):
-            np.lib.stride_tricks.as_strided(b[self.start:], shape=self.view.shape, strides=self.view.strides)[:] = 0
-        return np.array_equal(now, self.keep)
-
-
-def up(n, a):
-    return (n + a - 1) // a * a
 
 
 def run(emul, y, u, v, layout, matrix="bt601", full_range=False, rgb=False, place="grid"):
