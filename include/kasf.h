@@ -14,7 +14,7 @@
  *   kasf_model_create      <- KASportsFormer.__init__             model/KASportsFormer.py:291-318
  *   kasf_param_*           <- nn.Module.state_dict() layout       model/KASportsFormer.py:296-318 (names identical)
  *   kasf_forward           <- KASportsFormer.forward              model/KASportsFormer.py:320-347
- *   kasf_backward          <- torch.autograd of the above         train_and_evaluate_sp.py:241  (loss.backward())
+ *   kasf_backward          <- torch.autograd of the above         train_and_evaluate_sp.py:241  (loss.backward()); with KASF_FLAG_INPUT_GRAD also x.grad
  *   kasf_loss3             <- mpjpe + 0.5 n_mpjpe + 20 velocity   utils/loss_calc.py:6-27, train_and_evaluate_sp.py:212-222
  *   kasf_loss7             <- the complete seven-term loss: the three above + lambda_limb_len_var loss_limb_var_calc + lambda_limb_len loss_limb_len_calc
  *                             + lambda_limb_cos_simi loss_cos_simi_calc + lambda_limb_cos_simi_velocity loss_cos_simi_velocity_calc
@@ -74,6 +74,7 @@ extern "C" {
 #define KASF_FLAG_TRAIN 1       /* BatchNorm batch statistics + running-stat update; keep activations for backward */
 #define KASF_FLAG_RETURN_REP 2  /* out is the [B,T,17,512] tanh representation (forward(x, return_rep=True)) */
 #define KASF_FLAG_KEEP 4        /* keep activations for kasf_backward WITHOUT batch statistics: autograd through model.eval() (BatchNorm on running stats) */
+#define KASF_FLAG_INPUT_GRAD 8  /* with TRAIN or KEEP: kasf_backward also leaves d/dx [B,T,17,3] fp32 in the workspace entry "dx_input" (x.requires_grad_()) */
 
 typedef struct kasf_model kasf_model;
 
@@ -161,6 +162,10 @@ int kasf_forward(const kasf_model* m, const float* params, const void* packed, f
 /* Gradients of a preceding kasf_forward(KASF_FLAG_TRAIN or KASF_FLAG_KEEP) on the same workspace; `flags` = the forward's flags:
  * KASF_FLAG_TRAIN selects the batch-statistics BatchNorm backward (otherwise running statistics are constants), KASF_FLAG_RETURN_REP means
  * dout is the gradient of the [B,T,17,512] representation (otherwise dout [B,T,17,3] fp32).
+ * KASF_FLAG_INPUT_GRAD (pass it to kasf_workspace_bytes, kasf_forward, kasf_backward and kasf_ws_entry alike; it has no effect without TRAIN or KEEP): the
+ * workspace ends in three more fp32 [B*T*17*3] entries, "dx_joint3", "dbone3" and "dx_input"; the last stage writes the gradient with respect to x into
+ * "dx_input" (kasf_op_input_grad's arithmetic on the input gradients of the three embeddings; found by name through kasf_ws_entry, valid once the last stage
+ * has run, bit-reproducible, once-differentiable).  Without the flag the plan, the launches and every result are what they are without it.
  * Accumulates (+=) into grads[0, live); the caller zeroes it.  Stages [stage_begin, stage_end) of
  * kasf_backward_stages() are run; call with (0, stages) for the whole backward, or stage by stage to
  * overlap the gradient all-reduce of finished ranges. */
@@ -847,6 +852,15 @@ int kasf_op_embed_bwd(int32_t dtype, const void* g, const float* in3, const floa
  * else of grads is touched. */
 int kasf_op_refusion_bwd(const kasf_model* model, const float* params, const float* x, const float* dlimb3, float* grads, int64_t frames, float* scratch,
                          int64_t scratch_floats, void* stream);
+/* backward of the prologue with respect to the keypoints (ADDED under ABI 12 as well; k_input_grad.hip, the launch kasf_backward makes under KASF_FLAG_INPUT_GRAD):
+ * x [frames,17,3] raw joints; dx_joint3, dbone3, dlimb3 [frames,17,3] = din3 of the joints / bone / limb kasf_op_embed_bwd, any of them NULL = zero; all fp32
+ * whatever the model dtype.  dx [frames,17,3] is WRITTEN:  dx = dx_joint3 + (bone decomposition)^T dbone3 + (the 51 limb MLPs' input gradients) dlimb3, where a
+ * zero-length bone, whose length the forward replaced by the constant 1, passes its direction gradient through and its length gradient nowhere.  Every element is
+ * summed in one fixed order (joints, then its bones by index, then the limb-MLP inputs that read it by group and slot): no atomics, the same bits from run to run,
+ * and a frame's dx does not depend on the other frames of the call.  dx must not overlap an input.
+ * Error 2, before any device is touched: model, params, x or dx null, frames < 1 or frames * 17 * 384 >= 2^31.  Error 4: a layout-only model. */
+int kasf_op_input_grad(const kasf_model* model, const float* params, const float* x, const float* dx_joint3, const float* dbone3, const float* dlimb3,
+                       float* dx, int64_t frames, void* stream);
 /* alpha = softmax(cat(xa, xg, xb) w^T + bias) (w [3,384], bias [3]; adaptive == 0: 1/3 each), out = sum_k alpha_k x_k.  alpha [M,4] fp32 (slot 3 unused, not
  * written) or NULL. */
 int kasf_op_gate_fwd(int32_t dtype, const void* xa, const void* xg, const void* xb, const float* w, const float* bias, void* out, float* alpha, int64_t M,

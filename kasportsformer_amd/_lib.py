@@ -27,6 +27,7 @@ DRAW_MAX_THICKNESS, DRAW_MAX_RADIUS = 64, 32
 SORT_MAX = 64                          # KASF_SORT_MAX: slots and max_dets of kasf_sort_update
 SORT_HEADER_BYTES = 64                 # KASF_SORT_HEADER_BYTES
 FLAG_TRAIN, FLAG_RETURN_REP, FLAG_KEEP = 1, 2, 4
+FLAG_INPUT_GRAD = 8                    # KASF_FLAG_INPUT_GRAD: kasf_backward also leaves d/dx in the workspace entry "dx_input"
 EVAL_COLS = 22
 LOSS7_MAX_FRAMES = 360               # KASF_LOSS7_MAX_FRAMES: n_frames of kasf_loss7
 MISC_EMBED_BWD, MISC_REFUSION_BWD, MISC_GATE_BWD, MISC_HEAD_BWD = 0, 1, 2, 3      # KASF_MISC_*: ops of kasf_op_misc_scratch_floats
@@ -131,6 +132,7 @@ SIGNATURES = {
     "kasf_op_prologue_fwd": (_i32, [_vp] * 8 + [_i64, _vp]),
     "kasf_op_embed_bwd": (_i32, [_i32] + [_vp] * 7 + [_i64, _vp, _i64, _vp]),
     "kasf_op_refusion_bwd": (_i32, [_vp] * 5 + [_i64, _vp, _i64, _vp]),
+    "kasf_op_input_grad": (_i32, [_vp] * 7 + [_i64, _vp]),
     "kasf_op_gate_fwd": (_i32, [_i32] + [_vp] * 7 + [_i64, _i32, _vp]),
     "kasf_op_gate_bwd": (_i32, [_i32] + [_vp] * 13 + [_i64, _i32, _vp, _i64, _vp]),
     "kasf_op_head_fwd": (_i32, [_i32] + [_vp] * 4 + [_i64, _vp]),
@@ -200,3 +202,13 @@ def ws_entries(handle, batch, flags):
         check(lib.kasf_ws_entry(handle, batch, flags, i, name, 256, C.byref(off), C.byref(numel), C.byref(kind)))
         out[name.value.decode()] = (off.value, numel.value, kind.value)
     return out
+
+
+def ws_last_entry(handle, batch, flags):
+    """(name, byte offset, numel, kind) of the LAST workspace entry: two plan walks instead of the one per entry that ws_entries costs (a 26-layer plan has
+    some 1,500 entries), for the hot path -- KASF_FLAG_INPUT_GRAD puts "dx_input" there."""
+    lib = load()
+    name = C.create_string_buffer(64)
+    off, numel, kind = C.c_int64(), C.c_int64(), C.c_int32()
+    check(lib.kasf_ws_entry(handle, batch, flags, lib.kasf_ws_entries(handle, batch, flags) - 1, name, 64, C.byref(off), C.byref(numel), C.byref(kind)))
+    return name.value.decode(), off.value, numel.value, kind.value

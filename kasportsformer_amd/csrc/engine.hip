@@ -82,6 +82,7 @@ struct Plan {
     int64_t x3, bone3, limb3, xj, xb, xl, rep, uv;
     std::vector<LayerWs> layers;
     int64_t g_layer, g_prev, ga, gg, gb, g_limb, g_bone, dlimb3;
+    int64_t dx_joint3 = -1, dbone3 = -1, dx_input = -1;     // KASF_FLAG_INPUT_GRAD only
     int64_t col_cap = 0;     // floats per Scratch::col
     Scratch sc[3];
     std::vector<WsEntry> entries;
@@ -275,7 +276,7 @@ void build_layout(kasf_model* m) {
 
 inline int esize(const kasf_model* m) { return m->cfg.dtype == KASF_F32 ? 4 : 2; }
 
-void build_plan(const kasf_model* m, int B, bool train, bool names, Plan& p) {
+void build_plan(const kasf_model* m, int B, bool train, bool names, Plan& p, bool input_grad = false) {
     const int L = m->cfg.n_layers, T = m->cfg.n_frames, es = esize(m);
     const int64_t M = (int64_t)B * T * 17, groupsT = (int64_t)B * 17;
     int64_t cur = 0;
@@ -363,6 +364,11 @@ void build_plan(const kasf_model* m, int B, bool train, bool names, Plan& p) {
             s.xn_b = br == 2 ? take(M * 128, 0, nm("scratch_xn_b")) : -1;
             s.rbuf = br == 1 ? take(M * 128, 0, nm("gcn_r")) : -1;
             s.duv = br == 1 ? take(M * 256, 0, nm("gcn_duv")) : -1;
+        }
+        if (input_grad) {                                // behind everything else: no other offset moves
+            p.dx_joint3 = take(M * 3, 1, "dx_joint3");
+            p.dbone3 = take(M * 3, 1, "dbone3");
+            p.dx_input = take(M * 3, 1, "dx_input");
         }
     }
     p.total = cur;
@@ -775,20 +781,20 @@ int kasf_pack_weights(const kasf_model* m, const float* params, void* packed, vo
 int64_t kasf_workspace_bytes(const kasf_model* m, int32_t batch, int32_t flags) {
     if (m == nullptr || batch < 1) return 0;
     Plan p;
-    build_plan(m, batch, (flags & (KASF_FLAG_TRAIN | KASF_FLAG_KEEP)) != 0, false, p);
+    build_plan(m, batch, (flags & (KASF_FLAG_TRAIN | KASF_FLAG_KEEP)) != 0, false, p, (flags & KASF_FLAG_INPUT_GRAD) != 0);
     return p.total;
 }
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags) {
     if (m == nullptr || batch < 1) return 0;
     Plan p;
-    build_plan(m, batch, (flags & (KASF_FLAG_TRAIN | KASF_FLAG_KEEP)) != 0, true, p);
+    build_plan(m, batch, (flags & (KASF_FLAG_TRAIN | KASF_FLAG_KEEP)) != 0, true, p, (flags & KASF_FLAG_INPUT_GRAD) != 0);
     return (int32_t)p.entries.size();
 }
 int kasf_ws_entry(const kasf_model* m, int32_t batch, int32_t flags, int32_t idx, char* name, int32_t cap, int64_t* byte_offset, int64_t* numel,
                   int32_t* elem_kind) {
     if (check_model(m)) return 2;
     Plan p;
-    build_plan(m, batch, (flags & (KASF_FLAG_TRAIN | KASF_FLAG_KEEP)) != 0, true, p);
+    build_plan(m, batch, (flags & (KASF_FLAG_TRAIN | KASF_FLAG_KEEP)) != 0, true, p, (flags & KASF_FLAG_INPUT_GRAD) != 0);
     if (idx < 0 || idx >= (int32_t)p.entries.size()) return kasf_set_error(2, "workspace entry index out of range");
     const WsEntry& e = p.entries[idx];
     if (name != nullptr && cap > 0) { strncpy(name, e.name.c_str(), cap - 1); name[cap - 1] = 0; }
@@ -828,7 +834,7 @@ int kasf_forward(const kasf_model* m, const float* params, const void* packed, f
     const bool bn_train = (flags & KASF_FLAG_TRAIN) != 0;
     const bool train = bn_train || (flags & KASF_FLAG_KEEP) != 0;        // keep every layer's activations
     Plan p;
-    build_plan(m, batch, train, false, p);
+    build_plan(m, batch, train, false, p, (flags & KASF_FLAG_INPUT_GRAD) != 0);
     if (workspace_bytes < p.total) return kasf_set_error(5, "workspace too small (see kasf_workspace_bytes)");
     Ctx c{m, params, (const char*)packed, buffers, nullptr, (char*)workspace, (hipStream_t)stream, batch, m->cfg.n_frames, m->cfg.dtype, esize(m),
           (int64_t)batch * m->cfg.n_frames * 17, train, bn_train, nullptr};
@@ -881,7 +887,8 @@ int kasf_backward(const kasf_model* m, const float* params, const void* packed, 
     const int L = m->cfg.n_layers;
     if (stage_begin < 0 || stage_end > L + 2 || stage_begin > stage_end) return kasf_set_error(2, "bad stage range");
     Plan p;
-    build_plan(m, batch, true, false, p);
+    const bool input_grad = (flags & KASF_FLAG_INPUT_GRAD) != 0;
+    build_plan(m, batch, true, false, p, input_grad);
     if (workspace_bytes < p.total) return kasf_set_error(5, "workspace too small (see kasf_workspace_bytes)");
     Ctx c{m, params, (const char*)packed, nullptr, grads, (char*)workspace, (hipStream_t)stream, batch, m->cfg.n_frames, m->cfg.dtype, esize(m),
           (int64_t)batch * m->cfg.n_frames * 17, true, (flags & KASF_FLAG_TRAIN) != 0, nullptr};
@@ -949,6 +956,8 @@ int kasf_backward(const kasf_model* m, const float* params, const void* packed, 
             const KasfProOff& po = m->pro;
             const float* src[3] = {(const float*)c.w(p.x3), (const float*)c.w(p.bone3), (const float*)c.w(p.limb3)};
             const void* gs[3] = {g_x, c.w(p.g_bone), c.w(p.g_limb)};
+            // KASF_FLAG_INPUT_GRAD: the joints and bone passes leave their input gradients as well (the limb pass always does: the refusion backward reads it)
+            float* din3[3] = {input_grad ? (float*)c.w(p.dx_joint3) : nullptr, input_grad ? (float*)c.w(p.dbone3) : nullptr, (float*)c.w(p.dlimb3)};
             // the three embedding backward passes are independent: joints and bone on the side streams, limb (+ the limb-refusion MLPs that
             // consume its input gradient) on the caller's stream
             if (!one_stream) HIPCHK(hipEventRecord(m->ev_fork, c.s));
@@ -956,7 +965,7 @@ int kasf_backward(const kasf_model* m, const float* params, const void* packed, 
                 hipStream_t st = (sidx == 2 || one_stream) ? c.s : m->side[sidx];
                 if (st != c.s) HIPCHK(hipStreamWaitEvent(st, m->ev_fork, 0));
                 kasf_launch_embed_bwd(c.dt, st, gs[sidx], src[sidx], params + po.embed_w[sidx], grads + po.embed_w[sidx], grads + po.embed_b[sidx],
-                                      grads + po.pos[sidx], sidx == 2 ? (float*)c.w(p.dlimb3) : nullptr, frames, &sinks[sidx]);
+                                      grads + po.pos[sidx], din3[sidx], frames, &sinks[sidx]);
                 if (st != c.s) HIPCHK(hipEventRecord(m->ev_join[sidx], st));
             }
             // the 204 limb-MLP tensors occupy one contiguous range of the gradient array (build_layout): a scratch row mirrors it
@@ -966,6 +975,8 @@ int kasf_backward(const kasf_model* m, const float* params, const void* packed, 
                                      (int)(rf_end - rf_base));
             if (!one_stream)
                 for (int sidx = 0; sidx < 2; ++sidx) HIPCHK(hipStreamWaitEvent(c.s, m->ev_join[sidx], 0));
+            if (input_grad)                              // the side streams have joined: d/dx from the three input gradients, on the caller's stream
+                kasf_launch_input_grad(c.s, (const float*)c.w(p.x3), params, m->d_pro, din3[0], din3[1], din3[2], (float*)c.w(p.dx_input), frames);
         }
         kasf_col_flush(c.s, sink_ptrs, 3);          // every stream of the stage has joined the caller's: finish its per-channel gradients in a fixed order
     }
@@ -1720,6 +1731,16 @@ int kasf_op_refusion_bwd(const kasf_model* m, const float* params, const float* 
     const int rc = ms.finish((hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return rc;
+}
+int kasf_op_input_grad(const kasf_model* m, const float* params, const float* x, const float* dx_joint3, const float* dbone3, const float* dlimb3, float* dx,
+                       int64_t frames, void* stream) {
+    if (check_model(m)) return 2;
+    if (!params || !x || !dx) return kasf_set_error(2, "null pointer argument");
+    MISC_FRAMES_CHECK(frames);
+    if (m->d_pro == nullptr) return kasf_set_error(4, "layout-only model cannot run");
+    kasf_launch_input_grad((hipStream_t)stream, x, params, m->d_pro, dx_joint3, dbone3, dlimb3, dx, frames);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 int kasf_op_gate_fwd(int32_t dtype, const void* xa, const void* xg, const void* xb, const float* w, const float* bias, void* out, float* alpha, int64_t M,
                      int32_t adaptive, void* stream) {

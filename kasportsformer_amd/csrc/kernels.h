@@ -142,6 +142,10 @@ void kasf_launch_embed_bwd(int dt, hipStream_t s, const void* g, const float* in
 // grad_base / grad_len: the contiguous range of the flat gradient array that holds the 204 limb-MLP tensors (one scratch row mirrors it)
 void kasf_launch_refusion_bwd(hipStream_t s, const float* x, const float* dlimb3, const float* params, float* grads, const KasfProOff* off,
                               int64_t frames, KasfColSink* sink = nullptr, int64_t grad_base = 0, int grad_len = 0);
+// ---- k_input_grad.hip: the prologue's backward with respect to the keypoints: dx [frames,17,3] = dx_joint3 + d(bone3)/dx . dbone3 + d(limb3)/dx . dlimb3, all fp32
+// (dx_joint3 / dbone3 / dlimb3 = din3 of the three kasf_launch_embed_bwd calls; a null one counts as zero).  dx is written, not accumulated ----
+void kasf_launch_input_grad(hipStream_t s, const float* x, const float* params, const KasfProOff* off, const float* dx_joint3, const float* dbone3,
+                            const float* dlimb3, float* dx, int64_t frames);
 void kasf_launch_gate_fwd(int dt, hipStream_t s, const void* xa, const void* xg, const void* xb, const float* W, const float* b, void* out,
                           float* alpha, int64_t M, int adaptive);
 void kasf_launch_gate_bwd(int dt, hipStream_t s, const void* g, const void* g1, const void* g2, const void* xa, const void* xg, const void* xb,

@@ -69,21 +69,31 @@ def _former_box(kind, dim, n_frames, mlp_ratio, ls_init, use_layer_scale=True):
 
 
 class _KasfFunction(torch.autograd.Function):
-    """Whole-model autograd node: forward and backward are single C-ABI calls."""
+    """Whole-model autograd node: forward and backward are single C-ABI calls.  The parameters' gradients go to ``model.flat_grad`` / ``p.grad`` (the node
+    returns none for ``anchor``, which only ties it to the graph); the gradient with respect to ``x`` is returned when ``x`` requires one.  Both are
+    once-differentiable."""
 
     @staticmethod
     def forward(ctx, x, anchor, model, return_rep):
-        out, ws, flags = model._launch_forward(x, return_rep=return_rep, keep=True)
-        ctx.model, ctx.ws, ctx.batch, ctx.flags = model, ws, x.shape[0], flags
+        ctx.input_grad = x.requires_grad
+        ctx.param_grads = anchor.requires_grad           # False: a frozen model, only x asks for a gradient
+        out, ws, flags = model._launch_forward(x, return_rep=return_rep, keep=True, input_grad=ctx.input_grad)
+        ctx.model, ctx.ws, ctx.batch, ctx.flags, ctx.x_shape = model, ws, x.shape[0], flags, x.shape
         return out
 
     @staticmethod
     def backward(ctx, dout):
         if ctx.ws is None:
             raise RuntimeError("Trying to backward through the graph a second time (the kept activations were freed)")
-        ctx.model._launch_backward(ctx.ws, dout, ctx.batch, ctx.flags)
+        ctx.model._launch_backward(ctx.ws, dout, ctx.batch, ctx.flags, keep_param_grads=ctx.param_grads)
+        dx = None
+        if ctx.input_grad:                               # the engine left it in the workspace (KASF_FLAG_INPUT_GRAD): a copy that outlives the workspace
+            name, off, numel, _ = _lib.ws_last_entry(ctx.model._device_handle(), ctx.batch, ctx.flags)
+            if name != "dx_input":
+                raise RuntimeError(f"the workspace plan ends in {name!r}, not in 'dx_input'")
+            dx = ctx.ws[off:off + 4 * numel].view(torch.float32).view(ctx.x_shape).clone()
         ctx.ws = None
-        return None, None, None, None
+        return dx, None, None, None
 
 
 class KASportsFormer(nn.Module):
@@ -262,12 +272,14 @@ class KASportsFormer(nn.Module):
         if x.dtype != torch.float32:
             raise RuntimeError("x must be float32")
 
-    def _launch_forward(self, x, return_rep, keep):
+    def _launch_forward(self, x, return_rep, keep, input_grad=False):
         h = self._device_handle()
         self._ensure_packed()
         x = x.contiguous()
         B = x.shape[0]
         flags = (_lib.FLAG_TRAIN if self.training else 0) | (_lib.FLAG_RETURN_REP if return_rep else 0) | (_lib.FLAG_KEEP if keep else 0)
+        if input_grad and keep:
+            flags |= _lib.FLAG_INPUT_GRAD               # three more workspace entries behind the others; the backward fills "dx_input"
         nbytes = self._lib.kasf_workspace_bytes(h, B, flags)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         out = torch.empty((B, self.n_frames, 17, 512 if return_rep else 3), dtype=torch.float32, device=x.device)
@@ -303,9 +315,16 @@ class KASportsFormer(nn.Module):
         stages["rep_logit"] = get("rep", 512)
         return out, stages
 
-    def _launch_backward(self, ws, dout, B, flags):
+    def _launch_backward(self, ws, dout, B, flags, keep_param_grads=True):
         h = self._device_handle()
         dout = dout.contiguous().float()
+        if not keep_param_grads:
+            # a frozen model whose input asks for a gradient: the engine still forms the parameter gradients on its way down (skipping those launches is not
+            # built); they land in a scratch array that is dropped -- flat_grad, every p.grad and the stage hook stay untouched
+            g = torch.zeros(self.n_flat, dtype=torch.float32, device=dout.device)
+            _lib.check(self._lib.kasf_backward(h, self._flat.data_ptr(), self._packed.data_ptr(), dout.data_ptr(), g.data_ptr(), ws.data_ptr(), ws.numel(), B,
+                                               flags, 0, self._lib.kasf_backward_stages(h), self._stream()))
+            return
         # Gradient accumulation (a second backward before the optimizer step) follows torch PER PARAMETER: a tensor whose .grad is None (never
         # touched, or zeroed by an optimizer that owns only a subset of the parameters -- e.g. fine-tuning `head` alone) restarts from this
         # pass's gradient, every other one holds the SUM -- in p.grad and in the flat array FusedAdamW reads.  The engine's finishing kernels
@@ -384,11 +403,14 @@ class KASportsFormer(nn.Module):
     # ------------------------------------------------------------------ reference interface
     def forward(self, x, return_rep=False):
         """x [B, T, 17, 3] float32 on the GPU -> [B, T, 17, 3] (or the [B, T, 17, 512] tanh features).
-        Returns a fresh writable tensor and never modifies x (train_and_evaluate_sp.py:55 mutates the output)."""
+        Returns a fresh writable tensor and never modifies x (train_and_evaluate_sp.py:55 mutates the output).
+        With grad enabled the result is differentiable (once) with respect to the parameters -- when ``pos_embed.requires_grad``, the switch for all of them --
+        and with respect to ``x`` when ``x.requires_grad``, in ``train()`` and ``eval()`` alike; a frozen model then passes the gradient through to ``x`` and
+        leaves ``flat_grad`` and every ``p.grad`` alone."""
         self._check_input(x)
         if x.shape[0] == 0:        # the reference returns an empty result in both modes (checked against it); no kernel can be launched on zero clips
             return x.new_empty((0, self.n_frames, 17, 512 if return_rep else 3))
-        if torch.is_grad_enabled() and self.pos_embed.requires_grad:
+        if torch.is_grad_enabled() and (self.pos_embed.requires_grad or x.requires_grad):
             return _KasfFunction.apply(x, self.pos_embed, self, bool(return_rep))
         out, _, _ = self._launch_forward(x, return_rep, keep=False)
         return out
