@@ -204,6 +204,51 @@ int kasf_loss7(const float* pred, const float* target, float* dpred, float* loss
 int kasf_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2, float eps,
                     float weight_decay, int32_t step_index, float grad_scale, void* stream);
 
+/* ---- AdamW over a LIST of element ranges of the flat arrays, and the global norm of the gradient over the same list (ABI 12 additions; what
+ * kasportsformer_amd.AdamW, a torch.optim.AdamW subclass with parameter groups, parameter subsets, per-parameter step counts and norm clipping, launches) ----
+ * The caller describes the elements to update by a CHUNK TABLE in device memory, `n_chunks` records of 16 bytes:
+ *   begin   element index into params / grads / exp_avg / exp_avg_sq (all four are indexed alike), any value >= 0
+ *   count   1 .. KASF_OPT_CHUNK_MAX elements; begin + count <= n
+ *   cls     0 .. n_classes - 1: whose hyper-parameters the chunk's elements take (ignored by kasf_grad_norm)
+ * The caller builds it: take every parameter that steps as a segment (offset, numel, class), merge segments that touch and share a class into runs, cut every
+ * run into pieces of at most KASF_OPT_CHUNK_MAX elements (kasportsformer_amd/optim.py: plan_chunks does exactly this).  Chunks must not overlap; their order is free
+ * for the update and fixes the summation order of the norm.  begin and count need no alignment: a chunk's elements before the first and behind the last 16-byte
+ * boundary go through scalar accesses.  Elements outside every chunk are neither read-modified nor written, in any of the arrays.  The four array bases, like
+ * kasf_adamw_step's, must be 16-byte aligned. */
+#define KASF_OPT_CHUNK_MAX 4096
+#define KASF_OPT_MAX_CLASSES 32
+typedef struct KasfOptChunk {
+    int64_t begin;
+    int32_t count;
+    int32_t cls;
+} KasfOptChunk;
+typedef struct KasfAdamwClass {
+    float lr, beta1, beta2, eps, weight_decay;
+    float bc1, bc2;      /* OUT of the caller's hands: kasf_adamw_segments forms 1 - beta^step in double from `step` below, as kasf_adamw_step does */
+    int32_t step;        /* >= 1: the step count, after its increment, of every parameter of the class */
+} KasfAdamwClass;
+typedef struct KasfAdamwClasses {
+    KasfAdamwClass c[KASF_OPT_MAX_CLASSES];
+} KasfAdamwClasses;
+
+/* One launch: for every element i of every chunk, with its class's values, kasf_adamw_step's statements with `grad_scale` replaced by
+ * s = clip ? grad_scale * clip[1] : grad_scale (one fp32 product); `clip` is kasf_grad_norm's out2 or NULL.  `classes`: n_classes HOST records, 1..32 (a caller with
+ * more splits its table into several calls), passed to the kernel by value, so changing a learning rate needs no upload.  With clip == NULL, one class and one
+ * chunked run [0, n), n a multiple of 4, the result has kasf_adamw_step's bits.  n_chunks == 0: nothing happens.
+ * Errors: 2 for a null pointer (chunks may be NULL only with n_chunks == 0), misaligned array, n < 0, n_chunks < 0, n_classes outside 1..32, a class step < 1. */
+int kasf_adamw_segments(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const KasfOptChunk* chunks /* device */, int64_t n_chunks,
+                        const KasfAdamwClass* classes /* host */, int32_t n_classes, float grad_scale, const float* clip /* device, 2 floats, nullable */,
+                        void* stream);
+
+/* Two launches: out2[0] = (float)(sqrt(sum over the chunks' elements of (double)g * (double)g) * (double)grad_scale) -- with grad_scale = 1 / world_size the norm
+ * of the averaged gradient -- and out2[1] = min(1.0f, max_norm / (out2[0] + 1e-6f)), torch.nn.utils.clip_grad_norm_'s coefficient (a NaN norm gives a NaN
+ * coefficient as it does there; max_norm = +inf measures without clipping: 1.0f exactly for a finite norm).  `partial`: n_chunks doubles of device scratch, one
+ * per chunk, each summed in an order that its chunk's (begin, count) alone fix, then added in index order through a fixed tree by one workgroup: no atomics, the
+ * same bits from run to run and for every grid width.  n_chunks == 0: nothing happens (out2 keeps its contents).
+ * Errors: 2 for a null pointer, a misaligned grads, n < 0, n_chunks < 0. */
+int kasf_grad_norm(const float* grads, int64_t n, const KasfOptChunk* chunks /* device */, int64_t n_chunks, double* partial /* device */, float grad_scale,
+                   float max_norm, float* out2 /* device, 2 floats */, void* stream);
+
 /* ---- batch assembly from a clip set resident in device memory: x_all/y_all [n_clips,T,17,3] fp32 (y_all may be NULL) ----
  * x_out[b] = x_all[index[b]] (same for y), left/right flipped (flip_data, sp_dataset.py:36-40) where flip[b] != 0 (flip may be NULL).
  * An index outside [0,n_clips) yields a zero clip. */

@@ -7,6 +7,8 @@ Public surface mirrors the reference's interface for this path:
                                         describe -- limb-length variance, limb length, limb angles, angle velocity on top of the three -- and its
                                         gradient in one launch; `train_one_epoch(lambda_limb_len=...)`)
   FusedAdamW                            optim.AdamW as used in train_and_evaluate_sp.py:270-272
+  AdamW                                 the same as a `torch.optim.AdamW` subclass that takes parameters (the reference's `filter(requires_grad)` form): groups,
+                                        subsets, `grad is None`, per-parameter steps, `lr_scheduler.*`, `max_grad_norm` clipping; one launch over a chunk table
   DataParallel                          nn.DataParallel replacement: one process per GPU, RCCL all-reduce
   joint_flip, predict_flip_tta,         utils/utilities.py:128-135, train_and_evaluate_sp.py:27-149, utils/error_calc.py:5-48
   clip_metrics, Evaluator, evaluate_one_epoch
@@ -55,7 +57,7 @@ Public surface mirrors the reference's interface for this path:
 from .model import (KASportsFormer, load_model, set_single_stream, is_single_stream, set_deterministic, is_deterministic, set_fused_attention_backward,
                     is_fused_attention_backward)
 from .functional import loss3, loss7, LOSS7_NAMES
-from .optim import FusedAdamW
+from .optim import FusedAdamW, AdamW, plan_chunks
 from .parallel import DataParallel
 from .data import PackedClips, DeviceClipLoader, pack_clip_directory, read_clip_file, shard_indices
 from .checkpoint import checkpoint_save, checkpoint_load, strip_module_prefix, adamw_state_dict, load_adamw_state_dict
@@ -76,7 +78,7 @@ from .draw import draw_poses, bgr_to_nv12, poses_to_panel, DrawResult
 from .track import SortTracker, TrackResult, TrackState
 from .tracked import TrackedLifter, TrackedTick
 
-__all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_stream", "set_deterministic", "is_deterministic", "set_fused_attention_backward", "is_fused_attention_backward", "loss3", "loss7", "LOSS7_NAMES", "FusedAdamW", "DataParallel", "joint_flip", "predict_flip_tta", "clip_metrics", "Evaluator",
+__all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_stream", "set_deterministic", "is_deterministic", "set_fused_attention_backward", "is_fused_attention_backward", "loss3", "loss7", "LOSS7_NAMES", "FusedAdamW", "AdamW", "plan_chunks", "DataParallel", "joint_flip", "predict_flip_tta", "clip_metrics", "Evaluator",
            "evaluate_one_epoch", "PackedClips", "DeviceClipLoader", "pack_clip_directory", "read_clip_file", "shard_indices",
            "checkpoint_save", "checkpoint_load", "strip_module_prefix", "adamw_state_dict", "load_adamw_state_dict", "warmup_lr", "apply_warmup", "ReduceLROnPlateau", "train_one_epoch",
            "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample",

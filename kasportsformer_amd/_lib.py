@@ -32,12 +32,22 @@ EVAL_COLS = 22
 LOSS7_MAX_FRAMES = 360               # KASF_LOSS7_MAX_FRAMES: n_frames of kasf_loss7
 MISC_EMBED_BWD, MISC_REFUSION_BWD, MISC_GATE_BWD, MISC_HEAD_BWD = 0, 1, 2, 3      # KASF_MISC_*: ops of kasf_op_misc_scratch_floats
 GCN_STAT_WORDS = 4 * 512 * 5     # KASF_GCN_STAT_WORDS: int64 words of one BatchNorm statistics buffer of kasf_op_gcn_fwd / kasf_op_gcn_bwd
+OPT_CHUNK_MAX, OPT_MAX_CLASSES = 4096, 32      # KASF_OPT_CHUNK_MAX, KASF_OPT_MAX_CLASSES: kasf_adamw_segments / kasf_grad_norm
 ABI_VERSION = 12        # kasf_version() of the library these prototypes describe (a stale in-tree .so is refused)
 
 
 class KasfConfig(C.Structure):
     _fields_ = [("n_layers", C.c_int32), ("n_frames", C.c_int32), ("num_heads", C.c_int32), ("neighbour_num", C.c_int32),
                 ("use_adaptive_fusion", C.c_int32), ("dtype", C.c_int32)]
+
+
+class KasfOptChunk(C.Structure):         # one record of the chunk table of kasf_adamw_segments / kasf_grad_norm (numpy: optim.CHUNK_DTYPE)
+    _fields_ = [("begin", C.c_int64), ("count", C.c_int32), ("cls", C.c_int32)]
+
+
+class KasfAdamwClass(C.Structure):       # bc1 / bc2 are formed by the library from `step`
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("bc1", C.c_float),
+                ("bc2", C.c_float), ("step", C.c_int32)]
 
 
 class KasfError(RuntimeError):
@@ -80,6 +90,8 @@ SIGNATURES = {
     "kasf_loss3": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _vp]),
     "kasf_loss7": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(_f32), _f32, _vp]),
     "kasf_adamw_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp]),
+    "kasf_adamw_segments": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, C.POINTER(KasfAdamwClass), _i32, _f32, _vp, _vp]),
+    "kasf_grad_norm": (_i32, [_vp, _i64, _vp, _i64, _vp, _f32, _f32, _vp, _vp]),
     "kasf_gather_clips": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "kasf_joint_flip": (_i32, [_vp, _vp, _i64, _vp]),
     "kasf_tta_merge": (_i32, [_vp, _vp, _vp, _i64, _vp]),

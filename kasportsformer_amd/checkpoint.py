@@ -8,7 +8,9 @@ writer stores ``'learning_rate'`` / ``'wandb_id'`` (:291-297) -- the reader here
 
 The optimiser entry is a genuine ``torch.optim.AdamW`` state_dict (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq`` in
 ``model.parameters()`` order, no entry for parameters that never received a gradient), built from / scattered into
-``FusedAdamW``'s flat moment arrays, so either side can resume the other's run.
+``FusedAdamW``'s flat moment arrays, so either side can resume the other's run.  A ``torch.optim.Optimizer`` -- ``kasportsformer_amd.AdamW`` or a stock
+one -- goes through its own ``state_dict()`` / ``load_state_dict()``: a file written under ``FusedAdamW`` resumes under ``AdamW(model.parameters())``, and
+the reverse whenever all its step counts agree.
 """
 from __future__ import annotations
 
@@ -25,7 +27,11 @@ def strip_module_prefix(state_dict: dict) -> dict:
 
 
 def adamw_state_dict(optimizer) -> dict:
-    """``FusedAdamW`` -> ``torch.optim.AdamW.state_dict()`` layout."""
+    """``FusedAdamW`` (or any ``torch.optim.Optimizer``, through its own ``state_dict()``) -> ``torch.optim.AdamW.state_dict()`` layout, tensors as CPU copies."""
+    if isinstance(optimizer, torch.optim.Optimizer):
+        sd = optimizer.state_dict()
+        return {"state": {k: {n: (v.detach().cpu().clone() if isinstance(v, torch.Tensor) else v) for n, v in st.items()} for k, st in sd["state"].items()},
+                "param_groups": sd["param_groups"]}
     model, g = optimizer.model, optimizer.param_groups[0]
     live = {id(p): (off, numel, shape) for p, off, numel, shape in model._live}
     state, count = {}, 0
@@ -42,7 +48,11 @@ def adamw_state_dict(optimizer) -> dict:
 
 
 def load_adamw_state_dict(optimizer, sd: dict):
-    """``torch.optim.AdamW.state_dict()`` (or ``FusedAdamW.state_dict()``) -> ``FusedAdamW``."""
+    """``torch.optim.AdamW.state_dict()`` (or ``FusedAdamW.state_dict()``) -> ``FusedAdamW``; a ``torch.optim.Optimizer`` loads the stock layout itself."""
+    if isinstance(optimizer, torch.optim.Optimizer):
+        if "exp_avg" in sd:
+            raise ValueError("FusedAdamW's own flat state_dict() cannot go into a torch.optim optimizer: save it with adamw_state_dict(optimizer)")
+        return optimizer.load_state_dict(sd)
     if "exp_avg" in sd:                                  # FusedAdamW's own flat form
         return optimizer.load_state_dict(sd)
     model = optimizer.model

@@ -1018,6 +1018,42 @@ int kasf_adamw_step(float* params, const float* grads, float* exp_avg, float* ex
     return 0;
 }
 
+static bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+int kasf_adamw_segments(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const KasfOptChunk* chunks, int64_t n_chunks,
+                        const KasfAdamwClass* classes, int32_t n_classes, float grad_scale, const float* clip, void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !classes || (!chunks && n_chunks != 0)) return kasf_set_error(2, "null pointer argument");
+    if (misaligned16(params) || misaligned16(grads) || misaligned16(exp_avg) || misaligned16(exp_avg_sq))
+        return kasf_set_error(2, "adamw_segments: the four arrays must be 16-byte aligned");
+    if (n < 0 || n_chunks < 0) return kasf_set_error(2, "adamw_segments: negative count");
+    if (n_classes < 1 || n_classes > KASF_OPT_MAX_CLASSES) return kasf_set_error(2, "adamw_segments: n_classes outside 1..KASF_OPT_MAX_CLASSES (split the table)");
+    KasfAdamwClasses by_value;
+    memset(&by_value, 0, sizeof(by_value));
+    for (int k = 0; k < n_classes; ++k) {
+        KasfAdamwClass& c = by_value.c[k];
+        c = classes[k];
+        if (c.step < 1) return kasf_set_error(2, "adamw_segments: a class's step must be >= 1");
+        // torch.optim.AdamW forms the bias corrections in double, as kasf_adamw_step above
+        c.bc1 = (float)(1.0 - pow((double)c.beta1, (double)c.step));
+        c.bc2 = (float)(1.0 - pow((double)c.beta2, (double)c.step));
+    }
+    if (n_chunks == 0) return 0;
+    kasf_launch_adamw_segments((hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, chunks, n_chunks, by_value, grad_scale, clip, KASF_OPT_GRID_CAP);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int kasf_grad_norm(const float* grads, int64_t n, const KasfOptChunk* chunks, int64_t n_chunks, double* partial, float grad_scale, float max_norm, float* out2,
+                   void* stream) {
+    if (!grads || !out2 || ((!chunks || !partial) && n_chunks != 0)) return kasf_set_error(2, "null pointer argument");
+    if (misaligned16(grads)) return kasf_set_error(2, "grad_norm: grads must be 16-byte aligned");
+    if (n < 0 || n_chunks < 0) return kasf_set_error(2, "grad_norm: negative count");
+    if (n_chunks == 0) return 0;
+    kasf_launch_grad_norm((hipStream_t)stream, grads, chunks, n_chunks, partial, grad_scale, max_norm, out2, KASF_OPT_GRID_CAP);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 int kasf_gather_clips(const float* x_all, const float* y_all, const int64_t* index, const uint8_t* flip, int64_t n_clips, int32_t batch,
                       int32_t n_frames, float* x_out, float* y_out, void* stream) {
     if (!x_all || !index || !x_out || (y_all && !y_out)) return kasf_set_error(2, "null pointer argument");

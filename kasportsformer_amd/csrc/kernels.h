@@ -171,6 +171,16 @@ void kasf_launch_loss7(hipStream_t s, const float* pred, const float* tgt, float
 void kasf_launch_adamw(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float wd,
                        float bc1, float bc2, float grad_scale);
 
+// ---- k_optim.hip: AdamW and the global gradient norm over a chunk table (kasf.h: kasf_adamw_segments, kasf_grad_norm); the arrays' bases 16-byte aligned,
+// `grid_cap` workgroups at most (the results do not depend on it); n_chunks < 1: no launch ----
+struct KasfOptChunk;
+struct KasfAdamwClasses;
+#define KASF_OPT_GRID_CAP 2048
+void kasf_launch_adamw_segments(hipStream_t s, float* p, const float* g, float* m, float* v, const KasfOptChunk* chunks, int64_t n_chunks,
+                                const KasfAdamwClasses& classes, float grad_scale, const float* clip, int grid_cap);
+void kasf_launch_grad_norm(hipStream_t s, const float* g, const KasfOptChunk* chunks, int64_t n_chunks, double* partial, float grad_scale, float max_norm,
+                           float* out2, int grid_cap);
+
 // ---- k_eval.hip ----
 void kasf_launch_joint_flip(hipStream_t s, const float* src, float* dst, int64_t rows);
 void kasf_launch_tta_merge(hipStream_t s, const float* p, const float* pf, float* out, int64_t rows);

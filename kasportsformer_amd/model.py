@@ -9,6 +9,8 @@ shared library, raises.
 from __future__ import annotations
 
 import ctypes as C
+import itertools
+import weakref
 from collections import OrderedDict
 
 import torch
@@ -19,6 +21,21 @@ from . import _lib
 BLOCK_KINDS = ("att_spatial", "att_temporal", "graph_spatial", "graph_temporal", "bone_spatial", "bone_temporal")
 # modules/bone_refusion.py:34-40 (sizes only; the indices live in the kernels)
 _LIMB_SIZES = (3, 3, 2, 2, 3, 3, 4, 4, 4, 4, 3, 4, 4, 4, 4, 2, 2)
+
+
+# What leads from an nn.Parameter back to its model (kasportsformer_amd.AdamW takes parameters, not the model): _flatten leaves (token, element offset) on every
+# parameter -- two ints, so a parameter still pickles and copies -- and the token finds the model here for as long as it lives.
+_MODELS = weakref.WeakValueDictionary()
+_TOKENS = itertools.count(1)
+
+
+def parameter_owner(p):
+    """``(model, element offset into model._flat)`` of a parameter of a live ``KASportsFormer``; ``(None, None)`` for any other tensor."""
+    slot = getattr(p, "_kasf_slot", None)
+    if slot is None:
+        return None, None
+    model = _MODELS.get(slot[0])
+    return (model, slot[1]) if model is not None else (None, None)
 
 
 class _Box(nn.Module):
@@ -182,6 +199,8 @@ class KASportsFormer(nn.Module):
         self._packed = None
         self._packed_dirty = True
         self.static_weights = False         # True: trust mark_weights_dirty() instead of re-packing on every forward (inference serving)
+        self._token = next(_TOKENS)
+        _MODELS[self._token] = self
         self._flatten()
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.mark_weights_dirty())
 
@@ -197,6 +216,7 @@ class KASportsFormer(nn.Module):
             view = flat[off:off + p.numel()].view(shape)
             view.copy_(p.data)
             p.data = view
+            p._kasf_slot = (self._token, off)
             if off < self.n_live:
                 self._live.append((p, off, p.numel(), tuple(shape)))
         self._const_index = None
