@@ -37,6 +37,8 @@
  *                             demo/lib/hrnet/lib/utils/transforms.py:50-101, demo/lib/hrnet/lib/utils/utilitys.py:102-135
  *   kasf_heatmap_flip_keypoints <- the same behind HRNet's flip test: flip_back with the left / right pairs, SHIFT_HEATMAP, the float32 average
  *                             demo/lib/hrnet/lib/utils/transforms.py:15-30, demo/lib/hrnet/experiments/w48_384x288_adam_lr1e-3.yaml:119-121
+ *   kasf_heatmap_decode    <- the same two decodes with DARK (Zhang et al., CVPR 2020; mmpose post_process = 'unbiased') or DARK-UDP (Huang et al., CVPR
+ *                             2020; mmpose post_dark_udp, ViTPose) sub-pixel refinement and the UDP W - 1 / H - 1 affine; not in the demo, whose HRNet uses neither
  *   kasf_detect_boxes      <- predict_transform, write_results (objectness threshold, class arg-max, persons only, sort, greedy NMS) and the un-letterbox of
  *                             yolo_human_det: what the demo does between the YOLOv3 network's output and the person boxes
  *                             demo/lib/yolov3/util.py:34-81,107-225, demo/lib/yolov3/bbox.py:51-78, demo/lib/yolov3/human_detector.py:116-168
@@ -415,6 +417,59 @@ int kasf_heatmap_flip_keypoints(const void* hm, const void* hm_flipped, int32_t 
                                 const int32_t* partner /* host, 17 entries, NULL = COCO pairs */, int32_t shift,
                                 const float* geom, int32_t geom_kind, double aspect, int32_t refine, int32_t out_layout,
                                 float* out, float* coco_scratch, float* merged_out /* may be NULL */, void* stream);
+
+/* ---- pose-network heatmaps -> keypoints with DARK / UDP sub-pixel refinement (ADDED under ABI 12: additive, kasf_version() stays 12; look it up by name) ----
+ * kasf_heatmap_keypoints (hm_flipped = NULL) or kasf_heatmap_flip_keypoints (hm_flipped given) with the refinement and the affine that ViTPose and the *_dark /
+ * *_udp HRNet checkpoints are trained and evaluated with, in the same ONE launch: the quarter-pixel rule is off by up to a quarter of a heatmap pixel by
+ * construction, these are not.  The library is built with -ffp-contract=off and every rule below names its precision and order, so a numpy restatement performs
+ * the same IEEE operations (tests/test_heatmap_dark_cpu.py) and the device is held to it bit for bit.
+ *   mode      KASF_DECODE_QUARTER   kasf_heatmap_keypoints' refine rule (with udp = 0 the call computes what the existing entries compute)
+ *             KASF_DECODE_DARK      DARK, Zhang et al., CVPR 2020 "Distribution-Aware Coordinate Representation": mmpose's post_process = 'unbiased'
+ *             KASF_DECODE_DARK_UDP  the DARK step of UDP, Huang et al., CVPR 2020 "The Devil is in the Details": mmpose's post_dark_udp, what ViTPose's
+ *                                   use_udp = True, modulate_kernel = 11 selects
+ *   common    the argmax (py, px) and the score bv come from the RAW map -- from the merged map under hm_flipped, merged exactly as kasf_heatmap_flip_keypoints
+ *             merges --, by the total order and the "bv > 0" mask of kasf_heatmap_keypoints; with a false mask the coordinates are 0 and no step is made.  16-bit
+ *             inputs are widened exactly; raw(y, x) below is that map's value as fp32.
+ *   weights   w[0 .. K - 1], K odd, 1 <= K <= 17: the separable Gaussian, a HOST array read during the call and passed by value into the launch (unread with
+ *             KASF_DECODE_QUARTER).  The Python helper gaussian_weights(K, sigma) computes them in fp64 and rounds once to fp32: without sigma and for K = 1, 3, 5, 7
+ *             OpenCV's fixed tables [1], [.25, .5, .25], [.0625, .25, .375, .25, .0625], [.03125, .109375, .21875, .28125, .21875, .109375, .03125]; otherwise
+ *             sigma = ((K - 1) * 0.5 - 1) * 0.3 + 0.8 when none is given, w_i = exp(-(i - (K - 1) / 2)^2 / (2 sigma^2)), divided by their sum.
+ *   blur      blur(y, x), fp32, separable, horizontal first, r = K / 2: h(yy) = sum over kh = 0 .. K - 1, ascending, of w[kh] * raw_b(yy, x + kh - r); blur = sum
+ *             over kv = 0 .. K - 1, ascending, of w[kv] * h(y + kv - r); each product rounded, then added, accumulators starting at 0.0f.  raw_b is the border
+ *             rule: DARK zero outside the map (mmpose zero-pads by r, so OpenCV's own border never enters); DARK_UDP reflect-101 (-i -> i, n - 1 + i -> n - 1 - i),
+ *             repeated with period 2 (n - 1) for maps narrower than the radius, n = 1 always reading index 0.  DARK deliberately omits mmpose's renormalisation
+ *             "* origin_max / max(blurred)": a constant factor, hence an additive constant after the logarithm, which cancels in every difference below; it could
+ *             matter only through the 1e-10 clamp.
+ *   log       L(v), fp64, the library's own routine: frexp gives m in [0.5, 1) and e; if m < 0.7071067811865476 then m = 2 m, e = e - 1; s = (m - 1) / (m + 1),
+ *             z = s * s; p by Horner from 1 / 23 down over the odd denominators 21, 19, ... 1, each step p = p * z + 1.0 / d; L = e * 0.6931471805599453 +
+ *             2.0 * s * p.  +inf and NaN are returned as they are.  Within 4.4e-16 relative of the correctly rounded logarithm on [1e-10, 50].
+ *             clamps: max(v, lo) = v < lo ? lo : v and min(v, hi) = v > hi ? hi : v, so a NaN stays a NaN.
+ *   DARK      made only if 1 < px < W - 2 and 1 < py < H - 2.  g(dy, dx) = L(max((double)blur(py + dy, px + dx), 1e-10));
+ *             gx = 0.5 * (g(0,1) - g(0,-1)), gy = 0.5 * (g(1,0) - g(-1,0)); a = 0.25 * (g(0,2) - 2 g(0,0) + g(0,-2)), d = 0.25 * (g(2,0) - 2 g(0,0) + g(-2,0)),
+ *             b = 0.25 * (g(1,1) - g(-1,1) - g(1,-1) + g(-1,-1)); det = a * d - b * b; if det == 0 there is no step.
+ *   DARK_UDP  always made.  g(dy, dx) = L(min(max((double)blur(clamp(py + dy, 0, H - 1), clamp(px + dx, 0, W - 1)), 0.001), 50.0)), the clamp of the position
+ *             being mmpose's edge padding of the blurred map; gx, gy as above; a = g(0,1) - 2 g(0,0) + g(0,-1) + eps, d = g(1,0) - 2 g(0,0) + g(-1,0) + eps,
+ *             b = 0.5 * (g(1,1) - g(0,1) - g(1,0) + g(0,0) + g(0,0) - g(0,-1) - g(-1,0) + g(-1,-1)), eps = 2^-23; det = a * d - b * b.
+ *   step      fp64, left to right as written: x = px - (d * gx - b * gy) / det, y = py - (a * gy - b * gx) / det.  Nothing bounds the step, as in both
+ *             published procedures; infinities and NaNs propagate.
+ *   to image  udp = 0: kasf_heatmap_keypoints' affine, cx + (x - W / 2) kx and cy + (y - H / 2) ky.  udp != 0 (H, W >= 2): sw = fl32(scale_x * 200),
+ *             sh = fl32(scale_y * 200), x_img = fl32((double)cx + (x - (W - 1) * 0.5) * ((double)sw / (W - 1))), y_img likewise with sh, H, cy: heatmap
+ *             coordinates over W - 1 / H - 1 intervals, each axis by its own scale.  x, y stay fp64 from the step to this single rounding.  udp with
+ *             KASF_DECODE_QUARTER is allowed.  UDP on the crop side is not part of this entry: udp is for crops the caller made the UDP way.
+ * hm_flipped, partner, shift, merged_out: as kasf_heatmap_flip_keypoints takes them; hm_flipped = NULL means no flip test, and partner (checked when given), shift
+ * are then unused and merged_out must be NULL.  geom, geom_kind, aspect, out_layout, out, coco_scratch, stream: as kasf_heatmap_keypoints takes them.  One launch,
+ * plus kasf_coco_h36m's for KASF_LAYOUT_H36M; nothing is allocated.  n = 0 does nothing.  Error 2, before a device or a pointer is touched: every refusal of the two
+ * existing entries, a mode out of range, K even or outside 1 .. 17, weights NULL with a mode other than KASF_DECODE_QUARTER, udp with H < 2 or W < 2.
+ * NOT VERIFIED: the rules restate mmpose's two procedures and OpenCV's GaussianBlur (its kernel tables, its sigma rule, its reflect-101 border) from their published
+ * arithmetic; neither mmpose nor an OpenCV build was available to record a decode from, and cv2's SIMD blur may round differently, so equality with a particular
+ * mmpose / cv2 build is not verified and no bit equality with one is claimed. */
+#define KASF_DECODE_QUARTER 0
+#define KASF_DECODE_DARK 1
+#define KASF_DECODE_DARK_UDP 2
+int kasf_heatmap_decode(const void* hm, const void* hm_flipped /* NULL: no flip test */, int32_t dtype, int64_t n, int32_t H, int32_t W,
+                        const int32_t* partner /* host, 17 entries, NULL = COCO pairs */, int32_t shift,
+                        const float* geom, int32_t geom_kind, double aspect, int32_t mode, const float* weights /* host, K floats, read during the call */,
+                        int32_t K, int32_t udp, int32_t out_layout, float* out, float* coco_scratch, float* merged_out /* may be NULL */, void* stream);
 
 /* ---- YOLOv3 detector output -> person boxes in frame pixels (ADDED under ABI 12: additive, kasf_version() stays 12; a library without it fails to load on the
  * missing symbol).  Replaces, on the device and without a host synchronisation, what yolo_human_det does behind the detector network (human_detector.py:116-168):

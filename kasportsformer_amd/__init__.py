@@ -31,6 +31,9 @@ Public surface mirrors the reference's interface for this path:
   heatmaps_to_keypoints(flipped=...)    demo/lib/hrnet/lib/utils/transforms.py:15-30, demo/lib/hrnet/experiments/w48_384x288_adam_lr1e-3.yaml:119-121 (the flip test:
                                         the network's output for the mirrored crops mirrored back, left / right maps swapped, shifted one column,
                                         averaged with the direct output in float32 and decoded, in one launch; `push_heatmaps(flipped=...)`)
+  heatmaps_to_keypoints(decode=...),    not in the demo: DARK (Zhang et al., CVPR 2020) and DARK-UDP (Huang et al., CVPR 2020) sub-pixel refinement and the UDP
+  gaussian_weights                      affine, what ViTPose and the *_dark / *_udp HRNet checkpoints are evaluated with, in the same one launch (a Gaussian blur
+                                        and a logarithm around the argmax only, one Newton step; `push_heatmaps(decode=...)`)
   letterbox_frames, LetterboxResult     demo/lib/yolov3/preprocess.py:9-38, demo/lib/yolov3/human_detector.py:131 (video frames -> the YOLOv3 network's input, on the
                                         device: letterbox with bicubic resampling onto a canvas of 128, channel reversal, planes, / 255; one launch,
                                         reads the decoder's frame in place; its width / height are what `yolo_heads_to_boxes` takes)
@@ -69,7 +72,7 @@ from .slicing import slice_source, split_clips, mysplit_clips, resample
 from .lift import lift_track, lift_tracks, window_plan
 from .stream import StreamLifter
 from .pose import coco_to_h36m, poses_to_world, DEMO_CAMERA_ROTATION
-from .heatmap import heatmaps_to_keypoints
+from .heatmap import heatmaps_to_keypoints, gaussian_weights
 from .detect import detections_to_boxes, yolo_heads_to_boxes, DetectResult, YOLOV3_ANCHORS, YOLOV3_MASKS
 from .crop import crop_persons, CropResult
 from .letterbox import letterbox_frames, LetterboxResult
@@ -82,6 +85,6 @@ __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_strea
            "evaluate_one_epoch", "PackedClips", "DeviceClipLoader", "pack_clip_directory", "read_clip_file", "shard_indices",
            "checkpoint_save", "checkpoint_load", "strip_module_prefix", "adamw_state_dict", "load_adamw_state_dict", "warmup_lr", "apply_warmup", "ReduceLROnPlateau", "train_one_epoch",
            "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample",
-           "lift_track", "lift_tracks", "window_plan", "StreamLifter", "coco_to_h36m", "poses_to_world", "DEMO_CAMERA_ROTATION", "heatmaps_to_keypoints",
+           "lift_track", "lift_tracks", "window_plan", "StreamLifter", "coco_to_h36m", "poses_to_world", "DEMO_CAMERA_ROTATION", "heatmaps_to_keypoints", "gaussian_weights",
            "detections_to_boxes", "yolo_heads_to_boxes", "DetectResult", "YOLOV3_ANCHORS", "YOLOV3_MASKS", "crop_persons", "CropResult", "letterbox_frames", "LetterboxResult", "yuv_to_bgr", "nv12_to_bgr", "i420_to_bgr", "SortTracker", "TrackResult", "TrackState",
            "TrackedLifter", "TrackedTick", "draw_poses", "bgr_to_nv12", "poses_to_panel", "DrawResult"]

@@ -16,6 +16,7 @@ DTYPE_F32, DTYPE_BF16 = 0, 1
 DTYPE_F16 = 2                          # KASF_DTYPE_F16: heatmap / detector input and crop output only, no model runs in it
 GEOM_CENTER_SCALE, GEOM_BOX = 0, 1
 LAYOUT_COCO, LAYOUT_H36M = 0, 1
+DECODE_QUARTER, DECODE_DARK, DECODE_DARK_UDP = 0, 1, 2   # KASF_DECODE_*: the mode of kasf_heatmap_decode
 ROWS_PERSONS, ROWS_TRACKS = 0, 1         # KASF_ROWS_*: row order of kasf_stream_track_front
 DETECT_PREDICTION, DETECT_HEADS = 0, 1
 DETECT_MAX_CANDIDATES = 4096           # KASF_DETECT_MAX_CANDIDATES
@@ -112,6 +113,7 @@ SIGNATURES = {
     "kasf_pose_world": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "kasf_heatmap_keypoints": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i32, C.c_double, _i32, _i32, _vp, _vp, _vp]),
     "kasf_heatmap_flip_keypoints": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _vp, _i32, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "kasf_heatmap_decode": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _vp, _i32, C.c_double, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "kasf_crop_persons": (_i32, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _i32, C.c_double, _i64, _vp, _i32, _i32, _i32, C.POINTER(_f32), _i32, _vp, _vp]),
     "kasf_letterbox_plan": (_i32, [_i32, _i32, _i32, _i32, _pi32, _pi32, _pi32, _pi32]),
     "kasf_letterbox_frames": (_i32, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -1315,6 +1315,39 @@ int kasf_heatmap_flip_keypoints(const void* hm, const void* hm_flipped, int32_t 
     return 0;
 }
 
+// ---- DARK / UDP sub-pixel heatmap decode (kasf.h, kasf_heatmap_decode) ----
+int kasf_heatmap_decode(const void* hm, const void* hm_flipped, int32_t dtype, int64_t n, int32_t H, int32_t W, const int32_t* partner, int32_t shift,
+                        const float* geom, int32_t geom_kind, double aspect, int32_t mode, const float* weights, int32_t K, int32_t udp, int32_t out_layout,
+                        float* out, float* coco_scratch, float* merged_out, void* stream) {
+    static const int32_t coco_pairs[17] = {0, 2, 1, 4, 3, 6, 5, 8, 7, 10, 9, 12, 11, 14, 13, 16, 15};
+    if (heatmap_refusal("heatmap_decode", n, H, W, dtype, geom_kind, out_layout, aspect)) return 2;
+    if (mode != KASF_DECODE_QUARTER && mode != KASF_DECODE_DARK && mode != KASF_DECODE_DARK_UDP)
+        return kasf_set_error(2, "heatmap_decode: mode must be KASF_DECODE_QUARTER, _DARK or _DARK_UDP");
+    if (K < 1 || K > 17 || K % 2 == 0) return kasf_set_error(2, "heatmap_decode: K must be odd and in [1, 17]");
+    if (mode != KASF_DECODE_QUARTER && !weights) return kasf_set_error(2, "heatmap_decode: weights must be given with KASF_DECODE_DARK and _DARK_UDP");
+    if (udp && (H < 2 || W < 2)) return kasf_set_error(2, "heatmap_decode: udp needs H and W >= 2");
+    const int32_t* pt = partner ? partner : coco_pairs;
+    if (hm_flipped || partner) {
+        for (int j = 0; j < 17; ++j)
+            if (pt[j] < 0 || pt[j] > 16) return kasf_set_error(2, "heatmap_decode: partner entries must be in [0, 16]");
+        for (int j = 0; j < 17; ++j)
+            if (pt[pt[j]] != j) return kasf_set_error(2, "heatmap_decode: partner must be an involution (partner[partner[j]] == j)");
+    }
+    if (n == 0) return 0;
+    if (!hm || !geom || !out || (out_layout == KASF_LAYOUT_H36M && !coco_scratch)) return kasf_set_error(2, "null pointer argument");
+    if (merged_out && !hm_flipped) return kasf_set_error(2, "heatmap_decode: merged_out goes with hm_flipped");
+    if (merged_out && ((const void*)merged_out == hm || (const void*)merged_out == hm_flipped))
+        return kasf_set_error(2, "heatmap_decode: merged_out must not overlap hm or hm_flipped");
+    const bool h36m = out_layout == KASF_LAYOUT_H36M;
+    int pv[17];
+    for (int j = 0; j < 17; ++j) pv[j] = pt[j];
+    kasf_launch_heatmap_decode((hipStream_t)stream, hm, hm_flipped, dtype, n, H, W, pv, shift ? 1 : 0, geom, geom_kind, aspect, mode, weights, K, udp ? 1 : 0,
+                               h36m ? coco_scratch : out, merged_out);
+    if (h36m) kasf_launch_coco_h36m((hipStream_t)stream, coco_scratch, n, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // ---- person boxes -> pose-network inputs (kasf.h, kasf_crop_persons) ----
 int kasf_crop_persons(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, const int32_t* frame_index,
                       const float* geom, int32_t geom_kind, double aspect, int64_t n, void* out, int32_t out_dtype, int32_t out_w, int32_t out_h,

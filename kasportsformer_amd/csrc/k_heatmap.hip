@@ -280,7 +280,334 @@ void launch_flip(hipStream_t s, const void* hm, const void* hmf, int64_t maps, i
         hipLaunchKernelGGL((k_heatmap_flip_keypoints<E, ELEM>), grid, block, 0, s, a, b, maps, H, W, partner, shift, geom, geom_kind, aspect, refine, out, merged_out);
 }
 
+// ---- DARK / UDP sub-pixel decode (kasf.h, kasf_heatmap_decode) ----
+//   DARK      Zhang et al., CVPR 2020: blur the map, take its logarithm, one Newton step from the argmax (mmpose's post_process = 'unbiased')
+//   DARK-UDP  Huang et al., CVPR 2020: the same step on a 3 x 3 stencil with reflected borders (mmpose's post_dark_udp), and the W - 1 / H - 1 affine
+// Argmax and score come from the RAW map in both, so the streaming pass above is all the map-sized work there is; the blurred, logged map is needed at the
+// (2R + 1)^2 points around the argmax only (R = 2 for DARK, 1 for DARK-UDP), each a K x K window of raw values that the pass has just streamed (L2-hot).
+// MAPPING.  The same one wavefront per map.  Behind wave_first every lane knows the argmax, and the whole wave evaluates the stencil, in wave-uniform control
+// flow that does not depend on the map (an argmax on the border, a false mask: evaluated all the same, and not used), before lanes 1 .. 63 leave:
+//   1 the horizontal sums h(row, col), col one of the 2R + 1 stencil columns, row one of the K + 2R rows the stencil's vertical sums touch: (2R + 1)(K + 2R) <= 105
+//     ordered K-tap sums, one per lane, in up to two rounds of 64 (sum i sits in lane i & 63 of round i >> 6);
+//   2 lane p < (2R + 1)^2 owns stencil point (p / (2R + 1) - R, p % (2R + 1) - R): its vertical sum takes the K horizontal sums it needs through __shfl, in
+//     ascending order, then the clamp and the logarithm in fp64 (25 or 9 lanes at once; the step uses 13 or 7 of them);
+//   3 13 or 7 fp64 shuffles hand those to lane 0, which makes the step, applies the affine and stores.
+// No LDS, no second pass, no extra launch; the weights travel by value in the kernel arguments.  The streaming loops are the existing kernels' loops, restated as
+// functions: moving the existing kernels themselves onto these functions changed their generated code (compare signedness, operand order), so they keep theirs.
+constexpr int DM_QUARTER = 0, DM_DARK = 1, DM_UDP = 2;          // KASF_DECODE_*
+
+struct Blur {                                                   // the separable Gaussian: K odd, 1 .. 17, weights w[0 .. K - 1] (the rest 0)
+    float w[17];
+    int K;
+};
+
+// one lane's share of one map, streamed: its first pair under comes_first (k_heatmap_keypoints' loop)
+template <class E, bool VEC>
+__device__ inline Best stream_map(const typename Elem<E>::T* __restrict__ map, int HW, int lane) {
+    using T = typename Elem<E>::T;
+    constexpr int VW = Elem<E>::VW;
+    float bv = -INFINITY;
+    int bi = INT_MAX;
+    if (VEC) {
+        struct alignas(16) Vec { T e[VW]; };
+        const Vec* __restrict__ map_v = reinterpret_cast<const Vec*>(map);
+        const int nvec = HW / VW;
+#pragma unroll 4
+        for (int v = lane; v < nvec; v += 64) {
+            const Vec x = map_v[v];
+#pragma unroll
+            for (int k = 0; k < VW; ++k) {
+                const float f = Elem<E>::up(x.e[k]);
+                if (comes_first(f, v * VW + k, bv, bi)) { bv = f; bi = v * VW + k; }
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int i = lane; i < HW; i += 64) {
+            const float f = Elem<E>::up(map[i]);
+            if (comes_first(f, i, bv, bi)) { bv = f; bi = i; }
+        }
+    }
+    return {bv, bi};
+}
+
+// one lane's share of one merged map, streamed (and stored when mo is given): its first pair under comes_first (k_heatmap_flip_keypoints' loop)
+template <class E, int MODE>
+__device__ inline Best stream_merged(const typename Elem<E>::T* __restrict__ map, const typename Elem<E>::T* __restrict__ fmap, float* __restrict__ mo, int HW,
+                                     int W, int shift, int lane) {
+    using T = typename Elem<E>::T;
+    constexpr int VW = Elem<E>::VW;
+    float bv = -INFINITY;
+    int bi = INT_MAX;
+    if (MODE != ELEM) {
+        struct alignas(16) Vec { T e[VW]; };
+        const Vec* __restrict__ map_v = reinterpret_cast<const Vec*>(map);
+        const Vec* __restrict__ fmap_v = reinterpret_cast<const Vec*>(fmap);
+        const int nvec = HW / VW;
+#pragma unroll 2
+        for (int v = lane; v < nvec; v += 64) {
+            const int i0 = v * VW;
+            const Vec a = map_v[v];
+            float f[VW];
+            if (MODE == ROW) {
+                const int y = (int)((unsigned)i0 / (unsigned)W), x = i0 - y * W;
+                const int row = y * W, mirror = W - x - VW;                 // a multiple of VW: the aligned vector that holds columns W - x - VW .. W - x - 1
+                const Vec b = fmap_v[(row + mirror) / VW];
+                if (shift) {
+                    f[0] = merge(Elem<E>::up(a.e[0]), Elem<E>::up(fmap[row + min(W - x, W - 1)]));
+#pragma unroll
+                    for (int k = 1; k < VW; ++k) f[k] = merge(Elem<E>::up(a.e[k]), Elem<E>::up(b.e[VW - k]));
+                } else {
+#pragma unroll
+                    for (int k = 0; k < VW; ++k) f[k] = merge(Elem<E>::up(a.e[k]), Elem<E>::up(b.e[VW - 1 - k]));
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < VW; ++k) f[k] = merge(Elem<E>::up(a.e[k]), Elem<E>::up(fmap[flipped_index(i0 + k, W, shift)]));
+            }
+#pragma unroll
+            for (int k = 0; k < VW; ++k)
+                if (comes_first(f[k], i0 + k, bv, bi)) { bv = f[k]; bi = i0 + k; }
+            if (mo) {
+#pragma unroll
+                for (int q = 0; q < VW / 4; ++q) {
+                    Float4 o;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) o.e[k] = f[q * 4 + k];
+                    *reinterpret_cast<Float4*>(mo + i0 + q * 4) = o;
+                }
+            }
+        }
+    } else {
+#pragma unroll 2
+        for (int i = lane; i < HW; i += 64) {
+            const float f = merge(Elem<E>::up(map[i]), Elem<E>::up(fmap[flipped_index(i, W, shift)]));
+            if (comes_first(f, i, bv, bi)) { bv = f; bi = i; }
+            if (mo) mo[i] = f;
+        }
+    }
+    return {bv, bi};
+}
+
+// reflect-101 of any index onto 0 .. n - 1: -i -> i, n - 1 + i -> n - 1 - i, with period 2 (n - 1); n = 1 always reads index 0
+__device__ inline int reflect101(int i, int n) {
+    if (n == 1) return 0;
+    const int period = 2 * (n - 1);
+    i %= period;
+    if (i < 0) i += period;
+    return i < n ? i : period - i;
+}
+
+// kasf.h's L(v): the natural logarithm in fp64 by the library's own routine (argument reduction to [sqrt(1/2), sqrt(2)), the atanh series to z^11 in s = (m - 1) /
+// (m + 1)), so that the device and a numpy restatement agree bit for bit; +inf and NaN come back as they are.  v is positive (clamped by the caller) or NaN.
+__device__ inline double log_own(double v) {
+    if (!(v < (double)INFINITY)) return v;
+    int e;
+    double m = frexp(v, &e);
+    if (m < 0.7071067811865476) { m = 2.0 * m; e = e - 1; }
+    const double s = (m - 1.0) / (m + 1.0), z = s * s;
+    double p = 1.0 / 23.0;
+#pragma unroll
+    for (int d = 21; d >= 1; d -= 2) p = p * z + 1.0 / (double)d;
+    return (double)e * 0.6931471805599453 + 2.0 * s * p;
+}
+
+// The blurred, clamped, logged map at the stencil points around (py, px), by the whole wave: lane p < (2R + 1)^2 returns g(p / (2R + 1) - R, p % (2R + 1) - R),
+// the other lanes a value nobody reads.  at(row, col) as finish takes it.  Every collective below is reached by all 64 lanes, the same number of times for
+// every map of a launch.
+template <class At>
+__device__ inline double stencil_logs(int py, int px, int H, int W, int mode, const Blur& bl, int lane, At at) {
+    const int K = bl.K, r = K / 2;
+    const int R = mode == DM_DARK ? 2 : 1, NC = 2 * R + 1, NR = K + 2 * R, NH = NC * NR;      // NH <= 5 * 21
+    // 1: horizontal sums, fp32, taps in ascending order, each product rounded and then added
+    float h[2] = {0.0f, 0.0f};
+#pragma unroll
+    for (int round = 0; round < 2; ++round) {
+        const int i = round * 64 + lane;
+        if (i < NH) {
+            const int c = i / NR, t = i - c * NR;
+            const int yy = py - R - r + t, x0 = px - R + c - r;
+            float acc = 0.0f;
+            if (mode == DM_DARK) {                              // zero outside the map
+                const bool row_in = 0 <= yy && yy < H;
+                const int row = row_in ? yy * W : 0;
+                for (int kh = 0; kh < K; ++kh) {
+                    const int xx = x0 + kh;
+                    const float v = row_in && 0 <= xx && xx < W ? at(row, xx) : 0.0f;
+                    acc = acc + bl.w[kh] * v;
+                }
+            } else {                                            // reflect-101
+                const int row = reflect101(yy, H) * W;
+                for (int kh = 0; kh < K; ++kh) acc = acc + bl.w[kh] * at(row, reflect101(x0 + kh, W));
+            }
+            h[round] = acc;
+        }
+    }
+    // 2: vertical sums, the same way, then the clamp and the logarithm
+    const int p = lane < NC * NC ? lane : 0;
+    int y = py + p / NC - R, x = px + p % NC - R;
+    if (mode == DM_UDP) {                                       // mmpose's edge padding of the blurred map
+        y = min(max(y, 0), H - 1);
+        x = min(max(x, 0), W - 1);
+    }
+    const int first = (x - (px - R)) * NR + (y - (py - R));     // this point's topmost horizontal sum
+    float acc = 0.0f;
+    for (int kv = 0; kv < K; ++kv) {
+        const int i = first + kv;
+        float v = __shfl(h[0], i & 63);
+        if (NH > 64) {
+            const float v1 = __shfl(h[1], i & 63);
+            v = i >= 64 ? v1 : v;
+        }
+        acc = acc + bl.w[kv] * v;
+    }
+    double b = (double)acc;
+    if (mode == DM_DARK) {
+        b = b < 1e-10 ? 1e-10 : b;
+    } else {
+        b = b < 0.001 ? 0.001 : b;
+        b = b > 50.0 ? 50.0 : b;
+    }
+    return log_own(b);
+}
+
+// finish for kasf_heatmap_decode, reached by the whole wave: the stencil (modes 1, 2) by all lanes, then lane 0 alone -- the step, the affine, the store.
+template <class At>
+__device__ inline void finish_decode(float bv, int bi, int lane, int64_t m, int64_t person, int H, int W, const float* geom, int geom_kind, double aspect,
+                                     int mode, const Blur& bl, int udp, float* out, At at) {
+    int px = bi % W, py = bi / W;
+    const bool found = bv > 0.0f;                               // get_max_preds' mask, false for a NaN
+    if (!found) px = py = 0;
+    double x = (double)px, y = (double)py;
+    if (mode == DM_QUARTER) {
+        if (lane != 0) return;
+        if (1 < px && px < W - 1 && 1 < py && py < H - 1) {     // finish's POST_PROCESS
+            const int row = py * W;
+            x = (double)((float)px + sign_of(at(row, px + 1) - at(row, px - 1)) * 0.25f);
+            y = (double)((float)py + sign_of(at(row + W, px) - at(row - W, px)) * 0.25f);
+        }
+    } else {
+        const double g = stencil_logs(py, px, H, W, mode, bl, lane, at);
+        const int R = mode == DM_DARK ? 2 : 1, NC = 2 * R + 1;
+        auto G = [&](int dy, int dx) { return __shfl(g, (dy + R) * NC + dx + R); };
+        const double g00 = G(0, 0), g0p = G(0, 1), g0m = G(0, -1), gp0 = G(1, 0), gm0 = G(-1, 0), gpp = G(1, 1), gmm = G(-1, -1);
+        double a, b, d;
+        if (mode == DM_DARK) {
+            const double g0pp = G(0, 2), g0mm = G(0, -2), gpp0 = G(2, 0), gmm0 = G(-2, 0), gmp = G(-1, 1), gpm = G(1, -1);
+            a = 0.25 * (g0pp - 2.0 * g00 + g0mm);
+            d = 0.25 * (gpp0 - 2.0 * g00 + gmm0);
+            b = 0.25 * (gpp - gmp - gpm + gmm);
+        } else {
+            const double eps = 1.1920928955078125e-07;          // 2^-23
+            a = g0p - 2.0 * g00 + g0m + eps;
+            d = gp0 - 2.0 * g00 + gm0 + eps;
+            b = 0.5 * (gpp - g0p - gp0 + g00 + g00 - g0m - gm0 + gmm);
+        }
+        if (lane != 0) return;
+        const bool step = found && (mode == DM_UDP || (1 < px && px < W - 2 && 1 < py && py < H - 2));
+        const double gx = 0.5 * (g0p - g0m), gy = 0.5 * (gp0 - gm0);
+        const double det = a * d - b * b;
+        if (step && !(mode == DM_DARK && det == 0.0)) {         // nothing bounds the step; infinities and NaNs propagate
+            x = (double)px - (d * gx - b * gy) / det;
+            y = (double)py - (a * gy - b * gx) / det;
+        }
+    }
+    const KasfCropGeom cg = kasf_crop_geom(geom + person * 4, geom_kind, aspect, W);
+    float* o = out + m * 3;
+    if (udp) {                                                  // UDP: W - 1 and H - 1 intervals, each axis by its own scale (H, W >= 2: the entry point)
+        const float sw = cg.sx * 200.0f, sh = cg.sy * 200.0f;
+        o[0] = (float)((double)cg.cx + (x - (double)(W - 1) * 0.5) * ((double)sw / (double)(W - 1)));
+        o[1] = (float)((double)cg.cy + (y - (double)(H - 1) * 0.5) * ((double)sh / (double)(H - 1)));
+    } else {                                                    // finish's affine
+        o[0] = (float)((double)cg.cx + (x - (double)W * 0.5) * cg.kx);
+        o[1] = (float)((double)cg.cy + (y - (double)H * 0.5) * cg.ky);
+    }
+    o[2] = bv;
+}
+
+template <class E, bool VEC>
+__global__ __launch_bounds__(HM_THREADS) void k_heatmap_decode(const typename Elem<E>::T* __restrict__ hm, int64_t maps, int H, int W,
+                                                               const float* __restrict__ geom, int geom_kind, double aspect, int mode, Blur bl, int udp,
+                                                               float* __restrict__ out) {
+    using T = typename Elem<E>::T;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int HW = H * W;                                       // <= 2^24 (checked by the entry point)
+    for (int64_t m = (int64_t)blockIdx.x * HM_WAVES + wave; m < maps; m += (int64_t)gridDim.x * HM_WAVES) {   // the tail: a wave without a map leaves
+        const T* __restrict__ map = hm + m * HW;
+        const Best mine = stream_map<E, VEC>(map, HW, lane);
+        const Best b = wave_first(mine.v, mine.i);
+        finish_decode(b.v, b.i, lane, m, m / 17, H, W, geom, geom_kind, aspect, mode, bl, udp, out,
+                      [&](int row, int col) { return Elem<E>::up(map[row + col]); });
+    }
+}
+
+template <class E, int MODE>
+__global__ __launch_bounds__(HM_THREADS) void k_heatmap_flip_decode(const typename Elem<E>::T* __restrict__ hm, const typename Elem<E>::T* __restrict__ hmf,
+                                                                    int64_t maps, int H, int W, Partner partner, int shift, const float* __restrict__ geom,
+                                                                    int geom_kind, double aspect, int mode, Blur bl, int udp, float* __restrict__ out,
+                                                                    float* __restrict__ merged_out) {
+    using T = typename Elem<E>::T;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int HW = H * W;                                       // <= 2^24 (checked by the entry point)
+    for (int64_t m = (int64_t)blockIdx.x * HM_WAVES + wave; m < maps; m += (int64_t)gridDim.x * HM_WAVES) {   // the tail: a wave without a map leaves
+        const int64_t person = m / 17;
+        const T* __restrict__ map = hm + m * HW;
+        const T* __restrict__ fmap = hmf + (person * 17 + partner_of(partner, (int)(m - person * 17))) * HW;
+        float* __restrict__ mo = merged_out ? merged_out + m * HW : nullptr;
+        const Best mine = stream_merged<E, MODE>(map, fmap, mo, HW, W, shift, lane);
+        const Best b = wave_first(mine.v, mine.i);
+        // raw = the MERGED value, formed again from the two operands (never read back from merged_out)
+        finish_decode(b.v, b.i, lane, m, person, H, W, geom, geom_kind, aspect, mode, bl, udp, out,
+                      [&](int row, int col) { return merge(Elem<E>::up(map[row + col]), Elem<E>::up(fmap[row + src_x(col, W, shift)])); });
+    }
+}
+
+Partner pack_partner(const int* partner) {
+    Partner p = {0, 0};
+    for (int j = 0; j < 17; ++j) {
+        if (j < 12) p.lo |= (unsigned long long)(partner[j] & 31) << (5 * j);
+        else p.hi |= (unsigned long long)(partner[j] & 31) << (5 * (j - 12));
+    }
+    return p;
+}
+
+template <class E>
+void launch_decode(hipStream_t s, const void* hm, const void* hmf, int64_t maps, int H, int W, const int* partner, int shift, const float* geom, int geom_kind,
+                   double aspect, int mode, const Blur& bl, int udp, float* out, float* merged_out) {
+    using T = typename Elem<E>::T;
+    const int64_t map_bytes = (int64_t)H * W * (int64_t)sizeof(T);
+    const dim3 grid = hm_grid(maps), block(HM_THREADS);
+    const T* a = (const T*)hm;
+    const T* b = (const T*)hmf;
+    if (!hmf) {
+        const bool vec = ((uintptr_t)hm & 15) == 0 && (map_bytes & 15) == 0;
+        if (vec) hipLaunchKernelGGL((k_heatmap_decode<E, true>), grid, block, 0, s, a, maps, H, W, geom, geom_kind, aspect, mode, bl, udp, out);
+        else hipLaunchKernelGGL((k_heatmap_decode<E, false>), grid, block, 0, s, a, maps, H, W, geom, geom_kind, aspect, mode, bl, udp, out);
+        return;
+    }
+    const Partner p = pack_partner(partner);
+    const bool vec = (((uintptr_t)hm | (uintptr_t)hmf | (uintptr_t)merged_out) & 15) == 0 && (map_bytes & 15) == 0;
+    const int path = !vec ? ELEM : (W % Elem<E>::VW == 0 ? ROW : SPLIT);
+    if (path == ROW)
+        hipLaunchKernelGGL((k_heatmap_flip_decode<E, ROW>), grid, block, 0, s, a, b, maps, H, W, p, shift, geom, geom_kind, aspect, mode, bl, udp, out, merged_out);
+    else if (path == SPLIT)
+        hipLaunchKernelGGL((k_heatmap_flip_decode<E, SPLIT>), grid, block, 0, s, a, b, maps, H, W, p, shift, geom, geom_kind, aspect, mode, bl, udp, out, merged_out);
+    else
+        hipLaunchKernelGGL((k_heatmap_flip_decode<E, ELEM>), grid, block, 0, s, a, b, maps, H, W, p, shift, geom, geom_kind, aspect, mode, bl, udp, out, merged_out);
+}
+
 }  // namespace
+
+void kasf_launch_heatmap_decode(hipStream_t s, const void* hm, const void* hmf, int dtype, int64_t n, int H, int W, const int* partner, int shift,
+                                const float* geom, int geom_kind, double aspect, int mode, const float* weights, int K, int udp, float* out, float* merged_out) {
+    if (n <= 0) return;
+    Blur bl;
+    for (int k = 0; k < 17; ++k) bl.w[k] = mode != DM_QUARTER && k < K ? weights[k] : 0.0f;
+    bl.K = K;
+    if (dtype == KASF_F32) launch_decode<F32>(s, hm, hmf, n * 17, H, W, partner, shift, geom, geom_kind, aspect, mode, bl, udp, out, merged_out);
+    else if (dtype == KASF_F16) launch_decode<F16>(s, hm, hmf, n * 17, H, W, partner, shift, geom, geom_kind, aspect, mode, bl, udp, out, merged_out);
+    else launch_decode<BF16>(s, hm, hmf, n * 17, H, W, partner, shift, geom, geom_kind, aspect, mode, bl, udp, out, merged_out);
+}
 
 void kasf_launch_heatmap_keypoints(hipStream_t s, const void* hm, int dtype, int64_t n, int H, int W, const float* geom, int geom_kind, double aspect,
                                    int refine, float* out) {

@@ -233,6 +233,12 @@ void kasf_launch_heatmap_keypoints(hipStream_t s, const void* hm, int dtype, int
 void kasf_launch_heatmap_flip_keypoints(hipStream_t s, const void* hm, const void* hmf, int dtype, int64_t n, int H, int W, const int* partner, int shift,
                                         const float* geom, int geom_kind, double aspect, int refine, float* out, float* merged_out);
 
+// ---- k_heatmap.hip as well: the DARK / UDP decode (kasf.h, kasf_heatmap_decode): hmf null = no flip test (partner, shift, merged_out then unused); mode 0 quarter,
+// 1 dark, 2 dark_udp; weights = K HOST floats (K odd, 1 .. 17; unread with mode 0) passed by value into the launch; udp = the W - 1 / H - 1 affine (H, W >= 2);
+// everything else as kasf_launch_heatmap_flip_keypoints ----
+void kasf_launch_heatmap_decode(hipStream_t s, const void* hm, const void* hmf, int dtype, int64_t n, int H, int W, const int* partner, int shift,
+                                const float* geom, int geom_kind, double aspect, int mode, const float* weights, int K, int udp, float* out, float* merged_out);
+
 // ---- k_crop.hip: person boxes -> pose-network inputs (kasf.h, kasf_crop_persons): frames uint8 [n_frames][Hf][Wf][3] with byte strides, geom as k_heatmap.hip takes it,
 // out [n,3,out_h,out_w] of out_dtype, mean_std = six HOST floats passed by value into the launch, center_scale_out [n,4] fp32 or null.  Arguments as checked by the entry point ----
 void kasf_launch_crop_persons(hipStream_t s, const void* frames, int n_frames, int Hf, int Wf, int64_t row_stride, int64_t frame_stride,

@@ -5,6 +5,7 @@
     kp = heatmaps_to_keypoints(hm, center, scale, layout="h36m")          # ... and through coco_to_h36m: what lift_track / lift_tracks take
     poses = lifter.push_heatmaps(hm, center, scale)                       # StreamLifter: decode, then push
     kp = heatmaps_to_keypoints(hm, center, scale, flipped=hm_of_mirrored_crops)   # the flip test: mirror back, swap left / right, shift, average, decode: one launch
+    kp = heatmaps_to_keypoints(hm, center, scale, decode="dark_udp")      # ViTPose / *_udp checkpoints: DARK-UDP sub-pixel step, W - 1 / H - 1 affine; "dark": *_dark
 
 ``heatmaps_to_keypoints`` is ``get_final_preds`` (demo/lib/hrnet/lib/utils/inference.py:21-82: argmax per joint map, the quarter-pixel ``POST_PROCESS``
 step, ``transform_preds`` back to image pixels), which the demo runs on the host on a copy of HRNet's output (demo/lib/hrnet/gen_kpts.py:158-161); HRNet,
@@ -103,6 +104,68 @@ def check_flip_args(hm: torch.Tensor, flipped, shift, pairs, who: str):
     return hmf, bool(shift), partner_table(pairs, who)
 
 
+DECODES = {"quarter": _lib.DECODE_QUARTER, "dark": _lib.DECODE_DARK, "dark_udp": _lib.DECODE_DARK_UDP}
+_FIXED_WEIGHTS = {1: (1.0,), 3: (0.25, 0.5, 0.25), 5: (0.0625, 0.25, 0.375, 0.25, 0.0625),
+                  7: (0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125)}     # OpenCV's tables for sigma <= 0
+
+
+def _check_kernel(kernel, who: str) -> int:
+    if isinstance(kernel, (bool, np.bool_)) or not isinstance(kernel, (int, np.integer)):
+        raise TypeError(f"{who}: kernel must be an odd integer in [1, 17], got {kernel!r}")
+    if not 1 <= kernel <= 17 or kernel % 2 == 0:
+        raise ValueError(f"{who}: kernel must be an odd integer in [1, 17], got {kernel}")
+    return int(kernel)
+
+
+def _check_sigma(sigma, who: str) -> float:
+    if isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{who}: sigma must be a positive finite number, got {sigma!r}")
+    if not sigma > 0 or not np.isfinite(sigma):
+        raise ValueError(f"{who}: sigma must be a positive finite number, got {sigma!r}")
+    return float(sigma)
+
+
+def gaussian_weights(kernel: int = 11, sigma=None) -> np.ndarray:
+    """The ``kernel`` weights of the DARK decodes' separable Gaussian, float32 (include/kasf.h, ``kasf_heatmap_decode``): computed in float64 and rounded once.
+    ``kernel`` odd, 1..17.  Without ``sigma`` and for 1, 3, 5, 7 taps OpenCV's fixed tables; otherwise ``sigma = ((kernel - 1) * 0.5 - 1) * 0.3 + 0.8`` when none
+    is given (``cv2.GaussianBlur(..., (k, k), 0)``, what mmpose calls), ``w_i = exp(-(i - (kernel - 1) / 2)^2 / (2 sigma^2))`` divided by their sum."""
+    who = "gaussian_weights"
+    K = _check_kernel(kernel, who)
+    if sigma is None and K in _FIXED_WEIGHTS:
+        return np.array(_FIXED_WEIGHTS[K], dtype=np.float32)
+    sigma = ((K - 1) * 0.5 - 1) * 0.3 + 0.8 if sigma is None else _check_sigma(sigma, who)
+    i = np.arange(K, dtype=np.float64) - (K - 1) / 2
+    w = np.exp(-(i * i) / (2.0 * sigma * sigma))
+    return (w / w.sum()).astype(np.float32)
+
+
+def check_decode_args(hm: torch.Tensor, decode, kernel, sigma, udp, refine, who: str):
+    """``decode`` / ``kernel`` / ``sigma`` / ``udp``, refused without a device -> ``None`` when all four are at their defaults (the existing entries serve the
+    call, as before), else ``(mode, weights, udp)`` for ``kasf_heatmap_decode``: weights float32 [kernel] on the host, None with "quarter"."""
+    if not isinstance(decode, str) or decode not in DECODES:
+        raise ValueError(f"{who}: decode must be one of {', '.join(repr(k) for k in DECODES)}, got {decode!r}")
+    if udp is not None and not isinstance(udp, (bool, np.bool_)):
+        raise TypeError(f"{who}: udp must be None or a bool, got {udp!r}")
+    mode = DECODES[decode]
+    weights = None
+    if mode == _lib.DECODE_QUARTER:
+        if kernel is not None or sigma is not None:
+            raise ValueError(f"{who}: kernel and sigma go with decode='dark' or 'dark_udp'")
+    else:
+        if not refine:
+            raise ValueError(f"{who}: refine=False goes with decode='quarter' only: the DARK step is the refinement")
+        K = 11 if kernel is None else _check_kernel(kernel, who)
+        weights = gaussian_weights(K, None if sigma is None else _check_sigma(sigma, who))
+    udp = mode == _lib.DECODE_DARK_UDP if udp is None else bool(udp)
+    if udp and (hm.shape[-2] < 2 or hm.shape[-1] < 2):
+        raise ValueError(f"{who}: udp needs maps of at least 2 x 2, got {hm.shape[-2]} x {hm.shape[-1]}")
+    if mode == _lib.DECODE_QUARTER and not udp:
+        return None
+    if not refine:
+        raise ValueError(f"{who}: refine=False is not available with udp=True")
+    return mode, weights, udp
+
+
 def _check_merged(merged, hm: torch.Tensor, flip, who: str):
     """``merged=`` -> None, True, or the caller's tensor: contiguous CUDA fp32 of the heatmaps' shape."""
     if merged is None or merged is False:
@@ -132,7 +195,7 @@ def _spans_overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
 
 
 def heatmaps_to_keypoints(heatmaps, center=None, scale=None, *, boxes=None, aspect=None, refine: bool = True, layout: str = "coco",
-                          device=None, flipped=None, shift: bool = True, pairs=None, merged=None):
+                          device=None, flipped=None, shift: bool = True, pairs=None, merged=None, decode: str = "quarter", kernel=None, sigma=None, udp=None):
     """Pose-network heatmaps -> keypoints in image pixels: ``heatmaps`` [...,17,H,W], float32, float16 or bfloat16 (the 16-bit types are widened on load,
     exactly), a torch tensor on the GPU -- the normal case: read in place when contiguous (a strided view is packed first), never modified -- or numpy /
     torch on the host, which is uploaded.  Returns CUDA fp32 [...,17,3]: image x, image y, score (the map's maximum; a map that holds a NaN scores NaN).
@@ -154,28 +217,41 @@ def heatmaps_to_keypoints(heatmaps, center=None, scale=None, *, boxes=None, aspe
     arithmetic on the tensors gives: it is the reference's float32 procedure on the exact upcasts.  ``pairs``: the left / right joint pairs ``(a, b)``
     (default ``COCO_PAIRS``; ``[]`` swaps nothing).  ``merged=True`` also returns the fp32 merged maps [...,17,H,W]; ``merged=tensor`` writes them into the
     caller's contiguous CUDA float32 tensor of that shape.  With ``merged`` the call returns ``FlipDecode(keypoints, merged)``, otherwise the keypoints alone.
-    ``shift`` / ``pairs`` / ``merged`` without ``flipped`` raise ``ValueError``; without ``flipped`` the call is the plain decode, unchanged."""
+    ``shift`` / ``pairs`` / ``merged`` without ``flipped`` raise ``ValueError``; without ``flipped`` the call is the plain decode, unchanged.
+
+    Sub-pixel refinement (``kasf_heatmap_decode``, still one launch; include/kasf.h states every rule): ``decode="quarter"`` is the rule above, what HRNet's
+    own checkpoints use.  ``"dark"`` is DARK (Zhang et al., CVPR 2020; mmpose's ``post_process='unbiased'``, the ``*_dark`` checkpoints), ``"dark_udp"`` the
+    DARK step of UDP (Huang et al., CVPR 2020; mmpose's ``post_dark_udp``, ViTPose and the ``*_udp`` checkpoints): the map is blurred with a ``kernel``-tap
+    Gaussian (odd, 1..17, default 11; ``sigma`` default OpenCV's rule for that size, see ``gaussian_weights``) and logged around the argmax only, and one
+    Newton step is made from there; argmax and score still come from the raw (or merged) map.  ``udp``: map heatmap coordinates back over ``W - 1`` /
+    ``H - 1`` intervals, each axis by its own scale, for crops made the UDP way; ``None`` means ``decode == "dark_udp"``, and ``udp=True`` with ``"quarter"``
+    is allowed.  Everything composes with ``flipped`` / ``merged``, ``boxes`` and ``layout``.  ``kernel`` / ``sigma`` with ``"quarter"``, ``refine=False`` with a
+    DARK mode or with ``udp=True``, and ``udp=True`` on a map with a side of 1 raise ``ValueError``.  With all four at their defaults the call launches exactly
+    what it launched before.  The rules restate mmpose's and OpenCV's published arithmetic; equality with a particular mmpose / cv2 build is not verified."""
     who = "heatmaps_to_keypoints"
     h36m = not check_layout(layout, who)
     hm, parts, kind, aspect = check_heatmap_args(heatmaps, center, scale, boxes, aspect, who)
     flip = check_flip_args(hm, flipped, shift, pairs, who)
+    dark = check_decode_args(hm, decode, kernel, sigma, udp, refine, who)
     merged = _check_merged(merged, hm, flip, who)
     extra = ((flip[0],) if flip is not None else ()) + ((merged,) if isinstance(merged, torch.Tensor) else ())
     dev = _args.resolve_device((hm,) + parts + extra, device, who)
     if flip is None:
-        return decode(hm.to(dev), tuple(t.to(dev) for t in parts), kind, aspect, refine, h36m)
+        return _decode(hm.to(dev), tuple(t.to(dev) for t in parts), kind, aspect, refine, h36m, dark=dark)
     if isinstance(merged, torch.Tensor) and any(t.is_cuda and t.numel() and _spans_overlap(t, merged) for t in (hm, flip[0])):
         raise ValueError(f"{who}: merged must not overlap heatmaps or flipped")
     flip = (flip[0].to(dev),) + flip[1:]
     if merged is None:
-        return decode(hm.to(dev), tuple(t.to(dev) for t in parts), kind, aspect, refine, h36m, flip)
-    return FlipDecode(*decode(hm.to(dev), tuple(t.to(dev) for t in parts), kind, aspect, refine, h36m, flip, merged))
+        return _decode(hm.to(dev), tuple(t.to(dev) for t in parts), kind, aspect, refine, h36m, flip, dark=dark)
+    return FlipDecode(*_decode(hm.to(dev), tuple(t.to(dev) for t in parts), kind, aspect, refine, h36m, flip, merged, dark=dark))
 
 
-def decode(hm: torch.Tensor, parts, kind: int, aspect: float, refine: bool, h36m: bool, flip=None, merged=None):
+def decode(hm: torch.Tensor, parts, kind: int, aspect: float, refine: bool, h36m: bool, flip=None, merged=None, dark=None):
     """``kasf_heatmap_keypoints`` on checked CUDA tensors of one device (what ``heatmaps_to_keypoints`` and ``StreamLifter.push_heatmaps`` end in); with
     ``flip`` = ``(hmf, shift, partner)`` of ``check_flip_args``, ``kasf_heatmap_flip_keypoints``, and with ``merged`` (True, or the checked tensor to
-    fill) -> ``(keypoints, merged maps)``."""
+    fill) -> ``(keypoints, merged maps)``.  With ``dark`` = ``(mode, weights, udp)`` of ``check_decode_args``, ``kasf_heatmap_decode`` takes both cases."""
+    if dark is not None:
+        return _decode_dark(hm, parts, kind, aspect, h36m, flip, merged, dark)
     lead, (H, W) = tuple(hm.shape[:-3]), hm.shape[-2:]
     hm = hm.contiguous()                                         # the same tensor when it already is
     geom = (torch.cat(parts, dim=-1) if len(parts) == 2 else parts[0]).contiguous()
@@ -204,4 +280,36 @@ def decode(hm: torch.Tensor, parts, kind: int, aspect: float, refine: bool, h36m
                                                                _lib.LAYOUT_H36M if h36m else _lib.LAYOUT_COCO, out.data_ptr(),
                                                                scratch.data_ptr() if h36m else None, merged.data_ptr() if merged is not None else None,
                                                                _args.stream()))
+    return out if merged is None else (out, merged)
+
+
+_decode = decode                 # heatmaps_to_keypoints' own ``decode`` argument shadows the function's name there
+
+
+def _decode_dark(hm: torch.Tensor, parts, kind: int, aspect: float, h36m: bool, flip, merged, dark):
+    """``decode`` through ``kasf_heatmap_decode``."""
+    mode, weights, udp = dark
+    lead, (H, W) = tuple(hm.shape[:-3]), hm.shape[-2:]
+    hm = hm.contiguous()
+    geom = (torch.cat(parts, dim=-1) if len(parts) == 2 else parts[0]).contiguous()
+    out = torch.empty(lead + (17, 3), dtype=torch.float32, device=hm.device)
+    n = out.numel() // 51
+    hmf, shift, partner = (None, True, None) if flip is None else flip
+    if flip is not None:
+        partner = np.ascontiguousarray(partner, dtype=np.int32)  # host memory, read during the call
+        if partner.shape != (17,):
+            raise ValueError(f"heatmap decode: the partner table must have 17 entries, got shape {partner.shape}")
+        hmf = hmf.contiguous()
+        if merged is True:
+            merged = torch.empty(tuple(hm.shape), dtype=torch.float32, device=hm.device)
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=np.float32)  # host memory as well
+    if n:
+        scratch = torch.empty_like(out) if h36m else None
+        with torch.cuda.device(hm.device):
+            _lib.check(_lib.load().kasf_heatmap_decode(hm.data_ptr(), hmf.data_ptr() if flip is not None else None, _args.DTYPES[hm.dtype], n, int(H), int(W),
+                                                       partner.ctypes.data if flip is not None else None, int(shift), geom.data_ptr(), kind, aspect, mode,
+                                                       weights.ctypes.data if weights is not None else None, int(weights.size) if weights is not None else 1,
+                                                       int(udp), _lib.LAYOUT_H36M if h36m else _lib.LAYOUT_COCO, out.data_ptr(),
+                                                       scratch.data_ptr() if h36m else None, merged.data_ptr() if merged is not None else None, _args.stream()))
     return out if merged is None else (out, merged)

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _args, _lib
-from .heatmap import check_flip_args, check_heatmap_args, decode
+from .heatmap import check_decode_args, check_flip_args, check_heatmap_args, decode
 from .pose import check_layout, convert_frames
 from .lift import _as_tensor, _forward_windows, _model_device, _per_row, _upload, window_plan
 
@@ -49,15 +49,15 @@ def _checked_tables(lib, T: int, who: str):
     return r_tab, fp_tab
 
 
-def _decode_on(device, hm, parts, kind, aspect, refine: bool, h36m: bool, who: str, flip=None) -> torch.Tensor:
-    """``push_heatmaps``: the checked heatmaps and their geometry (and ``check_flip_args``' result), refused when on another GPU, decoded on ``device``
-    -> keypoints [n,17,3]."""
+def _decode_on(device, hm, parts, kind, aspect, refine: bool, h36m: bool, who: str, flip=None, dark=None) -> torch.Tensor:
+    """``push_heatmaps``: the checked heatmaps and their geometry (and ``check_flip_args``' and ``check_decode_args``' results), refused when on another GPU,
+    decoded on ``device`` -> keypoints [n,17,3]."""
     for t in (hm,) + parts + ((flip[0],) if flip is not None else ()):
         if t.is_cuda and t.device != device:
             raise RuntimeError(f"{who}: input on {t.device}, the model on {device}")
     if flip is not None:
         flip = (flip[0].to(device),) + flip[1:]
-    return decode(hm.to(device), tuple(t.to(device) for t in parts), kind, aspect, refine, h36m, flip)
+    return decode(hm.to(device), tuple(t.to(device) for t in parts), kind, aspect, refine, h36m, flip, dark=dark)
 
 
 class StreamLifter:
@@ -149,21 +149,23 @@ class StreamLifter:
             return self._lift(ids_d, K, self.lag, 1).view(K, 17, 3)
 
     def push_heatmaps(self, heatmaps, center=None, scale=None, *, boxes=None, aspect=None, refine: bool = True, slots=None, flipped=None,
-                      shift: bool = True, pairs=None) -> torch.Tensor:
+                      shift: bool = True, pairs=None, decode: str = "quarter", kernel=None, sigma=None, udp=None) -> torch.Tensor:
         """One new frame per slot straight from the pose network: ``heatmaps`` [K,17,H,W] (float32, float16 or bfloat16; normally the network's output
         on the model's GPU, read in place) with ``center`` / ``scale`` [K,2] or ``boxes`` [K,4] and ``aspect`` as ``heatmaps_to_keypoints`` takes them,
         decoded on the device and pushed: what ``push`` returns for ``heatmaps_to_keypoints(..., layout="h36m")`` of them (for the COCO result on a
         ``layout="coco"`` lifter, which is the same frames).  Two launches in front of ``push``'s, no host round trip.  Nothing is filtered: a map that
         holds a NaN gives a NaN score (and possibly coordinates) in the ring, as pushing those keypoints would.  ``flipped`` / ``shift`` / ``pairs``: the
-        flip test, as ``heatmaps_to_keypoints`` takes them (still one decode launch)."""
+        flip test, and ``decode`` / ``kernel`` / ``sigma`` / ``udp``: the DARK / UDP sub-pixel decode, as ``heatmaps_to_keypoints`` takes them (still one decode
+        launch)."""
         who = "StreamLifter.push_heatmaps"
         hm, parts, kind, aspect = check_heatmap_args(heatmaps, center, scale, boxes, aspect, who)
         flip = check_flip_args(hm, flipped, shift, pairs, who)
+        dark = check_decode_args(hm, decode, kernel, sigma, udp, refine, who)
         ids = self._ids(slots, who)
         K = self.slots if ids is None else int(ids.size)
         if hm.dim() != 4 or hm.shape[0] != K:
             raise ValueError(f"{who}: expected heatmaps [{K},17,H,W] (one person per pushed slot), got {tuple(hm.shape)}")
-        return self.push(_decode_on(self.device, hm, parts, kind, aspect, refine, not self._coco, who, flip), slots=slots)
+        return self.push(_decode_on(self.device, hm, parts, kind, aspect, refine, not self._coco, who, flip, dark), slots=slots)
 
     def tail(self, slots=None) -> torch.Tensor:
         """The ``lag`` frames ``push`` has not emitted yet, from the current windows, for the end of a track: [K,lag,17,3], row r = frame

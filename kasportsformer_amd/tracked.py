@@ -34,7 +34,7 @@ import torch
 
 from . import _args, _lib
 from ._args import index_in
-from .heatmap import check_flip_args, check_heatmap_args
+from .heatmap import check_decode_args, check_flip_args, check_heatmap_args
 from .lift import _as_tensor, _forward_windows, _model_device, _per_row, _upload
 from .pose import check_layout, convert_frames
 from .stream import _checked_tables, _decode_on
@@ -174,18 +174,20 @@ class TrackedLifter:
         return TrackedTick(poses, valid, ids_out, frames_out)
 
     def push_heatmaps(self, heatmaps, center=None, scale=None, track=None, *, boxes=None, aspect=None, refine: bool = True, flipped=None,
-                      shift: bool = True, pairs=None) -> TrackedTick:
+                      shift: bool = True, pairs=None, decode: str = "quarter", kernel=None, sigma=None, udp=None) -> TrackedTick:
         """One tick straight from the pose network: ``heatmaps`` [B*R,17,H,W] or [B,R,17,H,W] (float32, float16 or bfloat16) with ``center`` / ``scale``
         or ``boxes`` and ``aspect`` as ``heatmaps_to_keypoints`` takes them, decoded on the device and pushed: what ``push`` returns for
         ``heatmaps_to_keypoints(..., layout="h36m")`` of them (for the COCO result on a ``layout="coco"`` lifter, which is the same frames).
-        ``flipped`` / ``shift`` / ``pairs``: the flip test, as ``heatmaps_to_keypoints`` takes them."""
+        ``flipped`` / ``shift`` / ``pairs``: the flip test, and ``decode`` / ``kernel`` / ``sigma`` / ``udp``: the DARK / UDP sub-pixel decode, as
+        ``heatmaps_to_keypoints`` takes them."""
         who = "TrackedLifter.push_heatmaps"
         hm, parts, kind, aspect = check_heatmap_args(heatmaps, center, scale, boxes, aspect, who)
         flip = check_flip_args(hm, flipped, shift, pairs, who)
+        dark = check_decode_args(hm, decode, kernel, sigma, udp, refine, who)
         if tuple(hm.shape[:-3]) not in ((self.streams, self.R), (self.streams * self.R,)):
             raise ValueError(f"{who}: expected heatmaps [{self.streams * self.R},17,H,W] or [{self.streams},{self.R},17,H,W] (one person per row), "
                              f"got {tuple(hm.shape)}")
         if track is None:
             raise TypeError(f"{who}: track (the TrackResult of this tick) is required")
         check_tracked_tick(track, self.streams, self.track_slots, self.device, who)
-        return self.push(_decode_on(self.device, hm, parts, kind, aspect, refine, not self._coco, who, flip), track)
+        return self.push(_decode_on(self.device, hm, parts, kind, aspect, refine, not self._coco, who, flip, dark), track)
