@@ -59,6 +59,8 @@
  *                             demo/lib/sort/sort.py:15-222, demo/lib/hrnet/gen_kpts.py:111-148
  *   kasf_stream_track_front, kasf_stream_track_emit <- the seam between the two: gen_video_kpts hands each tracked person's keypoints to the lift by track
  *                             order; here the tracker's ids and slots drive the lifter's per-player histories on the device   demo/lib/hrnet/gen_kpts.py:125-170
+ *   kasf_one_euro_push, kasf_one_euro_tracked, kasf_one_euro_tracks <- nothing in the reference (its unused revise_kpts, demo/lib/preprocess.py:72-103, patches
+ *                             low-score leg joints): the One-Euro filter live pose pipelines put between the pose network and the lift, and behind the lift
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
  *   kasf_op_gcn_fwd, kasf_op_gcn_bwd <- GCN.forward between its U | V Linear and the residual, and autograd of it   model/modules/graph.py:19-134, KASportsFormer.py:109
  */
@@ -833,6 +835,72 @@ int kasf_stream_track_front(const float* frames, const int32_t* ids, const int32
                             const float* height, const int32_t* resample_tab, int32_t flip, float* x_out, int32_t* row_slot, void* stream);
 int kasf_stream_track_emit(const float* pred, int32_t flip, const int64_t* count, const int32_t* owner, const int32_t* row_slot, int32_t n_rows, int32_t T,
                            const int32_t* first_pos_tab, int32_t back, float* out, uint8_t* valid, int32_t* ids_out, int64_t* frames_out, void* stream);
+
+/* ---- steady keypoints and poses over time: the One-Euro filter (Casiez, Roussel, Vogel, CHI 2012) with its state on the device (ADDED under ABI 12:
+ * additive, kasf_version() stays 12; look the three symbols up by name).  What ties one tick to the next: in front of the lift over the 2-D keypoints, behind it
+ * over the 3-D poses; score-gated, so an occluded joint holds its last estimate.  One launch per call, nothing read back, nothing allocated.
+ *
+ * A ROW is one person's frame [J][Ct] fp32: the C filtered channels first and, with has_score, one more channel, the score: Ct = C + 1; without it Ct = C.
+ * Keypoints are J = 17, C = 2, has_score = 1; poses are J = 17, C = 3, has_score = 0.
+ *
+ * State per slot g (device, the caller's): xhat [S][J][C] fp32, dxhat [S][J][C] fp32, last [S][J] int64 = the tick of the joint's last update, -1 for none (the
+ * initial state is all -1; xhat and dxhat need no initial value), and for the tracked entry owner [S] int32, initially 0, S = streams * track_slots.
+ *
+ * Parameters (host values, passed by value into the launch): dt (seconds per tick), min_cutoff, d_cutoff (Hz), beta, min_score, max_hold (ticks), and tick, an
+ * int64 the caller increases by one per push.  They are in the units of the data: pixels for keypoints, model units for poses.
+ *
+ * The rule, per joint j of a pushed row x with slot g, in fp32, every line one rounded operation (a line with two: left to right) in this order; the library is
+ * built with -ffp-contract=off and a correctly rounded divide:
+ *   1. m[c] = x[j][c].  The joint is USABLE iff every m[c] is finite, |m[c]| <= 1e12f, and (with a score) x[j][C] >= min_score; a NaN score fails the comparison.
+ *   2. k = max(tick - last[g][j], 1).  If last[g][j] >= 0 and k - 1 > max_hold the estimate is dropped: last[g][j] is treated as -1.
+ *   3. No estimate: if the joint is usable, xhat = m, dxhat = 0, last = tick.  Either way the output is the input as it came.
+ *   4. Estimate, joint not usable: the output is xhat (hold).  The state is untouched, so k keeps growing.
+ *   5. Estimate, joint usable, per channel, with two_pi = 6.2831855f:
+ *        dtj  = float(k) * dt
+ *        d    = (m - xhat) / dtj
+ *        rd   = two_pi * d_cutoff * dtj
+ *        ad   = rd / (rd + 1)
+ *        dx   = dxhat + ad * (d - dxhat)
+ *        fc   = min_cutoff + beta * |dx|
+ *        r    = two_pi * fc * dtj
+ *        a    = r / (r + 1)
+ *        xnew = xhat + a * (m - xhat)
+ *      xhat = xnew, dxhat = dx, last = tick; the output is xnew.
+ *   6. The score channel is copied through unchanged in every case.
+ * The incremental form xhat + a * (m - xhat) reproduces a constant input exactly and returns the first sample as it is.
+ *
+ * kasf_one_euro_push: x, out [K][J][Ct]; row i goes to slot slots[i] (device int32 [K]), slots = NULL means slot i (K == S) as in kasf_stream_push.  The ids of
+ * a call are distinct; an id outside [0, S) makes the row a copy-through that touches no state.
+ *
+ * kasf_one_euro_tracked: x, out [streams * R][J][Ct]; ids, slot, born [streams][track_slots] int32 and count_b [streams] int32 are kasf_sort_update's outputs of
+ * this tick, read in place.  Row k of stream b is resolved by kasf_stream_track_front's rule to the word: count_b is clamped to [0, track_slots]; the row takes
+ * track row r = count_b - 1 - k (rows_mode = KASF_ROWS_PERSONS) or r = k (KASF_ROWS_TRACKS); it is VALID iff k < min(count_b, R), id = ids[b][r] >= 1,
+ * s = slot[b][r] is in [0, track_slots) and no lower row of the same stream that passes these three tests has the same s (the lowest row wins a duplicate).  For a
+ * valid row, g = b * track_slots + s; when owner[g] != id or born[b][r] != 0 the slot restarts -- every last[g][:] = -1, owner[g] = id -- and then the rule above
+ * runs.  An invalid row touches no state and is copied through.  row_slot [streams * R] int32 (may be NULL) receives g, or -1.
+ *
+ * kasf_one_euro_tracks: recorded tracks packed as x, out [N][J][Ct], track t = rows offsets[t] .. offsets[t + 1] - 1 (device int64 [P + 1], as
+ * kasf_lift_windows_ragged takes them; clamped into [0, N]).  Each track starts from an empty state and tick = frame index within the track; the state stays in
+ * registers, one launch, and the result equals kasf_one_euro_push called frame by frame bit for bit.
+ *
+ * One wavefront per row or track; valid rows have distinct g, so there are no atomics, the bits are the same from run to run, and a row's result does not depend
+ * on the other rows of the launch.  Every index formed from a device value is clamped.  x and out do not overlap; the inputs are never written.
+ *
+ * K = 0 / P = 0 does nothing.  Error 2, before a device or a device pointer is touched: J outside [1, 256] or C outside [1, 4]; K or S negative, K > S, NULL
+ * slots with 0 < K < S; P or N negative; streams < 1, track_slots outside 1..64, R < 1, streams * R or streams * track_slots beyond 32 bits, a rows_mode that is
+ * neither constant; dt, min_cutoff or d_cutoff not in [1e-6, 1e6]; beta not in [0, 1e6]; a non-finite min_score; max_hold outside [0, 2^20]; a negative tick;
+ * a null pointer (params included; slots and row_slot may be NULL). */
+typedef struct kasf_one_euro_params {
+    float dt, min_cutoff, d_cutoff, beta, min_score;
+    int32_t max_hold;
+} kasf_one_euro_params;
+int kasf_one_euro_push(const float* x, const int32_t* slots, int32_t K, int32_t S, int32_t J, int32_t C, int32_t has_score, const kasf_one_euro_params* params,
+                       int64_t tick, float* xhat, float* dxhat, int64_t* last, float* out, void* stream);
+int kasf_one_euro_tracked(const float* x, const int32_t* ids, const int32_t* slot, const int32_t* born, const int32_t* count_b, int32_t streams,
+                          int32_t track_slots, int32_t rows_mode, int32_t R, int32_t J, int32_t C, int32_t has_score, const kasf_one_euro_params* params,
+                          int64_t tick, float* xhat, float* dxhat, int64_t* last, int32_t* owner, float* out, int32_t* row_slot, void* stream);
+int kasf_one_euro_tracks(const float* x, const int64_t* offsets, int64_t N, int32_t P, int32_t J, int32_t C, int32_t has_score,
+                         const kasf_one_euro_params* params, float* out, void* stream);
 
 /* debugging / tests: locate a named activation inside the workspace (see kasf_ws_name()) */
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags);

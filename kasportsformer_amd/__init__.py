@@ -52,6 +52,10 @@ Public surface mirrors the reference's interface for this path:
   TrackedLifter, TrackedTick            the seam between the two stages (demo/lib/hrnet/gen_kpts.py:125-170 hands each tracked person's keypoints to the lift):
                                         `SortTracker`'s ids and slots drive `StreamLifter`-style per-player histories on the device, births and deaths
                                         included; no read-back of the tracker's output, two launches and one forward per tick
+  OneEuroFilter, smooth_tracks          not in the demo (its unused `revise_kpts`, demo/lib/preprocess.py:72-103, patches low-score leg joints): the One-Euro filter
+                                        (Casiez et al., CHI 2012) over 2-D keypoints in front of the lift and 3-D poses behind it, state on the device, driven
+                                        by host slot ids or by `TrackResult`, score-gated so that an occluded joint holds; one launch per tick, no read-back
+                                        (`python -m kasportsformer_amd.lift --smooth`)
   poses_to_world, DEMO_CAMERA_ROTATION  demo/lib/utils.py:55-73, demo/demo.py:242-248 (camera space -> world space, floor, unit scale; `--world`)
   draw_poses, bgr_to_nv12,              demo/demo.py:91-105,159-191,307-323, demo/lib/hrnet/lib/utils/utilitys.py:24-58 (`plot_on_frame`'s lines and dots over the frame, the
   poses_to_panel, DrawResult            score threshold, the 3-D plot's projection, and the frame as the NV12 surface an encoder takes, on the device: exact
@@ -80,6 +84,7 @@ from .yuv import yuv_to_bgr, nv12_to_bgr, i420_to_bgr
 from .draw import draw_poses, bgr_to_nv12, poses_to_panel, DrawResult
 from .track import SortTracker, TrackResult, TrackState
 from .tracked import TrackedLifter, TrackedTick
+from .smooth import OneEuroFilter, smooth_tracks
 
 __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_stream", "set_deterministic", "is_deterministic", "set_fused_attention_backward", "is_fused_attention_backward", "loss3", "loss7", "LOSS7_NAMES", "FusedAdamW", "AdamW", "plan_chunks", "DataParallel", "joint_flip", "predict_flip_tta", "clip_metrics", "Evaluator",
            "evaluate_one_epoch", "PackedClips", "DeviceClipLoader", "pack_clip_directory", "read_clip_file", "shard_indices",
@@ -87,4 +92,4 @@ __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_strea
            "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample",
            "lift_track", "lift_tracks", "window_plan", "StreamLifter", "coco_to_h36m", "poses_to_world", "DEMO_CAMERA_ROTATION", "heatmaps_to_keypoints", "gaussian_weights",
            "detections_to_boxes", "yolo_heads_to_boxes", "DetectResult", "YOLOV3_ANCHORS", "YOLOV3_MASKS", "crop_persons", "CropResult", "letterbox_frames", "LetterboxResult", "yuv_to_bgr", "nv12_to_bgr", "i420_to_bgr", "SortTracker", "TrackResult", "TrackState",
-           "TrackedLifter", "TrackedTick", "draw_poses", "bgr_to_nv12", "poses_to_panel", "DrawResult"]
+           "TrackedLifter", "TrackedTick", "OneEuroFilter", "smooth_tracks", "draw_poses", "bgr_to_nv12", "poses_to_panel", "DrawResult"]

@@ -51,6 +51,10 @@ class KasfAdamwClass(C.Structure):       # bc1 / bc2 are formed by the library f
                 ("bc2", C.c_float), ("step", C.c_int32)]
 
 
+class KasfOneEuroParams(C.Structure):     # kasf_one_euro_params: host values, passed by value into the launch
+    _fields_ = [("dt", C.c_float), ("min_cutoff", C.c_float), ("d_cutoff", C.c_float), ("beta", C.c_float), ("min_score", C.c_float), ("max_hold", C.c_int32)]
+
+
 class KasfError(RuntimeError):
     pass
 
@@ -109,6 +113,9 @@ SIGNATURES = {
     "kasf_stream_emit": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
     "kasf_stream_track_front": (_i32, [_vp] * 5 + [_i32] * 5 + [_vp] * 6 + [_i32, _vp, _vp, _vp]),
     "kasf_stream_track_emit": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "kasf_one_euro_push": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(KasfOneEuroParams), _i64, _vp, _vp, _vp, _vp, _vp]),
+    "kasf_one_euro_tracked": (_i32, [_vp] * 5 + [_i32] * 7 + [C.POINTER(KasfOneEuroParams), _i64] + [_vp] * 7),
+    "kasf_one_euro_tracks": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, C.POINTER(KasfOneEuroParams), _vp, _vp]),
     "kasf_coco_h36m": (_i32, [_vp, _i64, _vp, _vp]),
     "kasf_pose_world": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "kasf_heatmap_keypoints": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i32, C.c_double, _i32, _i32, _vp, _vp, _vp]),

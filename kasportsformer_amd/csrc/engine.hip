@@ -1246,6 +1246,61 @@ int kasf_stream_track_emit(const float* pred, int32_t flip, const int64_t* count
     return 0;
 }
 
+// ---- the One-Euro filter with its state on the device (kasf.h, kasf_one_euro_*) ----
+static const char* one_euro_error(int32_t J, int32_t C, const kasf_one_euro_params* p, KasfOneEuro* out) {
+    if (J < 1 || J > 256) return "one_euro: J must be in [1, 256]";
+    if (C < 1 || C > 4) return "one_euro: C must be in [1, 4]";
+    if (p == nullptr) return "null pointer argument";
+    const float in_hz[3] = {p->dt, p->min_cutoff, p->d_cutoff};
+    for (float v : in_hz)
+        if (!(v >= 1e-6f && v <= 1e6f)) return "one_euro: dt, min_cutoff and d_cutoff must be in [1e-6, 1e6]";
+    if (!(p->beta >= 0.0f && p->beta <= 1e6f)) return "one_euro: beta must be in [0, 1e6]";
+    if (!std::isfinite(p->min_score)) return "one_euro: min_score must be finite";
+    if (p->max_hold < 0 || p->max_hold > (1 << 20)) return "one_euro: max_hold must be in [0, 2^20]";
+    *out = KasfOneEuro{p->dt, p->min_cutoff, p->d_cutoff, p->beta, p->min_score, p->max_hold};
+    return nullptr;
+}
+int kasf_one_euro_push(const float* x, const int32_t* slots, int32_t K, int32_t S, int32_t J, int32_t C, int32_t has_score, const kasf_one_euro_params* params,
+                       int64_t tick, float* xhat, float* dxhat, int64_t* last, float* out, void* stream) {
+    KasfOneEuro p;
+    if (const char* e = one_euro_error(J, C, params, &p)) return kasf_set_error(2, e);
+    if (const char* e = stream_error(slots, K, S, 1)) return kasf_set_error(2, e);
+    if (tick < 0) return kasf_set_error(2, "one_euro: tick must be >= 0");
+    if (K == 0) return 0;
+    if (!x || !xhat || !dxhat || !last || !out) return kasf_set_error(2, "null pointer argument");
+    kasf_launch_one_euro_push((hipStream_t)stream, x, slots, K, S, J, C, has_score ? 1 : 0, p, tick, xhat, dxhat, last, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int kasf_one_euro_tracked(const float* x, const int32_t* ids, const int32_t* slot, const int32_t* born, const int32_t* count_b, int32_t streams,
+                          int32_t track_slots, int32_t rows_mode, int32_t R, int32_t J, int32_t C, int32_t has_score, const kasf_one_euro_params* params,
+                          int64_t tick, float* xhat, float* dxhat, int64_t* last, int32_t* owner, float* out, int32_t* row_slot, void* stream) {
+    KasfOneEuro p;
+    if (const char* e = one_euro_error(J, C, params, &p)) return kasf_set_error(2, e);
+    if (streams < 1) return kasf_set_error(2, "one_euro: streams must be >= 1");
+    if (track_slots < 1 || track_slots > KASF_SORT_MAX) return kasf_set_error(2, "one_euro: track_slots must be in [1, 64]");
+    if (R < 1) return kasf_set_error(2, "one_euro: R must be >= 1");
+    if (rows_mode != KASF_ROWS_PERSONS && rows_mode != KASF_ROWS_TRACKS) return kasf_set_error(2, "one_euro: rows_mode must be KASF_ROWS_PERSONS or KASF_ROWS_TRACKS");
+    if ((int64_t)streams * R > INT32_MAX || (int64_t)streams * track_slots > INT32_MAX) return kasf_set_error(2, "one_euro: streams * R and streams * track_slots must fit 32 bits");
+    if (tick < 0) return kasf_set_error(2, "one_euro: tick must be >= 0");
+    if (!x || !ids || !slot || !born || !count_b || !xhat || !dxhat || !last || !owner || !out) return kasf_set_error(2, "null pointer argument");
+    kasf_launch_one_euro_tracked((hipStream_t)stream, x, ids, slot, born, count_b, streams, track_slots, rows_mode, R, J, C, has_score ? 1 : 0, p, tick, xhat, dxhat,
+                                 last, owner, out, row_slot);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int kasf_one_euro_tracks(const float* x, const int64_t* offsets, int64_t N, int32_t P, int32_t J, int32_t C, int32_t has_score,
+                         const kasf_one_euro_params* params, float* out, void* stream) {
+    KasfOneEuro p;
+    if (const char* e = one_euro_error(J, C, params, &p)) return kasf_set_error(2, e);
+    if (P < 0 || N < 0) return kasf_set_error(2, "one_euro: P and N must be >= 0");
+    if (P == 0) return 0;
+    if (!offsets || (N > 0 && (!x || !out))) return kasf_set_error(2, "null pointer argument");
+    kasf_launch_one_euro_tracks((hipStream_t)stream, x, offsets, N, P, J, C, has_score ? 1 : 0, p, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // ---- the two ends of the lift (kasf.h, kasf_coco_h36m / kasf_pose_world) ----
 int kasf_coco_h36m(const float* coco, int64_t frames, float* h36m, void* stream) {
     if (frames < 0) return kasf_set_error(2, "coco_h36m: frames must be >= 0");

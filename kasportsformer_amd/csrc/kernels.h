@@ -218,6 +218,18 @@ void kasf_launch_stream_track_front(hipStream_t s, const float* frames, const in
 void kasf_launch_stream_track_emit(hipStream_t s, const float* pred, int flip, const int64_t* count, const int* owner, const int* row_slot, int64_t n_rows, int T,
                                    const int* first_pos_tab, int back, float* out, unsigned char* valid, int* ids_out, int64_t* frames_out);
 
+// ---- k_smooth.hip: the One-Euro filter over rows [J][C + has_score] with its state on the device (kasf.h, kasf_one_euro_*): xhat, dxhat [S,J,C], last [S,J],
+// owner [B*S_t]; C in [1, 4], J >= 1 and the parameters as checked by the entry points, p passed by value into the launch ----
+#include "one_euro.h"    // KasfOneEuro and the step the three kernels share
+void kasf_launch_one_euro_push(hipStream_t s, const float* x, const int* slots, int K, int S, int J, int C, int has_score, const KasfOneEuro& p, int64_t tick,
+                               float* xhat, float* dxhat, int64_t* last, float* out);
+void kasf_launch_one_euro_tracked(hipStream_t s, const float* x, const int* ids, const int* slot, const int* born, const int* count_b, int B, int S_t, int rows_mode,
+                                  int R, int J, int C, int has_score, const KasfOneEuro& p, int64_t tick, float* xhat, float* dxhat, int64_t* last, int* owner,
+                                  float* out, int* row_slot);
+// P tracks packed back to back: track t = rows [offsets[t], offsets[t+1]) of [N,J,C + has_score]
+void kasf_launch_one_euro_tracks(hipStream_t s, const float* x, const int64_t* offsets, int64_t N, int P, int J, int C, int has_score, const KasfOneEuro& p,
+                                 float* out);
+
 // ---- k_pose.hip: the two ends of the lift (kasf.h, kasf_coco_h36m / kasf_pose_world); frames of [17,3] fp32, src and dst distinct arrays ----
 void kasf_launch_coco_h36m(hipStream_t s, const float* coco, int64_t frames, float* h36m);
 // q [4], t [3]: host arrays, passed by value into the launch

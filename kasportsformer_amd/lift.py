@@ -20,7 +20,8 @@ the forward together (``kasf_lift_windows_ragged`` / ``kasf_lift_stitch_ragged``
 ``--online [--lag D]`` replays the file tick by tick through ``kasportsformer_amd.stream.StreamLifter`` (the lift of live streams) instead.
 
 ``layout="coco"`` (``--layout coco``) takes the keypoints as a COCO-17 detector writes them and converts them on the device first
-(``kasportsformer_amd.pose.coco_to_h36m``); ``--world [--world-floor] [--world-unit]`` sends the poses through ``poses_to_world`` before they are written.
+(``kasportsformer_amd.pose.coco_to_h36m``); ``--smooth [--smooth-rate] [--smooth-min-cutoff] [--smooth-beta] [--smooth-min-score]`` sends the keypoints
+through the One-Euro filter first (``kasportsformer_amd.smooth.smooth_tracks``), offline and ``--online`` alike; ``--world [--world-floor] [--world-unit]`` sends the poses through ``poses_to_world`` before they are written.
 """
 from __future__ import annotations
 
@@ -344,9 +345,21 @@ def _parse(argv=None):
     ap.add_argument("--world", action="store_true", help="write world-space poses: the demo's camera_to_world rotation (demo.py:243-245)")
     ap.add_argument("--world-floor", action="store_true", help="--world: put each frame's lowest joint at z = 0 (demo.py:246)")
     ap.add_argument("--world-unit", action="store_true", help="--world: divide each frame by its largest value (demo.py:247-248), after --world-floor")
+    ap.add_argument("--smooth", action="store_true", help="run the One-Euro filter (kasportsformer_amd.smooth_tracks) over the keypoints before the lift: steadier "
+                                                          "coordinates, joints scored below --smooth-min-score hold their last estimate")
+    ap.add_argument("--smooth-rate", type=float, default=None, help="--smooth: frames per second of the track (default 30)")
+    ap.add_argument("--smooth-min-cutoff", type=float, default=None, help="--smooth: cutoff at rest in Hz (default 1.0; lower: steadier, more lag)")
+    ap.add_argument("--smooth-beta", type=float, default=None, help="--smooth: cutoff gained per pixel / s of speed (default 0.01; higher: less lag in motion)")
+    ap.add_argument("--smooth-min-score", type=float, default=None, help="--smooth: a joint scored below this holds (default 0.3)")
     ap.add_argument("--out", required=True, help="output .npy of [P,N,17,3] (or [N,17,3]) float32 poses; tracks of different lengths: an .npz "
                                                  "of track_0 ... track_{P-1}")
     args = ap.parse_args(argv)
+    smooth_defaults = dict(smooth_rate=30.0, smooth_min_cutoff=1.0, smooth_beta=0.01, smooth_min_score=0.3)
+    if not args.smooth and any(getattr(args, k) is not None for k in smooth_defaults):
+        ap.error("--smooth-rate, --smooth-min-cutoff, --smooth-beta and --smooth-min-score belong to --smooth")
+    for k, v in smooth_defaults.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v)
     if args.online and args.stride is not None:
         ap.error("--online lifts the sliding window of every tick: it takes no --stride")
     if args.lag and not args.online:
@@ -369,6 +382,10 @@ def main(argv=None):
     model = load_model(cfg).cuda()
     checkpoint_load(args.checkpoint, model)
     keypoints = load_keypoints(args.keypoints)
+    if args.smooth:                                # every track from an empty state, on the model's GPU; the lifts below take the result where it is
+        from .smooth import smooth_tracks
+        keypoints = smooth_tracks(keypoints, score=True, rate=args.smooth_rate, min_cutoff=args.smooth_min_cutoff, beta=args.smooth_beta,
+                                  min_score=args.smooth_min_score, device=_model_device(model))
 
     def final(poses):
         return poses_to_world(poses, floor=args.world_floor, unit=args.world_unit) if args.world else poses
