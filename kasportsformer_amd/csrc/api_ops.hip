@@ -1,0 +1,299 @@
+// The C entry points around the model (kasf.h): loss, optimizer, data and evaluation, then the kasf_op_* entries that run one kernel family on its own for the
+// unit tests.  The entries that read a kasf_model are in engine.hip.  Every refusal returns before any device call.
+#include <cstring>
+
+#include "api_check.h"
+
+extern "C" {
+
+int kasf_loss3(const float* pred, const float* target, float* dpred, float* losses, int64_t losses_floats, int32_t batch, int32_t n_frames,
+               float lambda_n_mpjpe, float lambda_velocity, float grad_scale, void* stream) {
+    if (!pred || !target || !dpred || !losses) return refuse_null();
+    if (batch < 1 || n_frames < 1) return kasf_set_error(2, "loss3: batch and n_frames must be positive");
+    if (losses_floats < 4 + 4 * (int64_t)batch) return kasf_set_error(5, "loss3: `losses` must hold 4 + 4 * batch floats (the per-clip sums live behind the result)");
+    kasf_launch_loss3((hipStream_t)stream, pred, target, dpred, losses, batch, n_frames, lambda_n_mpjpe, lambda_velocity, grad_scale);
+    return api_done();
+}
+
+int kasf_loss7(const float* pred, const float* target, float* dpred, float* losses, int64_t losses_floats, int32_t batch, int32_t n_frames,
+               const float* lambdas, float grad_scale, void* stream) {
+    if (!pred || !target || !dpred || !losses || !lambdas) return refuse_null();
+    if (batch < 1 || n_frames < 1) return kasf_set_error(2, "loss7: batch and n_frames must be positive");
+    if (n_frames > KASF_LOSS7_MAX_FRAMES) return kasf_set_error(2, "loss7: n_frames above KASF_LOSS7_MAX_FRAMES (a clip's angles are held in 64 KB of LDS)");
+    if (losses_floats < 8 + 8 * (int64_t)batch) return kasf_set_error(5, "loss7: `losses` must hold 8 + 8 * batch floats (the per-clip sums live behind the result)");
+    static_assert(KASF_LOSS7_MAX_FRAMES * 174 + 2048 <= 65536, "k_loss7's LDS at the largest clip");
+    kasf_launch_loss7((hipStream_t)stream, pred, target, dpred, losses, batch, n_frames, lambdas, grad_scale);
+    return api_done();
+}
+
+int kasf_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2, float eps,
+                    float weight_decay, int32_t step_index, float grad_scale, void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq) return refuse_null();
+    if (n % 4 != 0 || step_index < 1) return kasf_set_error(2, "n must be a multiple of 4 and step_index >= 1");
+    // torch.optim.AdamW forms the bias corrections in double (1 - 0.999^t cancels badly in fp32 at small t)
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step_index)), bc2 = (float)(1.0 - pow((double)beta2, (double)step_index));
+    kasf_launch_adamw((hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale);
+    return api_done();
+}
+
+int kasf_adamw_segments(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const KasfOptChunk* chunks, int64_t n_chunks,
+                        const KasfAdamwClass* classes, int32_t n_classes, float grad_scale, const float* clip, void* stream) {
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !classes || (!chunks && n_chunks != 0)) return refuse_null();
+    if (misaligned16(params) || misaligned16(grads) || misaligned16(exp_avg) || misaligned16(exp_avg_sq))
+        return kasf_set_error(2, "adamw_segments: the four arrays must be 16-byte aligned");
+    if (n < 0 || n_chunks < 0) return kasf_set_error(2, "adamw_segments: negative count");
+    if (n_classes < 1 || n_classes > KASF_OPT_MAX_CLASSES) return kasf_set_error(2, "adamw_segments: n_classes outside 1..KASF_OPT_MAX_CLASSES (split the table)");
+    KasfAdamwClasses by_value;
+    memset(&by_value, 0, sizeof(by_value));
+    for (int k = 0; k < n_classes; ++k) {
+        KasfAdamwClass& c = by_value.c[k];
+        c = classes[k];
+        if (c.step < 1) return kasf_set_error(2, "adamw_segments: a class's step must be >= 1");
+        // torch.optim.AdamW forms the bias corrections in double, as kasf_adamw_step above
+        c.bc1 = (float)(1.0 - pow((double)c.beta1, (double)c.step));
+        c.bc2 = (float)(1.0 - pow((double)c.beta2, (double)c.step));
+    }
+    if (n_chunks == 0) return 0;
+    kasf_launch_adamw_segments((hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, chunks, n_chunks, by_value, grad_scale, clip, KASF_OPT_GRID_CAP);
+    return api_done();
+}
+
+int kasf_grad_norm(const float* grads, int64_t n, const KasfOptChunk* chunks, int64_t n_chunks, double* partial, float grad_scale, float max_norm, float* out2,
+                   void* stream) {
+    if (!grads || !out2 || ((!chunks || !partial) && n_chunks != 0)) return refuse_null();
+    if (misaligned16(grads)) return kasf_set_error(2, "grad_norm: grads must be 16-byte aligned");
+    if (n < 0 || n_chunks < 0) return kasf_set_error(2, "grad_norm: negative count");
+    if (n_chunks == 0) return 0;
+    kasf_launch_grad_norm((hipStream_t)stream, grads, chunks, n_chunks, partial, grad_scale, max_norm, out2, KASF_OPT_GRID_CAP);
+    return api_done();
+}
+
+int kasf_gather_clips(const float* x_all, const float* y_all, const int64_t* index, const uint8_t* flip, int64_t n_clips, int32_t batch,
+                      int32_t n_frames, float* x_out, float* y_out, void* stream) {
+    if (!x_all || !index || !x_out || (y_all && !y_out)) return refuse_null();
+    if (n_clips < 1 || n_frames < 1) return kasf_set_error(2, "gather_clips: empty clip set");
+    kasf_launch_gather_clips((hipStream_t)stream, x_all, y_all, index, flip, n_clips, batch, n_frames, x_out, y_out);
+    return api_done();
+}
+int kasf_joint_flip(const float* src, float* dst, int64_t rows, void* stream) {
+    if (!src || !dst || src == dst) return kasf_set_error(2, "joint_flip: null or aliased pointers");
+    kasf_launch_joint_flip((hipStream_t)stream, src, dst, rows);
+    return api_done();
+}
+int kasf_tta_merge(const float* pred, const float* pred_of_flipped, float* out, int64_t rows, void* stream) {
+    if (!pred || !out) return refuse_null();
+    kasf_launch_tta_merge((hipStream_t)stream, pred, pred_of_flipped, out, rows);
+    return api_done();
+}
+int kasf_eval_metrics(const float* pred, const float* label_scaled, const float* factor, const float* res, const int32_t* action, int32_t batch,
+                      int32_t n_frames, int32_t n_actions, float* mpjpe, float* p_mpjpe, float* accel, float* jpe, double* action_sums, void* stream) {
+    if (!pred || !label_scaled || !factor || !res || !mpjpe || !p_mpjpe || !accel || !jpe) return refuse_null();
+    if (n_frames < 3 || n_frames > 256) return kasf_set_error(2, "eval_metrics: n_frames must be in [3,256]");
+    if ((action == nullptr) != (action_sums == nullptr)) return kasf_set_error(2, "eval_metrics: action and action_sums go together");
+    api_clear_error();
+    kasf_launch_eval_metrics((hipStream_t)stream, pred, label_scaled, factor, res, action, batch, n_frames, n_actions, mpjpe, p_mpjpe, accel, jpe, action_sums);
+    return api_done(api_launchers_spoke());
+}
+
+#define OP_DT_CHECK(dt) \
+    if ((dt) != KASF_F32 && (dt) != KASF_BF16) return kasf_set_error(3, "bad dtype")
+
+int kasf_op_linear(int32_t dtype, const void* a, const void* w, const float* bias, void* y, int64_t M, int32_t N, const float* ln_g, const float* ln_b,
+                   void* xn_out, int32_t act, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (N % 128 != 0) return kasf_set_error(2, "N must be a multiple of 128");
+    kasf_launch_linear(dtype, (hipStream_t)stream, a, 128, w, 128, bias, y, N, M, N, ln_g, ln_b, xn_out, act);
+    return api_done();
+}
+int kasf_op_mlp_fwd(int32_t dtype, const void* x, const float* ln_g, const float* ln_b, const void* w1, const float* b1, const void* w2, const float* b2,
+                    const float* ls2, void* out, int64_t M, void* xn_out, void* stream) {
+    OP_DT_CHECK(dtype);
+    kasf_launch_mlp_fwd(dtype, (hipStream_t)stream, x, ln_g, ln_b, w1, b1, w2, b2, ls2, out, M, xn_out);
+    return api_done();
+}
+int kasf_op_mlp_bwd(int32_t dtype, const void* x, const void* g, const float* ln_g, const float* ln_b, const void* w1, const float* b1,
+                    const void* w2t_scaled, const void* w1t, void* hbuf, void* dzbuf, void* g_in, float* dgamma, float* dbeta, int64_t M, void* stream) {
+    OP_DT_CHECK(dtype);
+    kasf_launch_mlp_bwd(dtype, (hipStream_t)stream, x, g, ln_g, ln_b, w1, b1, w2t_scaled, w1t, hbuf, dzbuf, nullptr, g_in, dgamma, dbeta, M);
+    return api_done();
+}
+int kasf_op_mlp_bwd_fused(const void* x, const void* xn, const void* g, const float* ln_g, const void* w1, const float* b1, const void* w2t_scaled,
+                          const void* w1t, void* dapart, float* partial, float* dw1, float* dw2_unscaled, float* db1, float* gsum, void* g_in,
+                          float* dgamma, float* dbeta, int64_t M, void* stream) {
+    if (!x || !xn || !g || !dapart || !partial || !dw1 || !dw2_unscaled || !db1 || !gsum || !g_in) return refuse_null();
+    kasf_launch_mlp_bwd_q((hipStream_t)stream, x, xn, g, ln_g, w1, b1, w2t_scaled, w1t, dapart, partial, dw1, dw2_unscaled, db1, gsum, g_in, dgamma,
+                          dbeta, M);
+    return api_done();
+}
+int kasf_op_wgrad(int32_t dtype, const void* g, int32_t N, const void* x, int32_t K, const float* ln_g, const float* ln_b, float* dw, float* dbias,
+                  int64_t M, float* partial, int64_t partial_floats, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (N % 128 != 0 || K % 128 != 0) return kasf_set_error(2, "N and K must be multiples of 128");
+    if (ln_g != nullptr && K != 128) return kasf_set_error(2, "LayerNorm-fused wgrad needs K == 128");
+    kasf_launch_wgrad(dtype, (hipStream_t)stream, g, N, N, x, K, K, ln_g, ln_b, dw, K, dbias, M, partial, partial_floats);
+    return api_done();
+}
+int kasf_op_dgrad_lnbwd(int32_t dtype, const void* dy, int32_t Kd, const void* wt, const void* dxn_add, const void* x, const float* gamma,
+                        const void* resid, void* out, int32_t accumulate, float* dgamma, float* dbeta, int64_t M, void* xn_out, const float* beta,
+                        void* stream) {
+    OP_DT_CHECK(dtype);
+    if (Kd % 128 != 0) return kasf_set_error(2, "Kd must be a multiple of 128");
+    if (xn_out != nullptr && beta == nullptr) return kasf_set_error(2, "xn_out needs beta");
+    kasf_launch_dgrad_lnbwd(dtype, (hipStream_t)stream, dy, Kd, wt, dxn_add, x, gamma, resid, out, accumulate, dgamma, dbeta, M, xn_out, beta);
+    return api_done();
+}
+int kasf_op_attention_fwd(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int32_t batch, int32_t n_frames,
+                          int32_t mode, void* stream) {
+    OP_DT_CHECK(dtype);
+    api_clear_error();
+    kasf_launch_attn_fwd(dtype, (hipStream_t)stream, q, ldq, k, v, ldkv, o, batch, n_frames, mode);
+    return api_done(api_launchers_spoke());
+}
+int kasf_op_attention_bwd(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* d_o, void* dq, int64_t lddq,
+                          void* dk, void* dv, int64_t lddkv, int32_t batch, int32_t n_frames, int32_t mode, void* stream) {
+    OP_DT_CHECK(dtype);
+    api_clear_error();
+    kasf_launch_attn_bwd(dtype, (hipStream_t)stream, q, ldq, k, v, ldkv, d_o, dq, lddq, dk, dv, lddkv, batch, n_frames, mode);
+    return api_done(api_launchers_spoke());
+}
+int kasf_op_attention_fwd_heads(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int32_t batch, int32_t n_frames,
+                                int32_t mode, int32_t num_heads, void* stream) {
+    OP_DT_CHECK(dtype);
+    api_clear_error();
+    kasf_launch_attn_fwd(dtype, (hipStream_t)stream, q, ldq, k, v, ldkv, o, batch, n_frames, mode, num_heads);
+    return api_done(api_launchers_spoke());
+}
+int kasf_op_attention_bwd_heads(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* d_o, void* dq, int64_t lddq,
+                                void* dk, void* dv, int64_t lddkv, int32_t batch, int32_t n_frames, int32_t mode, int32_t num_heads, void* stream) {
+    OP_DT_CHECK(dtype);
+    api_clear_error();
+    kasf_launch_attn_bwd(dtype, (hipStream_t)stream, q, ldq, k, v, ldkv, d_o, dq, lddq, dk, dv, lddkv, batch, n_frames, mode, num_heads);
+    return api_done(api_launchers_spoke());
+}
+int kasf_op_attention_bwd_fused_do(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* g_mid, const void* wproj_t_scaled, void* dq,
+                                   int64_t lddq, void* dk, void* dv, int64_t lddkv, int32_t batch, int32_t n_frames, int32_t mode, int32_t form, const void* o_saved,
+                                   const float* lse, void* stream) {
+    api_clear_error();
+    if (form < 0 || form > 1) return kasf_set_error(2, "form: 0 (persistent) or 1 (one group per workgroup)");
+    if (batch < 1 || n_frames < 1 || (int64_t)batch * n_frames * 17 * 384 >= ((int64_t)1 << 31)) return kasf_set_error(2, "batch * n_frames * 17 * 384 must stay below 2^31");
+    if (!kasf_launch_attn_bwd_fused_do((hipStream_t)stream, q, ldq, k, v, ldkv, g_mid, wproj_t_scaled, dq, lddq, dk, dv, lddkv, batch, n_frames, mode, form, o_saved, lse))
+        return kasf_set_error(2, "fused-d_o attention backward: groups of at most 96 positions (form 1: at most 32); bf16, 8 heads");
+    return api_done(api_launchers_spoke());
+}
+// ---- the GCN mixer on its own (kasf.h, kasf_op_gcn_fwd / kasf_op_gcn_bwd): the launch sequence and `count` of block_forward / block_backward ----
+static_assert(KASF_GCN_STAT_WORDS == KASF_STAT_SLOTS * KASF_STAT_LD * KASF_STAT_WORDS, "kasf.h and kernels.h disagree on the size of a statistics buffer");
+static int gcn_shape_check(int32_t batch, int32_t n_frames, int32_t mode) {
+    if (mode != 0 && mode != 1) return kasf_set_error(2, "gcn: mode must be 0 (spatial) or 1 (temporal)");
+    if (n_frames < 4 || n_frames > KASF_MAX_NODES) return kasf_set_error(2, "gcn: n_frames must be in [4, 256]");
+    if (batch < 1 || (int64_t)batch * n_frames * 17 * 16 >= ((int64_t)1 << 31)) return kasf_set_error(2, "gcn: batch >= 1 and batch * n_frames * 17 * 16 must stay below 2^31");
+    return 0;
+}
+int kasf_op_gcn_fwd(int32_t dtype, const void* x_in, const void* xn, const void* uv, const float* bn_w, const float* bn_b, float* run_mean, float* run_var,
+                    const float* ls1, void* y, uint32_t* mask, void* stats, float* coef, void* out, int32_t batch, int32_t n_frames, int32_t mode,
+                    int32_t neighbour_num, int32_t training, float momentum, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (gcn_shape_check(batch, n_frames, mode) != 0) return 2;
+    if (neighbour_num < 1 || neighbour_num > 4) return kasf_set_error(2, "gcn: neighbour_num must be in [1, 4]");
+    if (!x_in || !xn || !uv || !bn_w || !bn_b || !run_mean || !run_var || !ls1 || !y || !stats || !coef || !out || (mode == 1 && !mask))
+        return refuse_null();
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(stats, 0, (size_t)KASF_GCN_STAT_WORDS * sizeof(int64_t), s));
+    kasf_launch_gcn_agg_fwd(dtype, s, uv, xn, y, mode == 1 ? mask : nullptr, (double*)stats, batch, n_frames, mode, neighbour_num);
+    const double count = mode == 0 ? (double)batch * n_frames * 128 : (double)batch * 17 * 128;
+    kasf_launch_gcn_apply(dtype, s, x_in, xn, y, (const double*)stats, bn_w, bn_b, run_mean, run_var, coef, ls1, out, batch, n_frames, mode, count,
+                          training ? 1 : 0, momentum);
+    return api_done();
+}
+int kasf_op_gcn_bwd(int32_t dtype, const void* g, const void* xn, const void* y, const float* coef, const uint32_t* mask, const float* ls1, void* r, void* duv,
+                    float* dls1, float* d_bn_w, float* d_bn_b, void* bstats, int32_t batch, int32_t n_frames, int32_t mode, int32_t training, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (gcn_shape_check(batch, n_frames, mode) != 0) return 2;
+    if (!g || !xn || !y || !coef || !ls1 || !r || !duv || !dls1 || !d_bn_w || !d_bn_b || !bstats || (mode == 1 && !mask))
+        return refuse_null();
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(bstats, 0, (size_t)KASF_GCN_STAT_WORDS * sizeof(int64_t), s));
+    kasf_launch_gcn_bwd1(dtype, s, g, xn, y, coef, ls1, r, dls1, (double*)bstats, batch, n_frames, mode);
+    const double count = mode == 0 ? (double)batch * n_frames * 128 : (double)batch * 17 * 128;
+    kasf_launch_gcn_bwd2(dtype, s, r, y, coef, mode == 1 ? mask : nullptr, duv, batch, n_frames, mode, (const double*)bstats, d_bn_w, d_bn_b, count,
+                         training ? 1 : 0);
+    return api_done();
+}
+// ---- the gate, head and embedding kernels on their own (kasf.h, kasf_op_embed_bwd ... kasf_op_add): the engine's own launchers; the scratch of api_check.h's MiscSink ----
+#define MISC_TOKENS_CHECK(M, what) \
+    if ((M) < 1 || (int64_t)(M) * 384 >= ((int64_t)1 << 31)) return kasf_set_error(2, what ": 1 <= tokens and tokens * 384 < 2^31")
+int kasf_op_embed_bwd(int32_t dtype, const void* g, const float* in3, const float* w, float* dw, float* db, float* dpos, float* din3, int64_t frames,
+                      float* scratch, int64_t scratch_floats, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!g || !in3 || !w || !dw || !db || !dpos) return refuse_null();
+    if (refuse_misc_frames(frames)) return 2;
+    if (misc_scratch_check(scratch, scratch_floats)) return 2;
+    MiscSink ms(scratch, scratch_floats);
+    kasf_launch_embed_bwd(dtype, (hipStream_t)stream, g, in3, w, dw, db, dpos, din3, frames, ms.p);
+    return api_done(ms.finish((hipStream_t)stream));
+}
+int kasf_op_gate_fwd(int32_t dtype, const void* xa, const void* xg, const void* xb, const float* w, const float* bias, void* out, float* alpha, int64_t M,
+                     int32_t adaptive, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!xa || !xg || !xb || !w || !bias || !out) return refuse_null();
+    MISC_TOKENS_CHECK(M, "gate_fwd");
+    kasf_launch_gate_fwd(dtype, (hipStream_t)stream, xa, xg, xb, w, bias, out, alpha, M, adaptive ? 1 : 0);
+    return api_done();
+}
+int kasf_op_gate_bwd(int32_t dtype, const void* g, const void* g1, const void* g2, const void* xa, const void* xg, const void* xb, const float* w,
+                     const float* alpha, void* ga, void* gg, void* gb, float* dw, float* db, int64_t M, int32_t adaptive, float* scratch,
+                     int64_t scratch_floats, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!g || !xa || !xg || !xb || !w || !alpha || !ga || !gg || !gb || (adaptive && (!dw || !db))) return refuse_null();
+    if (misaligned16(alpha)) return kasf_set_error(2, "gate_bwd: alpha must be 16-byte aligned");
+    MISC_TOKENS_CHECK(M, "gate_bwd");
+    if (misc_scratch_check(scratch, scratch_floats)) return 2;
+    MiscSink ms(scratch, scratch_floats);
+    kasf_launch_gate_bwd(dtype, (hipStream_t)stream, g, g1, g2, xa, xg, xb, w, alpha, ga, gg, gb, dw, db, M, adaptive ? 1 : 0, ms.p);
+    return api_done(ms.finish((hipStream_t)stream));
+}
+int kasf_op_head_fwd(int32_t dtype, const void* rep, const float* w, const float* bias, float* out, int64_t M, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!rep || !w || !bias || !out) return refuse_null();
+    MISC_TOKENS_CHECK(M, "head_fwd");
+    kasf_launch_head_fwd(dtype, (hipStream_t)stream, rep, w, bias, out, M);
+    return api_done();
+}
+int kasf_op_head_bwd(int32_t dtype, const float* dy, const void* rep, const float* w, void* dpre, float* dw, float* db, int64_t M, float* scratch,
+                     int64_t scratch_floats, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!dy || !rep || !w || !dpre || !dw || !db) return refuse_null();
+    MISC_TOKENS_CHECK(M, "head_bwd");
+    if (misc_scratch_check(scratch, scratch_floats)) return 2;
+    MiscSink ms(scratch, scratch_floats);
+    kasf_launch_head_bwd(dtype, (hipStream_t)stream, dy, rep, w, dpre, dw, db, M, ms.p);
+    return api_done(ms.finish((hipStream_t)stream));
+}
+int kasf_op_rep_bwd(int32_t dtype, const float* drep, const void* rep, void* dpre, int64_t M, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!drep || !rep || !dpre) return refuse_null();
+    MISC_TOKENS_CHECK(M, "rep_bwd");
+    kasf_launch_rep_bwd(dtype, (hipStream_t)stream, drep, rep, dpre, M);
+    return api_done();
+}
+int kasf_op_finalize_ls(float* dw, const float* w, const float* bias, const float* ls, float* db, float* dls, int32_t N, int32_t K, void* stream) {
+    if (!dw || !w || !bias || !ls || !db || !dls) return refuse_null();
+    if (N != 128 || (K != 128 && K != 512)) return kasf_set_error(2, "finalize_ls: (N, K) must be (128, 128) or (128, 512), the two layer-scaled Linear layers of a block");
+    kasf_launch_finalize_ls((hipStream_t)stream, dw, w, bias, ls, db, dls, N, K);
+    return api_done();
+}
+int kasf_op_add(int32_t dtype, void* dst, const void* a, const void* b, const void* c, int64_t n, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!dst || !a || (!b && c)) return kasf_set_error(2, "null pointer argument (c needs b)");
+    if (n < 8 || n % 8 != 0 || n >= ((int64_t)1 << 40)) return kasf_set_error(2, "add: n must be a multiple of 8 in [8, 2^40)");
+    if (b == nullptr) kasf_launch_add_inplace(dtype, (hipStream_t)stream, dst, a, n);
+    else kasf_launch_add3(dtype, (hipStream_t)stream, dst, a, b, c, n);
+    return api_done();
+}
+int kasf_op_cast(int32_t dtype, const void* src, void* dst, int64_t n, int32_t to_f32, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (to_f32) kasf_launch_cast_to_f32(dtype, (hipStream_t)stream, src, (float*)dst, n);
+    else kasf_launch_cast_from_f32(dtype, (hipStream_t)stream, (const float*)src, dst, n);
+    return api_done();
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// The arguments of kasf_launch_draw_poses (k_draw.hip), as the entry points of engine.hip have checked them (kasf.h, kasf_draw_poses): plain data, shared
+// The arguments of kasf_launch_draw_poses (k_draw.hip), as the entry points of api_video.hip have checked them (kasf.h, kasf_draw_poses): plain data, shared
 // with the host build of the kernel's source (tests/host_emul/emul_draw.cpp).
 #pragma once
 #include <stdint.h>

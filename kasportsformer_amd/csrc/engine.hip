@@ -3,15 +3,12 @@
 // (reference: model/KASportsFormer.py:204-347).  Pure launch code: no allocation, no synchronisation.
 #include <atomic>
 #include <mutex>
-#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
-#include <string>
 #include <vector>
 
-#include "kasf.h"
-#include "kernels.h"
+#include "api_check.h"
 
 namespace {
 
@@ -117,12 +114,6 @@ int kasf_set_error(int code, const char* msg) {
 }
 
 namespace {
-
-#define HIPCHK(x)                                                                           \
-    do {                                                                                    \
-        hipError_t e_ = (x);                                                                \
-        if (e_ != hipSuccess) return kasf_set_error(1000 + (int)e_, hipGetErrorString(e_)); \
-    } while (0)
 
 struct Alloc {
     std::vector<Entry>* out;
@@ -774,8 +765,7 @@ int kasf_pack_weights(const kasf_model* m, const float* params, void* packed, vo
     if (check_model(m)) return 2;
     if (m->d_pack == nullptr) return kasf_set_error(4, "layout-only model has no device tables");
     kasf_launch_pack(m->cfg.dtype, (hipStream_t)stream, params, packed, m->d_pack, m->d_tile_start, (int)m->pack.size(), m->pack_tiles);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return api_done();
 }
 
 int64_t kasf_workspace_bytes(const kasf_model* m, int32_t batch, int32_t flags) {
@@ -827,7 +817,7 @@ int kasf_forward(const kasf_model* m, const float* params, const void* packed, f
                  int64_t workspace_bytes, int32_t batch, int32_t flags, void* stream) {
     struct ModelPath { explicit ModelPath(int v) { kasf_tls_model_path = v; } ~ModelPath() { kasf_tls_model_path = 0; } } model_path((flags & (KASF_FLAG_TRAIN | KASF_FLAG_KEEP)) != 0 ? 1 : 2);      // grid widths of the persistent launches (kernels.h): 1 training step, 2 forward only
     if (check_model(m)) return 2;
-    if (!params || !packed || !buffers || !x || !out || !workspace) return kasf_set_error(2, "null pointer argument");
+    if (!params || !packed || !buffers || !x || !out || !workspace) return refuse_null();
     if (m->d_pro == nullptr) return kasf_set_error(4, "layout-only model cannot run");
     if (batch < 1 || (int64_t)batch * m->cfg.n_frames * 17 * 384 >= ((int64_t)1 << 31))
         return kasf_set_error(2, "batch: 1 <= batch and batch * n_frames * 17 * 384 < 2^31 (32-bit element offsets in the kernels)");
@@ -874,16 +864,14 @@ int kasf_forward(const kasf_model* m, const float* params, const void* packed, f
     kasf_launch_linear(c.dt, c.s, xcur, 128, c.pk(t.p_fc), 128, params + t.fc_b, c.w(p.rep), 512, c.M, 512, params + t.norm_w, params + t.norm_b, nullptr, 1);
     if (flags & KASF_FLAG_RETURN_REP) kasf_launch_cast_to_f32(c.dt, c.s, c.w(p.rep), out, c.M * 512);
     else kasf_launch_head_fwd(c.dt, c.s, c.w(p.rep), params + t.head_w, params + t.head_b, out, c.M);
-    HIPCHK(hipGetLastError());
-    if (!g_err.empty()) return 3;
-    return 0;
+    return api_done(api_launchers_spoke());
 }
 
 int kasf_backward(const kasf_model* m, const float* params, const void* packed, const float* dout, float* grads, void* workspace, int64_t workspace_bytes,
                   int32_t batch, int32_t flags, int32_t stage_begin, int32_t stage_end, void* stream) {
     struct ModelPath { ModelPath() { kasf_tls_model_path = 1; } ~ModelPath() { kasf_tls_model_path = 0; } } model_path;      // grid widths of the persistent launches (kernels.h)
     if (check_model(m)) return 2;
-    if (!params || !packed || !dout || !grads || !workspace) return kasf_set_error(2, "null pointer argument");
+    if (!params || !packed || !dout || !grads || !workspace) return refuse_null();
     const int L = m->cfg.n_layers;
     if (stage_begin < 0 || stage_end > L + 2 || stage_begin > stage_end) return kasf_set_error(2, "bad stage range");
     Plan p;
@@ -980,839 +968,10 @@ int kasf_backward(const kasf_model* m, const float* params, const void* packed, 
         }
         kasf_col_flush(c.s, sink_ptrs, 3);          // every stream of the stage has joined the caller's: finish its per-channel gradients in a fixed order
     }
-    HIPCHK(hipGetLastError());
-    if (!g_err.empty()) return 3;
-    return 0;
+    return api_done(api_launchers_spoke());
 }
 
-int kasf_loss3(const float* pred, const float* target, float* dpred, float* losses, int64_t losses_floats, int32_t batch, int32_t n_frames,
-               float lambda_n_mpjpe, float lambda_velocity, float grad_scale, void* stream) {
-    if (!pred || !target || !dpred || !losses) return kasf_set_error(2, "null pointer argument");
-    if (batch < 1 || n_frames < 1) return kasf_set_error(2, "loss3: batch and n_frames must be positive");
-    if (losses_floats < 4 + 4 * (int64_t)batch) return kasf_set_error(5, "loss3: `losses` must hold 4 + 4 * batch floats (the per-clip sums live behind the result)");
-    kasf_launch_loss3((hipStream_t)stream, pred, target, dpred, losses, batch, n_frames, lambda_n_mpjpe, lambda_velocity, grad_scale);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int kasf_loss7(const float* pred, const float* target, float* dpred, float* losses, int64_t losses_floats, int32_t batch, int32_t n_frames,
-               const float* lambdas, float grad_scale, void* stream) {
-    if (!pred || !target || !dpred || !losses || !lambdas) return kasf_set_error(2, "null pointer argument");
-    if (batch < 1 || n_frames < 1) return kasf_set_error(2, "loss7: batch and n_frames must be positive");
-    if (n_frames > KASF_LOSS7_MAX_FRAMES) return kasf_set_error(2, "loss7: n_frames above KASF_LOSS7_MAX_FRAMES (a clip's angles are held in 64 KB of LDS)");
-    if (losses_floats < 8 + 8 * (int64_t)batch) return kasf_set_error(5, "loss7: `losses` must hold 8 + 8 * batch floats (the per-clip sums live behind the result)");
-    static_assert(KASF_LOSS7_MAX_FRAMES * 174 + 2048 <= 65536, "k_loss7's LDS at the largest clip");
-    kasf_launch_loss7((hipStream_t)stream, pred, target, dpred, losses, batch, n_frames, lambdas, grad_scale);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int kasf_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2, float eps,
-                    float weight_decay, int32_t step_index, float grad_scale, void* stream) {
-    if (!params || !grads || !exp_avg || !exp_avg_sq) return kasf_set_error(2, "null pointer argument");
-    if (n % 4 != 0 || step_index < 1) return kasf_set_error(2, "n must be a multiple of 4 and step_index >= 1");
-    // torch.optim.AdamW forms the bias corrections in double (1 - 0.999^t cancels badly in fp32 at small t)
-    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step_index)), bc2 = (float)(1.0 - pow((double)beta2, (double)step_index));
-    kasf_launch_adamw((hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-static bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
-
-int kasf_adamw_segments(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, const KasfOptChunk* chunks, int64_t n_chunks,
-                        const KasfAdamwClass* classes, int32_t n_classes, float grad_scale, const float* clip, void* stream) {
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !classes || (!chunks && n_chunks != 0)) return kasf_set_error(2, "null pointer argument");
-    if (misaligned16(params) || misaligned16(grads) || misaligned16(exp_avg) || misaligned16(exp_avg_sq))
-        return kasf_set_error(2, "adamw_segments: the four arrays must be 16-byte aligned");
-    if (n < 0 || n_chunks < 0) return kasf_set_error(2, "adamw_segments: negative count");
-    if (n_classes < 1 || n_classes > KASF_OPT_MAX_CLASSES) return kasf_set_error(2, "adamw_segments: n_classes outside 1..KASF_OPT_MAX_CLASSES (split the table)");
-    KasfAdamwClasses by_value;
-    memset(&by_value, 0, sizeof(by_value));
-    for (int k = 0; k < n_classes; ++k) {
-        KasfAdamwClass& c = by_value.c[k];
-        c = classes[k];
-        if (c.step < 1) return kasf_set_error(2, "adamw_segments: a class's step must be >= 1");
-        // torch.optim.AdamW forms the bias corrections in double, as kasf_adamw_step above
-        c.bc1 = (float)(1.0 - pow((double)c.beta1, (double)c.step));
-        c.bc2 = (float)(1.0 - pow((double)c.beta2, (double)c.step));
-    }
-    if (n_chunks == 0) return 0;
-    kasf_launch_adamw_segments((hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, chunks, n_chunks, by_value, grad_scale, clip, KASF_OPT_GRID_CAP);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int kasf_grad_norm(const float* grads, int64_t n, const KasfOptChunk* chunks, int64_t n_chunks, double* partial, float grad_scale, float max_norm, float* out2,
-                   void* stream) {
-    if (!grads || !out2 || ((!chunks || !partial) && n_chunks != 0)) return kasf_set_error(2, "null pointer argument");
-    if (misaligned16(grads)) return kasf_set_error(2, "grad_norm: grads must be 16-byte aligned");
-    if (n < 0 || n_chunks < 0) return kasf_set_error(2, "grad_norm: negative count");
-    if (n_chunks == 0) return 0;
-    kasf_launch_grad_norm((hipStream_t)stream, grads, chunks, n_chunks, partial, grad_scale, max_norm, out2, KASF_OPT_GRID_CAP);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int kasf_gather_clips(const float* x_all, const float* y_all, const int64_t* index, const uint8_t* flip, int64_t n_clips, int32_t batch,
-                      int32_t n_frames, float* x_out, float* y_out, void* stream) {
-    if (!x_all || !index || !x_out || (y_all && !y_out)) return kasf_set_error(2, "null pointer argument");
-    if (n_clips < 1 || n_frames < 1) return kasf_set_error(2, "gather_clips: empty clip set");
-    kasf_launch_gather_clips((hipStream_t)stream, x_all, y_all, index, flip, n_clips, batch, n_frames, x_out, y_out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_joint_flip(const float* src, float* dst, int64_t rows, void* stream) {
-    if (!src || !dst || src == dst) return kasf_set_error(2, "joint_flip: null or aliased pointers");
-    kasf_launch_joint_flip((hipStream_t)stream, src, dst, rows);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_tta_merge(const float* pred, const float* pred_of_flipped, float* out, int64_t rows, void* stream) {
-    if (!pred || !out) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_tta_merge((hipStream_t)stream, pred, pred_of_flipped, out, rows);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_eval_metrics(const float* pred, const float* label_scaled, const float* factor, const float* res, const int32_t* action, int32_t batch,
-                      int32_t n_frames, int32_t n_actions, float* mpjpe, float* p_mpjpe, float* accel, float* jpe, double* action_sums, void* stream) {
-    if (!pred || !label_scaled || !factor || !res || !mpjpe || !p_mpjpe || !accel || !jpe) return kasf_set_error(2, "null pointer argument");
-    if (n_frames < 3 || n_frames > 256) return kasf_set_error(2, "eval_metrics: n_frames must be in [3,256]");
-    if ((action == nullptr) != (action_sums == nullptr)) return kasf_set_error(2, "eval_metrics: action and action_sums go together");
-    g_err.clear();
-    kasf_launch_eval_metrics((hipStream_t)stream, pred, label_scaled, factor, res, action, batch, n_frames, n_actions, mpjpe, p_mpjpe, accel, jpe, action_sums);
-    HIPCHK(hipGetLastError());
-    return g_err.empty() ? 0 : 3;
-}
-
-static const char* lift_plan_error(int64_t n, int32_t T, int32_t stride) {
-    if (T < 1 || T > 256) return "lift: T must be in [1, 256]";
-    if (stride < 1 || stride > T) return "lift: stride must be in [1, T]";
-    if (n < 0) return "lift: n must be >= 0";
-    return nullptr;
-}
-// the plan has a resampled window: the track is shorter than T, or the demo's windows (stride == T) leave a short tail
-static bool lift_plan_needs_table(int64_t n, int32_t T, int32_t stride) { return n > 0 && (n < T || (stride == T && n % T != 0)); }
-
-int64_t kasf_lift_window_count(int64_t n, int32_t T, int32_t stride) {
-    if (const char* e = lift_plan_error(n, T, stride)) return -(int64_t)kasf_set_error(2, e);
-    return kasf_lift_window_count_of(n, T, stride);
-}
-int kasf_lift_windows(const float* track, int32_t persons, int64_t n, float width, float height, int32_t T, int32_t stride, const int32_t* resample,
-                      int32_t flip, float* x_out, void* stream) {
-    if (const char* e = lift_plan_error(n, T, stride)) return kasf_set_error(2, e);
-    if (persons < 0) return kasf_set_error(2, "lift: persons must be >= 0");
-    if (!(width > 0.0f) || !(height > 0.0f)) return kasf_set_error(2, "lift: width and height must be positive");
-    if (persons == 0 || n == 0) return 0;
-    if (!track || !x_out) return kasf_set_error(2, "null pointer argument");
-    if (resample == nullptr && lift_plan_needs_table(n, T, stride)) return kasf_set_error(2, "lift: this plan has a resampled window and needs the resample table");
-    kasf_launch_lift_windows((hipStream_t)stream, track, persons, n, width, height, T, stride, resample, flip ? 1 : 0, x_out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_lift_stitch(const float* pred, int32_t flip, int32_t persons, int64_t n, int32_t T, int32_t stride, const int32_t* first_pos, float* out,
-                     void* stream) {
-    if (const char* e = lift_plan_error(n, T, stride)) return kasf_set_error(2, e);
-    if (persons < 0) return kasf_set_error(2, "lift: persons must be >= 0");
-    if (persons == 0 || n == 0) return 0;
-    if (!pred || !out) return kasf_set_error(2, "null pointer argument");
-    if (first_pos == nullptr && lift_plan_needs_table(n, T, stride)) return kasf_set_error(2, "lift: this plan has a resampled window and needs first_pos");
-    kasf_launch_lift_stitch((hipStream_t)stream, pred, flip ? 1 : 0, persons, n, T, stride, first_pos, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int64_t kasf_lift_ragged_plan(const int64_t* lengths, int32_t tracks, int32_t T, int32_t stride, int64_t* win_first) {
-    if (const char* e = lift_plan_error(0, T, stride)) return -(int64_t)kasf_set_error(2, e);
-    if (tracks < 0) return -(int64_t)kasf_set_error(2, "lift: tracks must be >= 0");
-    if (!win_first || (tracks > 0 && !lengths)) return -(int64_t)kasf_set_error(2, "null pointer argument");
-    int64_t total = 0;
-    for (int32_t p = 0; p < tracks; ++p) {                 // validate everything before writing anything
-        if (lengths[p] < 0) return -(int64_t)kasf_set_error(2, "lift: track lengths must be >= 0");
-        const int64_t w = kasf_lift_window_count_of(lengths[p], T, stride);
-        if (total > INT64_MAX - w) return -(int64_t)kasf_set_error(2, "lift: too many windows");
-        total += w;
-    }
-    win_first[0] = 0;
-    for (int32_t p = 0; p < tracks; ++p) win_first[p + 1] = win_first[p] + kasf_lift_window_count_of(lengths[p], T, stride);
-    return total;
-}
-// the host's sizes of the packed arrays: every window has a frame, every frame a track, and no track has more windows than frames
-static const char* lift_ragged_error(int32_t tracks, int64_t frames, int64_t windows, int32_t T, int32_t stride) {
-    if (const char* e = lift_plan_error(0, T, stride)) return e;
-    if (tracks < 0 || frames < 0 || windows < 0) return "lift: tracks, frames and windows must be >= 0";
-    if ((frames == 0) != (windows == 0) || windows > frames || (tracks == 0 && frames > 0))
-        return "lift: tracks, frames and windows do not belong to one plan";
-    return nullptr;
-}
-int kasf_lift_windows_ragged(const float* packed, const int64_t* offsets, const int64_t* win_first, int32_t tracks, int64_t frames, int64_t windows,
-                             const float* width, const float* height, int32_t T, int32_t stride, const int32_t* resample, int32_t flip, float* x_out,
-                             void* stream) {
-    if (const char* e = lift_ragged_error(tracks, frames, windows, T, stride)) return kasf_set_error(2, e);
-    if (windows == 0) return 0;
-    if (!packed || !offsets || !win_first || !width || !height || !resample || !x_out) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_lift_windows_ragged((hipStream_t)stream, packed, frames, offsets, win_first, tracks, windows, width, height, T, stride, resample,
-                                    flip ? 1 : 0, x_out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_lift_stitch_ragged(const float* pred, int32_t flip, const int64_t* offsets, const int64_t* win_first, int32_t tracks, int64_t frames,
-                            int64_t windows, int32_t T, int32_t stride, const int32_t* first_pos, float* out, void* stream) {
-    if (const char* e = lift_ragged_error(tracks, frames, windows, T, stride)) return kasf_set_error(2, e);
-    if (frames == 0) return 0;
-    if (!pred || !offsets || !win_first || !first_pos || !out) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_lift_stitch_ragged((hipStream_t)stream, pred, flip ? 1 : 0, windows, offsets, win_first, tracks, frames, T, stride, first_pos, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ---- one new frame per tick (kasf.h, kasf_stream_*) ----
-int kasf_stream_tables(int32_t T, int32_t* resample_tab, int32_t* first_pos_tab) {
-    if (T < 1 || T > 256) return kasf_set_error(2, "stream: T must be in [1, 256]");
-    if (!resample_tab || !first_pos_tab) return kasf_set_error(2, "null pointer argument");
-    for (int64_t i = 0; i < (int64_t)(T + 1) * T; ++i) resample_tab[i] = first_pos_tab[i] = 0;
-    for (int32_t n = 1; n <= T; ++n) {
-        int32_t* r = resample_tab + (int64_t)n * T;
-        int32_t* fp = first_pos_tab + (int64_t)n * T;
-        for (int32_t t = 0; t < T; ++t) {                  // demo.py:132-136: np.linspace(0, n, T, endpoint=False) is t * (n / T) in float64; floor; clip
-            const int64_t v = (int64_t)floor((double)t * ((double)n / (double)T));
-            r[t] = (int32_t)(v < 0 ? 0 : (v > n - 1 ? n - 1 : v));
-        }
-        for (int32_t t = T - 1; t >= 0; --t) fp[r[t]] = t;  // the first t of every frame (demo.py:146-153, np.unique(r, return_index=True)[1])
-    }
-    return 0;
-}
-static const char* stream_error(const void* slots, int32_t K, int32_t S, int32_t T) {
-    if (T < 1 || T > 256) return "stream: T must be in [1, 256]";
-    if (S < 0 || K < 0 || K > S) return "stream: need 0 <= K <= S";
-    if (slots == nullptr && K != 0 && K != S) return "stream: without slot ids the call covers every slot (K == S)";
-    return nullptr;
-}
-int kasf_stream_push(const float* frames, const int32_t* slots, int32_t K, int32_t S, int32_t T, float* ring, int64_t* count, void* stream) {
-    if (const char* e = stream_error(slots, K, S, T)) return kasf_set_error(2, e);
-    if (K == 0) return 0;
-    if (!frames || !ring || !count) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_stream_push((hipStream_t)stream, frames, slots, K, S, T, ring, count);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_stream_windows(const float* ring, const int64_t* count, const int32_t* slots, int32_t K, int32_t S, int32_t T, const float* width,
-                        const float* height, const int32_t* resample_tab, int32_t flip, float* x_out, void* stream) {
-    if (const char* e = stream_error(slots, K, S, T)) return kasf_set_error(2, e);
-    if (K == 0) return 0;
-    if (!ring || !count || !width || !height || !resample_tab || !x_out) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_stream_windows((hipStream_t)stream, ring, count, slots, K, S, T, width, height, resample_tab, flip ? 1 : 0, x_out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_stream_emit(const float* pred, int32_t flip, const int64_t* count, const int32_t* slots, int32_t K, int32_t S, int32_t T,
-                     const int32_t* first_pos_tab, int32_t back, int32_t n_out, float* out, void* stream) {
-    if (const char* e = stream_error(slots, K, S, T)) return kasf_set_error(2, e);
-    if (back < 0 || back > T - 1) return kasf_set_error(2, "stream: back must be in [0, T - 1]");
-    if (n_out < 0 || n_out > T) return kasf_set_error(2, "stream: n_out must be in [0, T]");
-    if (K == 0 || n_out == 0) return 0;
-    if (!pred || !count || !first_pos_tab || !out) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_stream_emit((hipStream_t)stream, pred, flip ? 1 : 0, count, slots, K, S, T, first_pos_tab, back, n_out, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ---- the stream lifter's slots driven by the tracker's output (kasf.h, kasf_stream_track_*) ----
-int kasf_stream_track_front(const float* frames, const int32_t* ids, const int32_t* slot, const int32_t* born, const int32_t* count_b, int32_t streams,
-                            int32_t track_slots, int32_t rows_mode, int32_t R, int32_t T, float* ring, int64_t* count, int32_t* owner, const float* width,
-                            const float* height, const int32_t* resample_tab, int32_t flip, float* x_out, int32_t* row_slot, void* stream) {
-    if (T < 1 || T > 256) return kasf_set_error(2, "stream_track: T must be in [1, 256]");
-    if (streams < 1) return kasf_set_error(2, "stream_track: streams must be >= 1");
-    if (track_slots < 1 || track_slots > KASF_SORT_MAX) return kasf_set_error(2, "stream_track: track_slots must be in [1, 64]");
-    if (R < 1) return kasf_set_error(2, "stream_track: R must be >= 1");
-    if (rows_mode != KASF_ROWS_PERSONS && rows_mode != KASF_ROWS_TRACKS) return kasf_set_error(2, "stream_track: rows_mode must be KASF_ROWS_PERSONS or KASF_ROWS_TRACKS");
-    if ((int64_t)streams * R > INT32_MAX || (int64_t)streams * track_slots > INT32_MAX) return kasf_set_error(2, "stream_track: streams * R and streams * track_slots must fit 32 bits");
-    if (!frames || !ids || !slot || !born || !count_b || !ring || !count || !owner || !width || !height || !resample_tab || !x_out || !row_slot)
-        return kasf_set_error(2, "null pointer argument");
-    kasf_launch_stream_track_front((hipStream_t)stream, frames, ids, slot, born, count_b, streams, track_slots, rows_mode, R, T, ring, count, owner, width, height,
-                                   resample_tab, flip ? 1 : 0, x_out, row_slot);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_stream_track_emit(const float* pred, int32_t flip, const int64_t* count, const int32_t* owner, const int32_t* row_slot, int32_t n_rows, int32_t T,
-                           const int32_t* first_pos_tab, int32_t back, float* out, uint8_t* valid, int32_t* ids_out, int64_t* frames_out, void* stream) {
-    if (T < 1 || T > 256) return kasf_set_error(2, "stream_track: T must be in [1, 256]");
-    if (back < 0 || back > T - 1) return kasf_set_error(2, "stream_track: back must be in [0, T - 1]");
-    if (n_rows < 0) return kasf_set_error(2, "stream_track: n_rows must be >= 0");
-    if (n_rows == 0) return 0;
-    if (!pred || !count || !owner || !row_slot || !first_pos_tab || !out || !valid || !ids_out || !frames_out) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_stream_track_emit((hipStream_t)stream, pred, flip ? 1 : 0, count, owner, row_slot, n_rows, T, first_pos_tab, back, out, valid, ids_out, frames_out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ---- the One-Euro filter with its state on the device (kasf.h, kasf_one_euro_*) ----
-static const char* one_euro_error(int32_t J, int32_t C, const kasf_one_euro_params* p, KasfOneEuro* out) {
-    if (J < 1 || J > 256) return "one_euro: J must be in [1, 256]";
-    if (C < 1 || C > 4) return "one_euro: C must be in [1, 4]";
-    if (p == nullptr) return "null pointer argument";
-    const float in_hz[3] = {p->dt, p->min_cutoff, p->d_cutoff};
-    for (float v : in_hz)
-        if (!(v >= 1e-6f && v <= 1e6f)) return "one_euro: dt, min_cutoff and d_cutoff must be in [1e-6, 1e6]";
-    if (!(p->beta >= 0.0f && p->beta <= 1e6f)) return "one_euro: beta must be in [0, 1e6]";
-    if (!std::isfinite(p->min_score)) return "one_euro: min_score must be finite";
-    if (p->max_hold < 0 || p->max_hold > (1 << 20)) return "one_euro: max_hold must be in [0, 2^20]";
-    *out = KasfOneEuro{p->dt, p->min_cutoff, p->d_cutoff, p->beta, p->min_score, p->max_hold};
-    return nullptr;
-}
-int kasf_one_euro_push(const float* x, const int32_t* slots, int32_t K, int32_t S, int32_t J, int32_t C, int32_t has_score, const kasf_one_euro_params* params,
-                       int64_t tick, float* xhat, float* dxhat, int64_t* last, float* out, void* stream) {
-    KasfOneEuro p;
-    if (const char* e = one_euro_error(J, C, params, &p)) return kasf_set_error(2, e);
-    if (const char* e = stream_error(slots, K, S, 1)) return kasf_set_error(2, e);
-    if (tick < 0) return kasf_set_error(2, "one_euro: tick must be >= 0");
-    if (K == 0) return 0;
-    if (!x || !xhat || !dxhat || !last || !out) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_one_euro_push((hipStream_t)stream, x, slots, K, S, J, C, has_score ? 1 : 0, p, tick, xhat, dxhat, last, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_one_euro_tracked(const float* x, const int32_t* ids, const int32_t* slot, const int32_t* born, const int32_t* count_b, int32_t streams,
-                          int32_t track_slots, int32_t rows_mode, int32_t R, int32_t J, int32_t C, int32_t has_score, const kasf_one_euro_params* params,
-                          int64_t tick, float* xhat, float* dxhat, int64_t* last, int32_t* owner, float* out, int32_t* row_slot, void* stream) {
-    KasfOneEuro p;
-    if (const char* e = one_euro_error(J, C, params, &p)) return kasf_set_error(2, e);
-    if (streams < 1) return kasf_set_error(2, "one_euro: streams must be >= 1");
-    if (track_slots < 1 || track_slots > KASF_SORT_MAX) return kasf_set_error(2, "one_euro: track_slots must be in [1, 64]");
-    if (R < 1) return kasf_set_error(2, "one_euro: R must be >= 1");
-    if (rows_mode != KASF_ROWS_PERSONS && rows_mode != KASF_ROWS_TRACKS) return kasf_set_error(2, "one_euro: rows_mode must be KASF_ROWS_PERSONS or KASF_ROWS_TRACKS");
-    if ((int64_t)streams * R > INT32_MAX || (int64_t)streams * track_slots > INT32_MAX) return kasf_set_error(2, "one_euro: streams * R and streams * track_slots must fit 32 bits");
-    if (tick < 0) return kasf_set_error(2, "one_euro: tick must be >= 0");
-    if (!x || !ids || !slot || !born || !count_b || !xhat || !dxhat || !last || !owner || !out) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_one_euro_tracked((hipStream_t)stream, x, ids, slot, born, count_b, streams, track_slots, rows_mode, R, J, C, has_score ? 1 : 0, p, tick, xhat, dxhat,
-                                 last, owner, out, row_slot);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_one_euro_tracks(const float* x, const int64_t* offsets, int64_t N, int32_t P, int32_t J, int32_t C, int32_t has_score,
-                         const kasf_one_euro_params* params, float* out, void* stream) {
-    KasfOneEuro p;
-    if (const char* e = one_euro_error(J, C, params, &p)) return kasf_set_error(2, e);
-    if (P < 0 || N < 0) return kasf_set_error(2, "one_euro: P and N must be >= 0");
-    if (P == 0) return 0;
-    if (!offsets || (N > 0 && (!x || !out))) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_one_euro_tracks((hipStream_t)stream, x, offsets, N, P, J, C, has_score ? 1 : 0, p, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ---- the two ends of the lift (kasf.h, kasf_coco_h36m / kasf_pose_world) ----
-int kasf_coco_h36m(const float* coco, int64_t frames, float* h36m, void* stream) {
-    if (frames < 0) return kasf_set_error(2, "coco_h36m: frames must be >= 0");
-    if (frames == 0) return 0;
-    if (!coco || !h36m) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_coco_h36m((hipStream_t)stream, coco, frames, h36m);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_pose_world(const float* poses, int64_t frames, const float* quat4, const float* trans3, int32_t floor, int32_t unit, float* out, void* stream) {
-    if (frames < 0) return kasf_set_error(2, "pose_world: frames must be >= 0");
-    if (frames == 0) return 0;
-    if (!poses || !quat4 || !out) return kasf_set_error(2, "null pointer argument");
-    const float zero[3] = {0.0f, 0.0f, 0.0f};
-    kasf_launch_pose_world((hipStream_t)stream, poses, frames, quat4, trans3 ? trans3 : zero, floor ? 1 : 0, unit ? 1 : 0, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ---- pose-network heatmaps -> keypoints (kasf.h, kasf_heatmap_keypoints) ----
-// what the plain and the flip-tested entry point refuse alike, in this order; who = the entry point's name in its messages
-static int heatmap_refusal(const char* who, int64_t n, int32_t H, int32_t W, int32_t dtype, int32_t geom_kind, int32_t out_layout, double aspect) {
-    const char* why = nullptr;
-    if (n < 0) why = "n must be >= 0";
-    else if (H < 1 || W < 1) why = "H and W must be >= 1";
-    else if ((int64_t)H * W > ((int64_t)1 << 24)) why = "H * W must be <= 2^24 (the reference's index arithmetic is fp32)";
-    else if (dtype != KASF_F32 && dtype != KASF_F16 && dtype != KASF_BF16) why = "dtype must be KASF_DTYPE_F32, _F16 or _BF16";
-    else if (geom_kind != KASF_GEOM_CENTER_SCALE && geom_kind != KASF_GEOM_BOX) why = "geom_kind must be KASF_GEOM_CENTER_SCALE or KASF_GEOM_BOX";
-    else if (out_layout != KASF_LAYOUT_COCO && out_layout != KASF_LAYOUT_H36M) why = "out_layout must be KASF_LAYOUT_COCO or KASF_LAYOUT_H36M";
-    else if (geom_kind == KASF_GEOM_BOX && !(aspect > 0.0)) why = "aspect must be > 0 with KASF_GEOM_BOX";
-    return why ? kasf_set_error(2, (std::string(who) + ": " + why).c_str()) : 0;
-}
-int kasf_heatmap_keypoints(const void* hm, int32_t dtype, int64_t n, int32_t H, int32_t W, const float* geom, int32_t geom_kind, double aspect, int32_t refine,
-                           int32_t out_layout, float* out, float* coco_scratch, void* stream) {
-    if (heatmap_refusal("heatmap_keypoints", n, H, W, dtype, geom_kind, out_layout, aspect)) return 2;
-    if (n == 0) return 0;
-    if (!hm || !geom || !out || (out_layout == KASF_LAYOUT_H36M && !coco_scratch)) return kasf_set_error(2, "null pointer argument");
-    const bool h36m = out_layout == KASF_LAYOUT_H36M;
-    kasf_launch_heatmap_keypoints((hipStream_t)stream, hm, dtype, n, H, W, geom, geom_kind, aspect, refine ? 1 : 0, h36m ? coco_scratch : out);
-    if (h36m) kasf_launch_coco_h36m((hipStream_t)stream, coco_scratch, n, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ---- flip-tested pose-network heatmaps -> keypoints (kasf.h, kasf_heatmap_flip_keypoints) ----
-int kasf_heatmap_flip_keypoints(const void* hm, const void* hm_flipped, int32_t dtype, int64_t n, int32_t H, int32_t W, const int32_t* partner, int32_t shift,
-                                const float* geom, int32_t geom_kind, double aspect, int32_t refine, int32_t out_layout, float* out, float* coco_scratch,
-                                float* merged_out, void* stream) {
-    static const int32_t coco_pairs[17] = {0, 2, 1, 4, 3, 6, 5, 8, 7, 10, 9, 12, 11, 14, 13, 16, 15};
-    if (heatmap_refusal("heatmap_flip_keypoints", n, H, W, dtype, geom_kind, out_layout, aspect)) return 2;
-    const int32_t* pt = partner ? partner : coco_pairs;
-    for (int j = 0; j < 17; ++j)
-        if (pt[j] < 0 || pt[j] > 16) return kasf_set_error(2, "heatmap_flip_keypoints: partner entries must be in [0, 16]");
-    for (int j = 0; j < 17; ++j)
-        if (pt[pt[j]] != j) return kasf_set_error(2, "heatmap_flip_keypoints: partner must be an involution (partner[partner[j]] == j)");
-    if (n == 0) return 0;
-    if (!hm || !hm_flipped || !geom || !out || (out_layout == KASF_LAYOUT_H36M && !coco_scratch)) return kasf_set_error(2, "null pointer argument");
-    if (merged_out && ((const void*)merged_out == hm || (const void*)merged_out == hm_flipped))
-        return kasf_set_error(2, "heatmap_flip_keypoints: merged_out must not overlap hm or hm_flipped");
-    const bool h36m = out_layout == KASF_LAYOUT_H36M;
-    int pv[17];
-    for (int j = 0; j < 17; ++j) pv[j] = pt[j];
-    kasf_launch_heatmap_flip_keypoints((hipStream_t)stream, hm, hm_flipped, dtype, n, H, W, pv, shift ? 1 : 0, geom, geom_kind, aspect, refine ? 1 : 0,
-                                       h36m ? coco_scratch : out, merged_out);
-    if (h36m) kasf_launch_coco_h36m((hipStream_t)stream, coco_scratch, n, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ---- DARK / UDP sub-pixel heatmap decode (kasf.h, kasf_heatmap_decode) ----
-int kasf_heatmap_decode(const void* hm, const void* hm_flipped, int32_t dtype, int64_t n, int32_t H, int32_t W, const int32_t* partner, int32_t shift,
-                        const float* geom, int32_t geom_kind, double aspect, int32_t mode, const float* weights, int32_t K, int32_t udp, int32_t out_layout,
-                        float* out, float* coco_scratch, float* merged_out, void* stream) {
-    static const int32_t coco_pairs[17] = {0, 2, 1, 4, 3, 6, 5, 8, 7, 10, 9, 12, 11, 14, 13, 16, 15};
-    if (heatmap_refusal("heatmap_decode", n, H, W, dtype, geom_kind, out_layout, aspect)) return 2;
-    if (mode != KASF_DECODE_QUARTER && mode != KASF_DECODE_DARK && mode != KASF_DECODE_DARK_UDP)
-        return kasf_set_error(2, "heatmap_decode: mode must be KASF_DECODE_QUARTER, _DARK or _DARK_UDP");
-    if (K < 1 || K > 17 || K % 2 == 0) return kasf_set_error(2, "heatmap_decode: K must be odd and in [1, 17]");
-    if (mode != KASF_DECODE_QUARTER && !weights) return kasf_set_error(2, "heatmap_decode: weights must be given with KASF_DECODE_DARK and _DARK_UDP");
-    if (udp && (H < 2 || W < 2)) return kasf_set_error(2, "heatmap_decode: udp needs H and W >= 2");
-    const int32_t* pt = partner ? partner : coco_pairs;
-    if (hm_flipped || partner) {
-        for (int j = 0; j < 17; ++j)
-            if (pt[j] < 0 || pt[j] > 16) return kasf_set_error(2, "heatmap_decode: partner entries must be in [0, 16]");
-        for (int j = 0; j < 17; ++j)
-            if (pt[pt[j]] != j) return kasf_set_error(2, "heatmap_decode: partner must be an involution (partner[partner[j]] == j)");
-    }
-    if (n == 0) return 0;
-    if (!hm || !geom || !out || (out_layout == KASF_LAYOUT_H36M && !coco_scratch)) return kasf_set_error(2, "null pointer argument");
-    if (merged_out && !hm_flipped) return kasf_set_error(2, "heatmap_decode: merged_out goes with hm_flipped");
-    if (merged_out && ((const void*)merged_out == hm || (const void*)merged_out == hm_flipped))
-        return kasf_set_error(2, "heatmap_decode: merged_out must not overlap hm or hm_flipped");
-    const bool h36m = out_layout == KASF_LAYOUT_H36M;
-    int pv[17];
-    for (int j = 0; j < 17; ++j) pv[j] = pt[j];
-    kasf_launch_heatmap_decode((hipStream_t)stream, hm, hm_flipped, dtype, n, H, W, pv, shift ? 1 : 0, geom, geom_kind, aspect, mode, weights, K, udp ? 1 : 0,
-                               h36m ? coco_scratch : out, merged_out);
-    if (h36m) kasf_launch_coco_h36m((hipStream_t)stream, coco_scratch, n, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ---- person boxes -> pose-network inputs (kasf.h, kasf_crop_persons) ----
-int kasf_crop_persons(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, const int32_t* frame_index,
-                      const float* geom, int32_t geom_kind, double aspect, int64_t n, void* out, int32_t out_dtype, int32_t out_w, int32_t out_h,
-                      const float* mean_std, int32_t swap_rb, float* center_scale_out, void* stream) {
-    if (n < 0) return kasf_set_error(2, "crop_persons: n must be >= 0");
-    if (out_w < 1 || out_h < 1 || out_w > 32767 || out_h > 32767) return kasf_set_error(2, "crop_persons: out_w and out_h must be in [1, 32767]");
-    if (Hf < 1 || Hf > 32767 || Wf < 1 || Wf > 32767) return kasf_set_error(2, "crop_persons: Hf and Wf must be in [1, 32767]");
-    if (n_frames < 1) return kasf_set_error(2, "crop_persons: n_frames must be >= 1");
-    if (row_stride < (int64_t)3 * Wf) return kasf_set_error(2, "crop_persons: the row stride must be at least 3 * Wf bytes");
-    if (n_frames > 1 && frame_stride < 0) return kasf_set_error(2, "crop_persons: the frame stride must be >= 0");
-    if (out_dtype != KASF_F32 && out_dtype != KASF_F16 && out_dtype != KASF_BF16) return kasf_set_error(2, "crop_persons: out_dtype must be KASF_DTYPE_F32, _F16 or _BF16");
-    if (geom_kind != KASF_GEOM_CENTER_SCALE && geom_kind != KASF_GEOM_BOX) return kasf_set_error(2, "crop_persons: geom_kind must be KASF_GEOM_CENTER_SCALE or KASF_GEOM_BOX");
-    if (geom_kind == KASF_GEOM_BOX && !(aspect > 0.0)) return kasf_set_error(2, "crop_persons: aspect must be > 0 with KASF_GEOM_BOX");
-    if (!mean_std) return kasf_set_error(2, "null pointer argument");
-    for (int c = 0; c < 3; ++c)
-        if (!std::isfinite(mean_std[3 + c]) || mean_std[3 + c] == 0.0f) return kasf_set_error(2, "crop_persons: every std must be finite and not 0");
-    if (n == 0) return 0;
-    if (!frames || !geom || !out || (n_frames > 1 && !frame_index)) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_crop_persons((hipStream_t)stream, frames, n_frames, Hf, Wf, row_stride, frame_stride, frame_index, geom, geom_kind, aspect, n, out, out_dtype,
-                             out_w, out_h, mean_std, swap_rb ? 1 : 0, center_scale_out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ---- video frames -> detector inputs (kasf.h, kasf_letterbox_plan / kasf_letterbox_frames) ----
-int kasf_letterbox_plan(int32_t Wf, int32_t Hf, int32_t out_w, int32_t out_h, int32_t* new_w, int32_t* new_h, int32_t* pad_x, int32_t* pad_y) {
-    if (Hf < 1 || Hf > 32767 || Wf < 1 || Wf > 32767) return kasf_set_error(2, "letterbox: Hf and Wf must be in [1, 32767]");
-    if (out_w < 1 || out_h < 1 || out_w > KASF_LETTERBOX_MAX_SIDE || out_h > KASF_LETTERBOX_MAX_SIDE)
-        return kasf_set_error(2, "letterbox: out_w and out_h must be in [1, 4096] (KASF_LETTERBOX_MAX_SIDE: one table entry per output column in LDS)");
-    if (!new_w || !new_h || !pad_x || !pad_y) return kasf_set_error(2, "null pointer argument");
-    // rule 1: the reference's int(img_w * min(w / img_w, h / img_h)) in the same IEEE doubles
-    const double rw = (double)out_w / (double)Wf, rh = (double)out_h / (double)Hf;
-    const double r = rh < rw ? rh : rw;
-    const int32_t nw = (int32_t)((double)Wf * r), nh = (int32_t)((double)Hf * r);
-    if (nw < 1 || nh < 1) return kasf_set_error(2, "letterbox: the frame is so elongated that the resized image has no pixels (new_w or new_h < 1)");
-    *new_w = nw; *new_h = nh;
-    *pad_x = (out_w - nw) / 2; *pad_y = (out_h - nh) / 2;
-    return 0;
-}
-
-int kasf_letterbox_frames(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, void* out, int32_t out_dtype,
-                          int32_t out_w, int32_t out_h, int32_t pad_value, int32_t swap_rb, void* stream) {
-    if (n_frames < 0) return kasf_set_error(2, "letterbox_frames: n_frames must be >= 0");
-    int32_t new_w, new_h, pad_x, pad_y;
-    if (kasf_letterbox_plan(Wf, Hf, out_w, out_h, &new_w, &new_h, &pad_x, &pad_y)) return 2;
-    if (row_stride < (int64_t)3 * Wf) return kasf_set_error(2, "letterbox_frames: the row stride must be at least 3 * Wf bytes");
-    if (frame_stride < 0) return kasf_set_error(2, "letterbox_frames: the frame stride must be >= 0");
-    if (n_frames > 1 && frame_stride / Hf < row_stride)     // frame_stride < Hf * row_stride, without the product that a huge row_stride overflows
-        return kasf_set_error(2, "letterbox_frames: the frame stride must be at least Hf * row_stride with more than one frame");
-    if (out_dtype != KASF_F32 && out_dtype != KASF_F16 && out_dtype != KASF_BF16) return kasf_set_error(2, "letterbox_frames: out_dtype must be KASF_DTYPE_F32, _F16 or _BF16");
-    if (pad_value < 0 || pad_value > 255) return kasf_set_error(2, "letterbox_frames: pad_value must be in [0, 255]");
-    if (n_frames == 0) return 0;
-    if (!frames || !out) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_letterbox((hipStream_t)stream, frames, n_frames, Hf, Wf, row_stride, frame_stride, out, out_dtype, out_w, out_h, new_w, new_h, pad_x, pad_y,
-                          pad_value, swap_rb ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ---- decoder surfaces -> BGR frames (kasf.h, kasf_yuv420_to_bgr) ----
-int kasf_yuv420_to_bgr(const void* y, const void* c0, const void* c1, int32_t layout, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t y_row_stride,
-                       int64_t c_row_stride, int64_t y_frame_stride, int64_t c_frame_stride, void* out, int64_t out_row_stride, int64_t out_frame_stride,
-                       int32_t matrix, int32_t full_range, int32_t rgb, void* stream) {
-    static const int kCoef[2][2][5] = {{KASF_YUV_COEF_BT601_LIMITED, KASF_YUV_COEF_BT601_FULL}, {KASF_YUV_COEF_BT709_LIMITED, KASF_YUV_COEF_BT709_FULL}};
-    if (n_frames < 0) return kasf_set_error(2, "yuv420_to_bgr: n_frames must be >= 0");
-    if (Hf < 1 || Hf > 32767 || Wf < 1 || Wf > 32767) return kasf_set_error(2, "yuv420_to_bgr: Hf and Wf must be in [1, 32767]");
-    if (layout != KASF_YUV_NV12 && layout != KASF_YUV_I420) return kasf_set_error(2, "yuv420_to_bgr: layout must be KASF_YUV_NV12 or KASF_YUV_I420");
-    if (matrix != KASF_YUV_BT601 && matrix != KASF_YUV_BT709) return kasf_set_error(2, "yuv420_to_bgr: matrix must be KASF_YUV_BT601 or KASF_YUV_BT709");
-    const bool nv12 = layout == KASF_YUV_NV12;
-    const int64_t cw = (Wf + 1) / 2, ch = (Hf + 1) / 2;
-    if (y_row_stride < Wf) return kasf_set_error(2, "yuv420_to_bgr: the luma row stride must be at least Wf bytes");
-    if (c_row_stride < (nv12 ? 2 * cw : cw))
-        return kasf_set_error(2, "yuv420_to_bgr: the chroma row stride must be at least 2 * ((Wf + 1) / 2) bytes for NV12, (Wf + 1) / 2 for I420");
-    if (out_row_stride < (int64_t)3 * Wf) return kasf_set_error(2, "yuv420_to_bgr: the output row stride must be at least 3 * Wf bytes");
-    if (y_frame_stride < 0 || c_frame_stride < 0 || out_frame_stride < 0) return kasf_set_error(2, "yuv420_to_bgr: the frame strides must be >= 0");
-    // frame_stride < rows * row_stride, without the product that a huge row stride overflows
-    if (n_frames > 1 && (y_frame_stride / Hf < y_row_stride || c_frame_stride / ch < c_row_stride || out_frame_stride / Hf < out_row_stride))
-        return kasf_set_error(2, "yuv420_to_bgr: with more than one frame every frame stride must cover its plane (rows * row stride)");
-    if (nv12 ? c1 != nullptr : c1 == nullptr) return kasf_set_error(2, "yuv420_to_bgr: c1 is the V plane of I420 and must be NULL for NV12");
-    if (n_frames == 0) return 0;
-    if (!y || !c0 || !out) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_yuv420_to_bgr((hipStream_t)stream, y, c0, c1, nv12 ? 1 : 0, n_frames, Hf, Wf, y_row_stride, c_row_stride, y_frame_stride, c_frame_stride, out,
-                              out_row_stride, out_frame_stride, kCoef[matrix][full_range ? 1 : 0], full_range ? 1 : 0, rgb ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ---- skeletons over the frame and the encoder's surface (kasf.h, kasf_draw_poses / kasf_bgr_to_nv12 / kasf_pose_panel) ----
-int kasf_draw_poses(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, const float* keypoints, int32_t P,
-                    int32_t J, int32_t C, int64_t kp_frame_stride, int64_t kp_person_stride, int64_t kp_joint_stride, int64_t kp_coord_stride,
-                    const uint8_t* valid, int64_t valid_frame_stride, int64_t valid_person_stride, const int32_t* segments, const uint8_t* colors, int32_t S,
-                    const uint8_t* dot_color, int32_t thickness, int32_t dot_radius, float min_score, const int32_t* fills, int32_t R, void* out_bgr,
-                    int64_t out_row_stride, int64_t out_frame_stride, void* out_y, void* out_uv, int64_t y_row_stride, int64_t uv_row_stride,
-                    int64_t y_frame_stride, int64_t uv_frame_stride, int32_t matrix, int32_t full_range, int32_t rgb, void* stream) {
-    static const int kCoef[2][2][8] = {{KASF_RGB2YUV_COEF_BT601_LIMITED, KASF_RGB2YUV_COEF_BT601_FULL}, {KASF_RGB2YUV_COEF_BT709_LIMITED, KASF_RGB2YUV_COEF_BT709_FULL}};
-    if (n_frames < 0) return kasf_set_error(2, "draw_poses: n_frames must be >= 0");
-    if (Hf < 1 || Hf > 32767 || Wf < 1 || Wf > 32767) return kasf_set_error(2, "draw_poses: Hf and Wf must be in [1, 32767]");
-    if (matrix != KASF_YUV_BT601 && matrix != KASF_YUV_BT709) return kasf_set_error(2, "draw_poses: matrix must be KASF_YUV_BT601 or KASF_YUV_BT709");
-    if (!out_bgr && !out_y && !out_uv) return kasf_set_error(2, "draw_poses: out_bgr, or out_y and out_uv, must be given");
-    if (!out_y != !out_uv) return kasf_set_error(2, "draw_poses: out_y and out_uv are one surface: both or neither");
-    const int64_t cw = (Wf + 1) / 2, ch = (Hf + 1) / 2;
-    if (row_stride < (int64_t)3 * Wf) return kasf_set_error(2, "draw_poses: the row stride must be at least 3 * Wf bytes");
-    if (frame_stride < 0) return kasf_set_error(2, "draw_poses: the frame strides must be >= 0");
-    // frame_stride < rows * row_stride, without the product that a huge row stride overflows
-    if (n_frames > 1 && frame_stride / Hf < row_stride) return kasf_set_error(2, "draw_poses: with more than one frame every frame stride must cover its plane (rows * row stride)");
-    if (out_bgr) {
-        if (out_row_stride < (int64_t)3 * Wf) return kasf_set_error(2, "draw_poses: the output row stride must be at least 3 * Wf bytes");
-        if (out_frame_stride < 0) return kasf_set_error(2, "draw_poses: the frame strides must be >= 0");
-        if (n_frames > 1 && out_frame_stride / Hf < out_row_stride)
-            return kasf_set_error(2, "draw_poses: with more than one frame every frame stride must cover its plane (rows * row stride)");
-    }
-    if (out_y) {
-        if (y_row_stride < Wf) return kasf_set_error(2, "draw_poses: the luma row stride must be at least Wf bytes");
-        if (uv_row_stride < 2 * cw) return kasf_set_error(2, "draw_poses: the chroma row stride must be at least 2 * ((Wf + 1) / 2) bytes");
-        if (y_frame_stride < 0 || uv_frame_stride < 0) return kasf_set_error(2, "draw_poses: the frame strides must be >= 0");
-        if (n_frames > 1 && (y_frame_stride / Hf < y_row_stride || uv_frame_stride / ch < uv_row_stride))
-            return kasf_set_error(2, "draw_poses: with more than one frame every frame stride must cover its plane (rows * row stride)");
-    }
-    if (P < 0 || P > (1 << 20)) return kasf_set_error(2, "draw_poses: P must be in [0, 2^20]");
-    if (S < 0 || S > 32) return kasf_set_error(2, "draw_poses: S must be in [0, 32]");
-    if (P > 0 && S > 0) {
-        if (J < 1 || J > 32) return kasf_set_error(2, "draw_poses: J must be in [1, 32]");
-        if (C != 2 && C != 3) return kasf_set_error(2, "draw_poses: C must be 2 (x, y) or 3 (x, y, score)");
-        if (!keypoints || !segments || !colors) return kasf_set_error(2, "null pointer argument");
-    }
-    if (!dot_color) return kasf_set_error(2, "null pointer argument");
-    if (thickness < 1 || thickness > 64) return kasf_set_error(2, "draw_poses: thickness must be in [1, 64]");
-    if (dot_radius < 0 || dot_radius > 32) return kasf_set_error(2, "draw_poses: dot_radius must be in [0, 32]");
-    if (R < 0 || R > 8) return kasf_set_error(2, "draw_poses: R must be in [0, 8]");
-    if (R > 0 && !fills) return kasf_set_error(2, "null pointer argument");
-    if (n_frames == 0) return 0;
-    if (!frames) return kasf_set_error(2, "null pointer argument");
-    KasfDrawLaunch d;
-    d.frames = frames; d.n_frames = n_frames; d.Hf = Hf; d.Wf = Wf; d.row_stride = row_stride; d.frame_stride = frame_stride;
-    d.keypoints = keypoints; d.P = P; d.J = J; d.use_score = (C == 3 && std::isfinite(min_score)) ? 1 : 0;
-    d.kp_frame_stride = kp_frame_stride; d.kp_person_stride = kp_person_stride; d.kp_joint_stride = kp_joint_stride; d.kp_coord_stride = kp_coord_stride;
-    d.valid = valid; d.valid_frame_stride = valid_frame_stride; d.valid_person_stride = valid_person_stride;
-    d.segments = segments; d.colors = colors; d.S = S;
-    for (int c = 0; c < 3; ++c) d.dot_color[c] = dot_color[c];
-    d.thickness = thickness; d.dot_radius = dot_radius; d.min_score = min_score; d.fills = fills; d.R = R;
-    d.out_bgr = out_bgr; d.out_row_stride = out_row_stride; d.out_frame_stride = out_frame_stride;
-    d.out_y = out_y; d.out_uv = out_uv; d.y_row_stride = y_row_stride; d.uv_row_stride = uv_row_stride; d.y_frame_stride = y_frame_stride;
-    d.uv_frame_stride = uv_frame_stride;
-    d.coef = kCoef[matrix][full_range ? 1 : 0]; d.full_range = full_range ? 1 : 0; d.rgb = rgb ? 1 : 0;
-    kasf_launch_draw_poses((hipStream_t)stream, &d);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int kasf_bgr_to_nv12(const void* frames, int32_t n_frames, int32_t Hf, int32_t Wf, int64_t row_stride, int64_t frame_stride, void* out_y, void* out_uv,
-                     int64_t y_row_stride, int64_t uv_row_stride, int64_t y_frame_stride, int64_t uv_frame_stride, int32_t matrix, int32_t full_range, int32_t rgb,
-                     void* stream) {
-    static const uint8_t kNoDot[3] = {0, 0, 0};
-    if (!out_y || !out_uv) return kasf_set_error(2, "null pointer argument");
-    return kasf_draw_poses(frames, n_frames, Hf, Wf, row_stride, frame_stride, nullptr, 0, 0, 0, 0, 0, 0, 0, nullptr, 0, 0, nullptr, nullptr, 0, kNoDot, 1, 0, 0.0f,
-                           nullptr, 0, nullptr, 0, 0, out_y, out_uv, y_row_stride, uv_row_stride, y_frame_stride, uv_frame_stride, matrix, full_range, rgb, stream);
-}
-
-int kasf_pose_panel(const float* poses, int64_t n, const float* view, float* out, void* stream) {
-    if (n < 0 || n > ((int64_t)1 << 40)) return kasf_set_error(2, "pose_panel: n must be in [0, 2^40]");
-    if (!view) return kasf_set_error(2, "null pointer argument");
-    for (int i = 0; i < 8; ++i)
-        if (!std::isfinite(view[i])) return kasf_set_error(2, "pose_panel: every view coefficient must be finite");
-    if (n == 0) return 0;
-    if (!poses || !out) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_pose_panel((hipStream_t)stream, poses, n, view, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ---- detector output -> person boxes (kasf.h, kasf_detect_boxes) ----
-static const char* detect_shape_error(int32_t batch, int64_t n_per_image, int32_t max_candidates) {
-    if (batch < 0 || batch > 65535) return "detect: batch must be in [0, 65535]";
-    if (n_per_image < 1 || n_per_image > ((int64_t)1 << 24)) return "detect: candidates per image must be in [1, 2^24]";
-    if (max_candidates < 1 || max_candidates > KASF_DETECT_MAX_CANDIDATES) return "detect: max_candidates must be in [1, 4096] (KASF_DETECT_MAX_CANDIDATES: sort and NMS run in LDS)";
-    return nullptr;
-}
-int64_t kasf_detect_workspace_bytes(int32_t batch, int64_t n_per_image, int32_t max_candidates) {
-    if (const char* e = detect_shape_error(batch, n_per_image, max_candidates)) return -(int64_t)kasf_set_error(2, e);
-    return kasf_detect_ws_bytes(batch, n_per_image);
-}
-int kasf_detect_boxes(const void* const* src, int32_t n_src, int32_t form, int32_t dtype, int32_t batch, const int32_t* grid, int32_t A, int32_t C,
-                      const float* anchors, int32_t inp_dim, const float* frame_wh, float confidence, float nms, int32_t class_id, int32_t max_candidates,
-                      int32_t max_boxes, float* boxes, int32_t* index, int32_t* count, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (form != KASF_DETECT_PREDICTION && form != KASF_DETECT_HEADS) return kasf_set_error(2, "detect_boxes: form must be KASF_DETECT_PREDICTION or KASF_DETECT_HEADS");
-    if (dtype != KASF_F32 && dtype != KASF_F16 && dtype != KASF_BF16) return kasf_set_error(2, "detect_boxes: dtype must be KASF_DTYPE_F32, _F16 or _BF16");
-    if (n_src < 1 || n_src > KASF_DETECT_MAX_SRC || (form == KASF_DETECT_PREDICTION && n_src != 1))
-        return kasf_set_error(2, "detect_boxes: n_src must be in [1, 4], and 1 in the prediction form");
-    if (!src || !grid) return kasf_set_error(2, "null pointer argument");
-    if (C < 1 || C > 65536) return kasf_set_error(2, "detect_boxes: C must be in [1, 65536]");
-    if (class_id < 0 || class_id >= C) return kasf_set_error(2, "detect_boxes: class_id must be in [0, C)");
-    if (inp_dim < 1) return kasf_set_error(2, "detect_boxes: inp_dim must be >= 1");
-    int64_t N = 0;
-    if (form == KASF_DETECT_HEADS) {
-        if (A < 1 || A > KASF_DETECT_MAX_A) return kasf_set_error(2, "detect_boxes: A must be in [1, 8]");
-        if (!anchors) return kasf_set_error(2, "null pointer argument");
-        for (int k = 0; k < n_src; ++k) {
-            if (grid[k] < 1 || grid[k] > 4096 || inp_dim % grid[k] != 0) return kasf_set_error(2, "detect_boxes: every grid must be in [1, 4096] and divide inp_dim");
-            N += (int64_t)grid[k] * grid[k] * A;
-        }
-    } else {
-        N = grid[0];
-    }
-    if (const char* e = detect_shape_error(batch, N, max_candidates)) return kasf_set_error(2, e);
-    if (max_boxes < 1 || max_boxes > max_candidates) return kasf_set_error(2, "detect_boxes: max_boxes must be in [1, max_candidates]");
-    if (!std::isfinite(confidence) || !std::isfinite(nms)) return kasf_set_error(2, "detect_boxes: confidence and nms must be finite");
-    if (batch == 0) return 0;
-    for (int k = 0; k < n_src; ++k)
-        if (!src[k]) return kasf_set_error(2, "null pointer argument");
-    if (!frame_wh || !boxes || !index || !count || !workspace) return kasf_set_error(2, "null pointer argument");
-    if (((uintptr_t)workspace & 15) != 0) return kasf_set_error(2, "detect_boxes: workspace must be 16-byte aligned");
-    if (workspace_bytes < kasf_detect_ws_bytes(batch, N)) return kasf_set_error(2, "detect_boxes: workspace too small (see kasf_detect_workspace_bytes)");
-    if (const char* e = kasf_launch_detect_boxes((hipStream_t)stream, src, n_src, form, dtype, batch, grid, A, C, anchors, inp_dim, frame_wh, confidence, nms,
-                                                 class_id, max_candidates, max_boxes, boxes, index, count, workspace))
-        return kasf_set_error(3, e);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ---- person boxes -> tracked person boxes (kasf.h, kasf_sort_update) ----
-static const char* sort_shape_error(int32_t streams, int32_t slots, int32_t max_dets) {
-    if (streams < 0 || streams > 65535) return "sort: streams must be in [0, 65535]";
-    if (slots < 1 || slots > KASF_SORT_MAX) return "sort: slots must be in [1, 64] (one lane of a wavefront per track)";
-    if (max_dets < 1 || max_dets > KASF_SORT_MAX) return "sort: max_dets must be in [1, 64] (one lane of a wavefront per detection)";
-    return nullptr;
-}
-int64_t kasf_sort_state_bytes(int32_t streams, int32_t slots, int32_t max_dets) {
-    if (const char* e = sort_shape_error(streams, slots, max_dets)) return -(int64_t)kasf_set_error(2, e);
-    return (int64_t)streams * kasf_sort_stream_bytes(slots, max_dets);
-}
-int kasf_sort_update(void* state, int32_t streams, int32_t slots, int32_t max_dets, const float* dets, int32_t det_rows, int64_t det_stream_stride, int64_t det_row_stride,
-                     const int32_t* det_count, int32_t max_age, int32_t min_hits, float iou_threshold, int32_t num_person, int32_t hold_last, float* boxes,
-                     int32_t* ids, int32_t* slot, int32_t* born, int32_t* count, int32_t* dropped, float* persons, int32_t* person_count, void* stream) {
-    if (const char* e = sort_shape_error(streams, slots, max_dets)) return kasf_set_error(2, e);
-    if (det_rows < 0 || det_rows > max_dets) return kasf_set_error(2, "sort_update: det_rows must be in [0, max_dets]");
-    if (det_row_stride < 4) return kasf_set_error(2, "sort_update: the detection row stride must be at least 4 elements");
-    if (det_stream_stride < 0) return kasf_set_error(2, "sort_update: the detection stream stride must be >= 0");
-    if (max_age < 0 || min_hits < 0) return kasf_set_error(2, "sort_update: max_age and min_hits must be >= 0");
-    if (!std::isfinite(iou_threshold)) return kasf_set_error(2, "sort_update: iou_threshold must be finite");
-    if (num_person < 1 || num_person > 65535) return kasf_set_error(2, "sort_update: num_person must be in [1, 65535]");
-    if (streams == 0) return 0;
-    if (!state || (!dets && det_rows > 0) || !boxes || !ids || !slot || !born || !count || !dropped || !persons || !person_count) return kasf_set_error(2, "null pointer argument");
-    if (((uintptr_t)state & 7) != 0) return kasf_set_error(2, "sort_update: state must be 8-byte aligned");
-    kasf_launch_sort_update((hipStream_t)stream, state, streams, slots, max_dets, dets, det_rows, det_stream_stride, det_row_stride, det_count, max_age, min_hits,
-                            iou_threshold, num_person, hold_last ? 1 : 0, boxes, ids, slot, born, count, dropped, persons, person_count);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-#define OP_DT_CHECK(dt) \
-    if ((dt) != KASF_F32 && (dt) != KASF_BF16) return kasf_set_error(3, "bad dtype")
-
-int kasf_op_linear(int32_t dtype, const void* a, const void* w, const float* bias, void* y, int64_t M, int32_t N, const float* ln_g, const float* ln_b,
-                   void* xn_out, int32_t act, void* stream) {
-    OP_DT_CHECK(dtype);
-    if (N % 128 != 0) return kasf_set_error(2, "N must be a multiple of 128");
-    kasf_launch_linear(dtype, (hipStream_t)stream, a, 128, w, 128, bias, y, N, M, N, ln_g, ln_b, xn_out, act);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_op_mlp_fwd(int32_t dtype, const void* x, const float* ln_g, const float* ln_b, const void* w1, const float* b1, const void* w2, const float* b2,
-                    const float* ls2, void* out, int64_t M, void* xn_out, void* stream) {
-    OP_DT_CHECK(dtype);
-    kasf_launch_mlp_fwd(dtype, (hipStream_t)stream, x, ln_g, ln_b, w1, b1, w2, b2, ls2, out, M, xn_out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_op_mlp_bwd(int32_t dtype, const void* x, const void* g, const float* ln_g, const float* ln_b, const void* w1, const float* b1,
-                    const void* w2t_scaled, const void* w1t, void* hbuf, void* dzbuf, void* g_in, float* dgamma, float* dbeta, int64_t M, void* stream) {
-    OP_DT_CHECK(dtype);
-    kasf_launch_mlp_bwd(dtype, (hipStream_t)stream, x, g, ln_g, ln_b, w1, b1, w2t_scaled, w1t, hbuf, dzbuf, nullptr, g_in, dgamma, dbeta, M);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_op_mlp_bwd_fused(const void* x, const void* xn, const void* g, const float* ln_g, const void* w1, const float* b1, const void* w2t_scaled,
-                          const void* w1t, void* dapart, float* partial, float* dw1, float* dw2_unscaled, float* db1, float* gsum, void* g_in,
-                          float* dgamma, float* dbeta, int64_t M, void* stream) {
-    if (!x || !xn || !g || !dapart || !partial || !dw1 || !dw2_unscaled || !db1 || !gsum || !g_in) return kasf_set_error(2, "null pointer argument");
-    kasf_launch_mlp_bwd_q((hipStream_t)stream, x, xn, g, ln_g, w1, b1, w2t_scaled, w1t, dapart, partial, dw1, dw2_unscaled, db1, gsum, g_in, dgamma,
-                          dbeta, M);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_op_wgrad(int32_t dtype, const void* g, int32_t N, const void* x, int32_t K, const float* ln_g, const float* ln_b, float* dw, float* dbias,
-                  int64_t M, float* partial, int64_t partial_floats, void* stream) {
-    OP_DT_CHECK(dtype);
-    if (N % 128 != 0 || K % 128 != 0) return kasf_set_error(2, "N and K must be multiples of 128");
-    if (ln_g != nullptr && K != 128) return kasf_set_error(2, "LayerNorm-fused wgrad needs K == 128");
-    kasf_launch_wgrad(dtype, (hipStream_t)stream, g, N, N, x, K, K, ln_g, ln_b, dw, K, dbias, M, partial, partial_floats);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_op_dgrad_lnbwd(int32_t dtype, const void* dy, int32_t Kd, const void* wt, const void* dxn_add, const void* x, const float* gamma,
-                        const void* resid, void* out, int32_t accumulate, float* dgamma, float* dbeta, int64_t M, void* xn_out, const float* beta,
-                        void* stream) {
-    OP_DT_CHECK(dtype);
-    if (Kd % 128 != 0) return kasf_set_error(2, "Kd must be a multiple of 128");
-    if (xn_out != nullptr && beta == nullptr) return kasf_set_error(2, "xn_out needs beta");
-    kasf_launch_dgrad_lnbwd(dtype, (hipStream_t)stream, dy, Kd, wt, dxn_add, x, gamma, resid, out, accumulate, dgamma, dbeta, M, xn_out, beta);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_op_attention_fwd(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int32_t batch, int32_t n_frames,
-                          int32_t mode, void* stream) {
-    OP_DT_CHECK(dtype);
-    g_err.clear();
-    kasf_launch_attn_fwd(dtype, (hipStream_t)stream, q, ldq, k, v, ldkv, o, batch, n_frames, mode);
-    HIPCHK(hipGetLastError());
-    return g_err.empty() ? 0 : 3;
-}
-int kasf_op_attention_bwd(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* d_o, void* dq, int64_t lddq,
-                          void* dk, void* dv, int64_t lddkv, int32_t batch, int32_t n_frames, int32_t mode, void* stream) {
-    OP_DT_CHECK(dtype);
-    g_err.clear();
-    kasf_launch_attn_bwd(dtype, (hipStream_t)stream, q, ldq, k, v, ldkv, d_o, dq, lddq, dk, dv, lddkv, batch, n_frames, mode);
-    HIPCHK(hipGetLastError());
-    return g_err.empty() ? 0 : 3;
-}
-int kasf_op_attention_fwd_heads(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int32_t batch, int32_t n_frames,
-                                int32_t mode, int32_t num_heads, void* stream) {
-    OP_DT_CHECK(dtype);
-    g_err.clear();
-    kasf_launch_attn_fwd(dtype, (hipStream_t)stream, q, ldq, k, v, ldkv, o, batch, n_frames, mode, num_heads);
-    HIPCHK(hipGetLastError());
-    return g_err.empty() ? 0 : 3;
-}
-int kasf_op_attention_bwd_heads(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* d_o, void* dq, int64_t lddq,
-                                void* dk, void* dv, int64_t lddkv, int32_t batch, int32_t n_frames, int32_t mode, int32_t num_heads, void* stream) {
-    OP_DT_CHECK(dtype);
-    g_err.clear();
-    kasf_launch_attn_bwd(dtype, (hipStream_t)stream, q, ldq, k, v, ldkv, d_o, dq, lddq, dk, dv, lddkv, batch, n_frames, mode, num_heads);
-    HIPCHK(hipGetLastError());
-    return g_err.empty() ? 0 : 3;
-}
-int kasf_op_attention_bwd_fused_do(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* g_mid, const void* wproj_t_scaled, void* dq,
-                                   int64_t lddq, void* dk, void* dv, int64_t lddkv, int32_t batch, int32_t n_frames, int32_t mode, int32_t form, const void* o_saved,
-                                   const float* lse, void* stream) {
-    g_err.clear();
-    if (form < 0 || form > 1) return kasf_set_error(2, "form: 0 (persistent) or 1 (one group per workgroup)");
-    if (batch < 1 || n_frames < 1 || (int64_t)batch * n_frames * 17 * 384 >= ((int64_t)1 << 31)) return kasf_set_error(2, "batch * n_frames * 17 * 384 must stay below 2^31");
-    if (!kasf_launch_attn_bwd_fused_do((hipStream_t)stream, q, ldq, k, v, ldkv, g_mid, wproj_t_scaled, dq, lddq, dk, dv, lddkv, batch, n_frames, mode, form, o_saved, lse))
-        return kasf_set_error(2, "fused-d_o attention backward: groups of at most 96 positions (form 1: at most 32); bf16, 8 heads");
-    HIPCHK(hipGetLastError());
-    return g_err.empty() ? 0 : 3;
-}
-// ---- the GCN mixer on its own (kasf.h, kasf_op_gcn_fwd / kasf_op_gcn_bwd): the launch sequence and `count` of block_forward / block_backward ----
-static_assert(KASF_GCN_STAT_WORDS == KASF_STAT_SLOTS * KASF_STAT_LD * KASF_STAT_WORDS, "kasf.h and kernels.h disagree on the size of a statistics buffer");
-static int gcn_shape_check(int32_t batch, int32_t n_frames, int32_t mode) {
-    if (mode != 0 && mode != 1) return kasf_set_error(2, "gcn: mode must be 0 (spatial) or 1 (temporal)");
-    if (n_frames < 4 || n_frames > KASF_MAX_NODES) return kasf_set_error(2, "gcn: n_frames must be in [4, 256]");
-    if (batch < 1 || (int64_t)batch * n_frames * 17 * 16 >= ((int64_t)1 << 31)) return kasf_set_error(2, "gcn: batch >= 1 and batch * n_frames * 17 * 16 must stay below 2^31");
-    return 0;
-}
-int kasf_op_gcn_fwd(int32_t dtype, const void* x_in, const void* xn, const void* uv, const float* bn_w, const float* bn_b, float* run_mean, float* run_var,
-                    const float* ls1, void* y, uint32_t* mask, void* stats, float* coef, void* out, int32_t batch, int32_t n_frames, int32_t mode,
-                    int32_t neighbour_num, int32_t training, float momentum, void* stream) {
-    OP_DT_CHECK(dtype);
-    if (gcn_shape_check(batch, n_frames, mode) != 0) return 2;
-    if (neighbour_num < 1 || neighbour_num > 4) return kasf_set_error(2, "gcn: neighbour_num must be in [1, 4]");
-    if (!x_in || !xn || !uv || !bn_w || !bn_b || !run_mean || !run_var || !ls1 || !y || !stats || !coef || !out || (mode == 1 && !mask))
-        return kasf_set_error(2, "null pointer argument");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemsetAsync(stats, 0, (size_t)KASF_GCN_STAT_WORDS * sizeof(int64_t), s));
-    kasf_launch_gcn_agg_fwd(dtype, s, uv, xn, y, mode == 1 ? mask : nullptr, (double*)stats, batch, n_frames, mode, neighbour_num);
-    const double count = mode == 0 ? (double)batch * n_frames * 128 : (double)batch * 17 * 128;
-    kasf_launch_gcn_apply(dtype, s, x_in, xn, y, (const double*)stats, bn_w, bn_b, run_mean, run_var, coef, ls1, out, batch, n_frames, mode, count,
-                          training ? 1 : 0, momentum);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_op_gcn_bwd(int32_t dtype, const void* g, const void* xn, const void* y, const float* coef, const uint32_t* mask, const float* ls1, void* r, void* duv,
-                    float* dls1, float* d_bn_w, float* d_bn_b, void* bstats, int32_t batch, int32_t n_frames, int32_t mode, int32_t training, void* stream) {
-    OP_DT_CHECK(dtype);
-    if (gcn_shape_check(batch, n_frames, mode) != 0) return 2;
-    if (!g || !xn || !y || !coef || !ls1 || !r || !duv || !dls1 || !d_bn_w || !d_bn_b || !bstats || (mode == 1 && !mask))
-        return kasf_set_error(2, "null pointer argument");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemsetAsync(bstats, 0, (size_t)KASF_GCN_STAT_WORDS * sizeof(int64_t), s));
-    kasf_launch_gcn_bwd1(dtype, s, g, xn, y, coef, ls1, r, dls1, (double*)bstats, batch, n_frames, mode);
-    const double count = mode == 0 ? (double)batch * n_frames * 128 : (double)batch * 17 * 128;
-    kasf_launch_gcn_bwd2(dtype, s, r, y, coef, mode == 1 ? mask : nullptr, duv, batch, n_frames, mode, (const double*)bstats, d_bn_w, d_bn_b, count,
-                         training ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-// ---- the prologue, gate, head and embedding kernels on their own (kasf.h, kasf_op_prologue_fwd ... kasf_op_add): the engine's own launchers.  scratch != NULL: a local
-// KasfColSink on it and the fixed-order finish on the same stream, as a backward stage does; NULL: the fp32 atomics ----
-#define MISC_TOKENS_CHECK(M, what) \
-    if ((M) < 1 || (int64_t)(M) * 384 >= ((int64_t)1 << 31)) return kasf_set_error(2, what ": 1 <= tokens and tokens * 384 < 2^31")
-#define MISC_FRAMES_CHECK(f) \
-    if ((f) < 1 || (int64_t)(f) * 17 * 384 >= ((int64_t)1 << 31)) return kasf_set_error(2, "frames: 1 <= frames and frames * 17 * 384 < 2^31")
-namespace {
-struct MiscSink {
-    KasfColSink sink;
-    KasfColSink* p;
-    MiscSink(float* scratch, int64_t floats) : p(scratch != nullptr ? &sink : nullptr) { sink.scratch = scratch; sink.cap = floats; }
-    // the finish; error 6 (set by kasf_col_flush) when a launch found the scratch too small and fell back to atomics
-    int finish(hipStream_t s) {
-        if (p == nullptr) return 0;
-        const bool overflow = sink.overflow;
-        kasf_col_flush(s, &p, 1);
-        return overflow ? 6 : 0;
-    }
-};
-int misc_scratch_check(const float* scratch, int64_t floats) {
-    if (scratch != nullptr && floats < 1) return kasf_set_error(2, "scratch_floats must be >= 1 with a scratch pointer");
-    if (scratch != nullptr && ((uintptr_t)scratch & 15) != 0) return kasf_set_error(2, "scratch must be 16-byte aligned");
-    return 0;
-}
-}  // namespace
+// ---- the prologue kernels on their own (kasf.h, kasf_op_prologue_fwd / kasf_op_refusion_bwd / kasf_op_input_grad): the ones of api_ops.hip's kasf_op_* that read a model ----
 int64_t kasf_op_misc_scratch_floats(int32_t op, int64_t n) {
     if (n < 1) { kasf_set_error(2, "misc_scratch_floats: n must be >= 1"); return -2; }
     const int64_t r = kasf_misc_scratch_floats(op, n, refusion_grad_len());
@@ -1822,123 +981,33 @@ int64_t kasf_op_misc_scratch_floats(int32_t op, int64_t n) {
 int kasf_op_prologue_fwd(const kasf_model* m, const float* params, const float* x, void* xj, void* xb, void* xl, float* bone3, float* limb3, int64_t frames,
                          void* stream) {
     if (check_model(m)) return 2;
-    if (!params || !x || !xj || !xb || !xl || !bone3 || !limb3) return kasf_set_error(2, "null pointer argument");
-    MISC_FRAMES_CHECK(frames);
+    if (!params || !x || !xj || !xb || !xl || !bone3 || !limb3) return refuse_null();
+    if (refuse_misc_frames(frames)) return 2;
     if (m->d_pro == nullptr) return kasf_set_error(4, "layout-only model cannot run");
     kasf_launch_prologue_fwd(m->cfg.dtype, (hipStream_t)stream, x, params, m->d_pro, xj, xb, xl, bone3, limb3, frames);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_op_embed_bwd(int32_t dtype, const void* g, const float* in3, const float* w, float* dw, float* db, float* dpos, float* din3, int64_t frames,
-                      float* scratch, int64_t scratch_floats, void* stream) {
-    OP_DT_CHECK(dtype);
-    if (!g || !in3 || !w || !dw || !db || !dpos) return kasf_set_error(2, "null pointer argument");
-    MISC_FRAMES_CHECK(frames);
-    if (misc_scratch_check(scratch, scratch_floats)) return 2;
-    MiscSink ms(scratch, scratch_floats);
-    kasf_launch_embed_bwd(dtype, (hipStream_t)stream, g, in3, w, dw, db, dpos, din3, frames, ms.p);
-    const int rc = ms.finish((hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return rc;
+    return api_done();
 }
 int kasf_op_refusion_bwd(const kasf_model* m, const float* params, const float* x, const float* dlimb3, float* grads, int64_t frames, float* scratch,
                          int64_t scratch_floats, void* stream) {
     if (check_model(m)) return 2;
-    if (!params || !x || !dlimb3 || !grads) return kasf_set_error(2, "null pointer argument");
-    MISC_FRAMES_CHECK(frames);
+    if (!params || !x || !dlimb3 || !grads) return refuse_null();
+    if (refuse_misc_frames(frames)) return 2;
     if (misc_scratch_check(scratch, scratch_floats)) return 2;
     if (m->d_pro == nullptr) return kasf_set_error(4, "layout-only model cannot run");
     int64_t rf_base, rf_end;
     refusion_grad_range(m->pro, rf_base, rf_end);
     MiscSink ms(scratch, scratch_floats);
     kasf_launch_refusion_bwd((hipStream_t)stream, x, dlimb3, params, grads, m->d_pro, frames, ms.p, rf_base, (int)(rf_end - rf_base));
-    const int rc = ms.finish((hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return rc;
+    return api_done(ms.finish((hipStream_t)stream));
 }
 int kasf_op_input_grad(const kasf_model* m, const float* params, const float* x, const float* dx_joint3, const float* dbone3, const float* dlimb3, float* dx,
                        int64_t frames, void* stream) {
     if (check_model(m)) return 2;
-    if (!params || !x || !dx) return kasf_set_error(2, "null pointer argument");
-    MISC_FRAMES_CHECK(frames);
+    if (!params || !x || !dx) return refuse_null();
+    if (refuse_misc_frames(frames)) return 2;
     if (m->d_pro == nullptr) return kasf_set_error(4, "layout-only model cannot run");
     kasf_launch_input_grad((hipStream_t)stream, x, params, m->d_pro, dx_joint3, dbone3, dlimb3, dx, frames);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_op_gate_fwd(int32_t dtype, const void* xa, const void* xg, const void* xb, const float* w, const float* bias, void* out, float* alpha, int64_t M,
-                     int32_t adaptive, void* stream) {
-    OP_DT_CHECK(dtype);
-    if (!xa || !xg || !xb || !w || !bias || !out) return kasf_set_error(2, "null pointer argument");
-    MISC_TOKENS_CHECK(M, "gate_fwd");
-    kasf_launch_gate_fwd(dtype, (hipStream_t)stream, xa, xg, xb, w, bias, out, alpha, M, adaptive ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_op_gate_bwd(int32_t dtype, const void* g, const void* g1, const void* g2, const void* xa, const void* xg, const void* xb, const float* w,
-                     const float* alpha, void* ga, void* gg, void* gb, float* dw, float* db, int64_t M, int32_t adaptive, float* scratch,
-                     int64_t scratch_floats, void* stream) {
-    OP_DT_CHECK(dtype);
-    if (!g || !xa || !xg || !xb || !w || !alpha || !ga || !gg || !gb || (adaptive && (!dw || !db))) return kasf_set_error(2, "null pointer argument");
-    if (((uintptr_t)alpha & 15) != 0) return kasf_set_error(2, "gate_bwd: alpha must be 16-byte aligned");
-    MISC_TOKENS_CHECK(M, "gate_bwd");
-    if (misc_scratch_check(scratch, scratch_floats)) return 2;
-    MiscSink ms(scratch, scratch_floats);
-    kasf_launch_gate_bwd(dtype, (hipStream_t)stream, g, g1, g2, xa, xg, xb, w, alpha, ga, gg, gb, dw, db, M, adaptive ? 1 : 0, ms.p);
-    const int rc = ms.finish((hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return rc;
-}
-int kasf_op_head_fwd(int32_t dtype, const void* rep, const float* w, const float* bias, float* out, int64_t M, void* stream) {
-    OP_DT_CHECK(dtype);
-    if (!rep || !w || !bias || !out) return kasf_set_error(2, "null pointer argument");
-    MISC_TOKENS_CHECK(M, "head_fwd");
-    kasf_launch_head_fwd(dtype, (hipStream_t)stream, rep, w, bias, out, M);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_op_head_bwd(int32_t dtype, const float* dy, const void* rep, const float* w, void* dpre, float* dw, float* db, int64_t M, float* scratch,
-                     int64_t scratch_floats, void* stream) {
-    OP_DT_CHECK(dtype);
-    if (!dy || !rep || !w || !dpre || !dw || !db) return kasf_set_error(2, "null pointer argument");
-    MISC_TOKENS_CHECK(M, "head_bwd");
-    if (misc_scratch_check(scratch, scratch_floats)) return 2;
-    MiscSink ms(scratch, scratch_floats);
-    kasf_launch_head_bwd(dtype, (hipStream_t)stream, dy, rep, w, dpre, dw, db, M, ms.p);
-    const int rc = ms.finish((hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return rc;
-}
-int kasf_op_rep_bwd(int32_t dtype, const float* drep, const void* rep, void* dpre, int64_t M, void* stream) {
-    OP_DT_CHECK(dtype);
-    if (!drep || !rep || !dpre) return kasf_set_error(2, "null pointer argument");
-    MISC_TOKENS_CHECK(M, "rep_bwd");
-    kasf_launch_rep_bwd(dtype, (hipStream_t)stream, drep, rep, dpre, M);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_op_finalize_ls(float* dw, const float* w, const float* bias, const float* ls, float* db, float* dls, int32_t N, int32_t K, void* stream) {
-    if (!dw || !w || !bias || !ls || !db || !dls) return kasf_set_error(2, "null pointer argument");
-    if (N != 128 || (K != 128 && K != 512)) return kasf_set_error(2, "finalize_ls: (N, K) must be (128, 128) or (128, 512), the two layer-scaled Linear layers of a block");
-    kasf_launch_finalize_ls((hipStream_t)stream, dw, w, bias, ls, db, dls, N, K);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_op_add(int32_t dtype, void* dst, const void* a, const void* b, const void* c, int64_t n, void* stream) {
-    OP_DT_CHECK(dtype);
-    if (!dst || !a || (!b && c)) return kasf_set_error(2, "null pointer argument (c needs b)");
-    if (n < 8 || n % 8 != 0 || n >= ((int64_t)1 << 40)) return kasf_set_error(2, "add: n must be a multiple of 8 in [8, 2^40)");
-    if (b == nullptr) kasf_launch_add_inplace(dtype, (hipStream_t)stream, dst, a, n);
-    else kasf_launch_add3(dtype, (hipStream_t)stream, dst, a, b, c, n);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int kasf_op_cast(int32_t dtype, const void* src, void* dst, int64_t n, int32_t to_f32, void* stream) {
-    OP_DT_CHECK(dtype);
-    if (to_f32) kasf_launch_cast_to_f32(dtype, (hipStream_t)stream, src, (float*)dst, n);
-    else kasf_launch_cast_from_f32(dtype, (hipStream_t)stream, (const float*)src, dst, n);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return api_done();
 }
 
 }  // extern "C"

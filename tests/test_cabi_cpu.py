@@ -168,7 +168,7 @@ def test_unsupported_configurations_raise_like_the_reference():
 
 
 def test_device_free_entry_points_under_address_and_ub_sanitizers(tmp_path):
-    """SURVEY section 5.2 (sanitizers; GPU ASan is not available on the pool, so: the host side).  `make asan` builds engine.hip's host code with
+    """SURVEY section 5.2 (sanitizers; GPU ASan is not available on the pool, so: the host side).  `make asan` builds the host code of engine.hip, api_video.hip and api_ops.hip with
     -fsanitize=address,undefined; a C driver built with the same runtime creates layout-only handles for the shipped and for corner configurations and walks
     every query that needs no device -- names with exact-fit and too-short buffers, out-of-range indices, every stage and workspace entry in every flag
     combination -- then destroys them.  Any heap / stack / global overflow, use after free, signed overflow or misaligned access in that code aborts the driver."""
