@@ -911,6 +911,9 @@ int kasf_ws_entry(const kasf_model* m, int32_t batch, int32_t flags, int32_t idx
 /* y = act(LN?(a) W^T + bias): a [M,128], w [N,128] (dtype), N % 128 == 0; ln_g == NULL -> no LayerNorm; act 0 none, 1 tanh */
 int kasf_op_linear(int32_t dtype, const void* a, const void* w, const float* bias, void* y, int64_t M, int32_t N, const float* ln_g, const float* ln_b,
                    void* xn_out, int32_t act, void* stream);
+/* attention proj + layer scale + residual: out = resid + ls * (a W^T + bias): a, resid, out [M,128] and w [128,128] of dtype; bias, ls [128] fp32.  M <= 0: returns 0,
+ * nothing is launched (as every entry of this family) */
+int kasf_op_linear_res(int32_t dtype, const void* a, const void* w, const float* bias, const float* ls, const void* resid, void* out, int64_t M, void* stream);
 /* modules/mlp.py inside a FormerModule: out = x + ls2 * (GELU(LN(x) W1^T + b1) W2^T + b2) */
 /* xn_out (optional; bf16 only): also receives LN(x), which kasf_op_mlp_bwd_fused streams instead of recomputing (what training mode does).
  * ABI 7: with dtype = bf16, w2 [128,512] is IEEE FP16 (torch.float16), not bf16: the forward evaluates GELU in packed fp16 and keeps the hidden
@@ -925,9 +928,12 @@ int kasf_op_mlp_bwd(int32_t dtype, const void* x, const void* g, const float* ln
 /* bf16 only: fused MLP backward (hidden-quarter ownership, weights in registers): data gradient AND both weight gradients.
  * g_in = g + LNbwd(dA); dw1 [512,128] += dZ^T LN(x); db1 [512] += colsum(dZ); dw2_unscaled [128,512] += g^T H;
  * gsum [128] += colsum(g); dgamma/dbeta += LayerNorm parameter gradients.  dapart: 4*M*128 elements of scratch (bf16: the four hidden quarters' dA partials;
- * with KASF_MLP_BWD_DZ=1 in the environment, dZ [M,512] in the same bytes);
- * partial: >= 2*64*65536 + 2048 floats of scratch (the tail holds the inter-workgroup hand-off flags; word 2*64*65536 + 1024 is set to 1 if a
- * bounded wait ran out). */
+ * with KASF_MLP_BWD_DZ=1 in the environment, dZ [M,512] in the same bytes: the second launch then forms dA = dZ W1 itself).
+ * partial: scratch of at least ranges * 65536 floats, 16-byte aligned, where tiles = ceil(M / 32), per = ceil(tiles / min(tiles, 64)) and
+ * ranges = ceil(tiles / per) <= 64 (64 * 65536 floats cover every M).  It is read as bf16: token range r leaves its share of dW1 as one [512][128] bf16 tile
+ * at bf16 element r * 65536 and its share of dW2 as one [128][512] bf16 tile at bf16 element (ranges + r) * 65536; the second launch adds the tiles in a fixed
+ * order.  Both forms (dA partials and dZ) use exactly these 2 * ranges tiles: nothing behind them is read or written, and no word of it is a flag.
+ * M <= 0: nothing is launched. */
 int kasf_op_mlp_bwd_fused(const void* x, const void* xn /* LN(x) from kasf_op_mlp_fwd */, const void* g, const float* ln_g, const void* w1, const float* b1, const void* w2t_scaled,
                           const void* w1t, void* dapart, float* partial, float* dw1, float* dw2_unscaled, float* db1, float* gsum, void* g_in,
                           float* dgamma, float* dbeta, int64_t M, void* stream);
@@ -941,6 +947,22 @@ int kasf_op_wgrad(int32_t dtype, const void* g, int32_t N, const void* x, int32_
 int kasf_op_dgrad_lnbwd(int32_t dtype, const void* dy, int32_t Kd, const void* wt, const void* dxn_add, const void* x, const float* gamma,
                         const void* resid, void* out, int32_t accumulate, float* dgamma, float* dbeta, int64_t M, void* xn_out, const float* beta,
                         void* stream);
+/* bf16 only: kasf_op_dgrad_lnbwd with the weight gradient of the same linear in the same launch, finished as a backward stage finishes it: after the call
+ * out, dgamma, dbeta (as kasf_op_dgrad_lnbwd, no xn_out) and dw [Kd,128] += dY^T LN(x) are complete.  Five forms, anything else is error 2:
+ *   Kd 384 or 128 with resid, no accumulate                        (the qkv / q linears)
+ *   Kd 256, no resid, accumulate                                     (the bone kv linear)
+ *   Kd 256 with resid, dxn_add and dbias [256] += colsum(dY)         (the GCN's U | V linear)
+ *   Kd 128 with resid and proj_o [M,128]                             (the bone q linear carrying the block's output-projection gradient): with G = resid^T proj_o
+ *       and c = colsum(resid):  dproj_w [128,128] += proj_ls[n] G[n][:],  dproj_b [128] += proj_ls . c,  dproj_ls [128] += <proj_w[n], G[n]> + proj_b . c;
+ *       proj_o, proj_w, proj_b, proj_ls, dproj_w, dproj_b, dproj_ls and proj_part go together.
+ * Scratch, all 16-byte aligned: wpart, wpart_bytes >= 256 * Kd * 128 * 2 (bf16 partial tiles of dw, one per workgroup); proj_part, proj_part_bytes >= 256 * 128 * 128 * 2
+ * + 256 * 128 * 4 (the proj tiles and behind them one fp32 row of colsum(resid) per workgroup); scratch, scratch_floats >= rows * ld rounded up to 64, rows =
+ * the workgroups that own a tile (tiles = ceil(M / 32), per = ceil(tiles / min(tiles, 256)), rows = ceil(tiles / per)), ld = 512 with dbias and 256 without: one row
+ * of dgamma | dbeta (| dbias) per workgroup, summed in a fixed order.  M <= 0: returns 0 after the checks, nothing is launched. */
+int kasf_op_dgrad_wg(const void* dy, int32_t Kd, const void* wt, const void* dxn_add, const void* x, const float* gamma, const float* beta, const void* resid,
+                     void* out, int32_t accumulate, float* dgamma, float* dbeta, float* dw, float* dbias, const void* proj_o, const float* proj_w,
+                     const float* proj_b, const float* proj_ls, float* dproj_w, float* dproj_b, float* dproj_ls, int64_t M, void* wpart, int64_t wpart_bytes,
+                     void* proj_part, int64_t proj_part_bytes, float* scratch, int64_t scratch_floats, void* stream);
 /* attention core (selfattention.py:18-41): q [*,ldq], k/v [*,ldkv] token-major; mode 0 spatial, 1 temporal */
 int kasf_op_attention_fwd(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int32_t batch, int32_t n_frames,
                           int32_t mode, void* stream);

@@ -105,6 +105,12 @@ int kasf_op_linear(int32_t dtype, const void* a, const void* w, const float* bia
     kasf_launch_linear(dtype, (hipStream_t)stream, a, 128, w, 128, bias, y, N, M, N, ln_g, ln_b, xn_out, act);
     return api_done();
 }
+int kasf_op_linear_res(int32_t dtype, const void* a, const void* w, const float* bias, const float* ls, const void* resid, void* out, int64_t M, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (!a || !w || !bias || !ls || !resid || !out) return refuse_null();
+    kasf_launch_linear_res(dtype, (hipStream_t)stream, a, w, bias, ls, resid, out, M);
+    return api_done();
+}
 int kasf_op_mlp_fwd(int32_t dtype, const void* x, const float* ln_g, const float* ln_b, const void* w1, const float* b1, const void* w2, const float* b2,
                     const float* ls2, void* out, int64_t M, void* xn_out, void* stream) {
     OP_DT_CHECK(dtype);
@@ -141,6 +147,39 @@ int kasf_op_dgrad_lnbwd(int32_t dtype, const void* dy, int32_t Kd, const void* w
     if (xn_out != nullptr && beta == nullptr) return kasf_set_error(2, "xn_out needs beta");
     kasf_launch_dgrad_lnbwd(dtype, (hipStream_t)stream, dy, Kd, wt, dxn_add, x, gamma, resid, out, accumulate, dgamma, dbeta, M, xn_out, beta);
     return api_done();
+}
+// the fused data + weight gradient launch with a column sink of its own and the finish launches of a backward stage (engine.hip: kasf_launch_bf16_reduce, or
+// kasf_launch_proj_finish for the PROJ form, then the sink's flush on the same stream)
+int kasf_op_dgrad_wg(const void* dy, int32_t Kd, const void* wt, const void* dxn_add, const void* x, const float* gamma, const float* beta, const void* resid,
+                     void* out, int32_t accumulate, float* dgamma, float* dbeta, float* dw, float* dbias, const void* proj_o, const float* proj_w,
+                     const float* proj_b, const float* proj_ls, float* dproj_w, float* dproj_b, float* dproj_ls, int64_t M, void* wpart, int64_t wpart_bytes,
+                     void* proj_part, int64_t proj_part_bytes, float* scratch, int64_t scratch_floats, void* stream) {
+    if (!dy || !wt || !x || !gamma || !beta || !out || !dgamma || !dbeta || !dw || !wpart || !scratch) return refuse_null();
+    const int nproj = (proj_o != nullptr) + (proj_w != nullptr) + (proj_b != nullptr) + (proj_ls != nullptr) + (dproj_w != nullptr) + (dproj_b != nullptr) +
+                      (dproj_ls != nullptr) + (proj_part != nullptr);
+    if (nproj != 0 && nproj != 8) return refuse("dgrad_wg", "proj_o, proj_w, proj_b, proj_ls, dproj_w, dproj_b, dproj_ls and proj_part go together");
+    const bool proj = nproj == 8;
+    if (Kd < 128 || Kd > 384 || !kasf_dgrad_wg_supported(Kd, resid != nullptr, accumulate != 0, dxn_add != nullptr, dbias != nullptr, proj, 1, INT64_MAX))
+        return refuse("dgrad_wg", "not one of the five fused forms (Kd 384 or 128 with resid; Kd 256 accumulating without resid; Kd 256 with resid, dxn_add and dbias; "
+                                  "Kd 128 with resid and proj_o)");
+    if (wpart_bytes < (int64_t)256 * Kd * 128 * 2) return refuse("dgrad_wg", "wpart_bytes must be at least 256 * Kd * 128 * 2");
+    const int64_t proj_tile_bytes = (int64_t)256 * 128 * 128 * 2;
+    if (proj && proj_part_bytes < proj_tile_bytes + 256 * 128 * 4) return refuse("dgrad_wg", "proj_part_bytes must be at least 256 * 128 * 128 * 2 + 256 * 128 * 4");
+    if (misaligned16(wpart) || (proj && misaligned16(proj_part))) return refuse("dgrad_wg", "wpart and proj_part must be 16-byte aligned");
+    if (int rc = misc_scratch_check(scratch, scratch_floats)) return rc;
+    if (M <= 0) return 0;
+    const int64_t need = ((int64_t)kasf_dgrad_r_rows(M) * (dbias != nullptr ? 512 : 256) + 63) / 64 * 64;
+    if (scratch_floats < need) return refuse("dgrad_wg", "scratch_floats is below one row of dgamma | dbeta (| dbias) per workgroup that owns a tile");
+    hipStream_t s = (hipStream_t)stream;
+    MiscSink ms(scratch, scratch_floats);
+    float* pbrow = proj ? (float*)((char*)proj_part + proj_tile_bytes) : nullptr;
+    const int np = kasf_launch_dgrad_wg(s, dy, Kd, wt, x, gamma, beta, resid, out, accumulate, dgamma, dbeta, M, ms.p, wpart, wpart_bytes, dxn_add, dbias, proj_o,
+                                        proj_part, pbrow);
+    if (np <= 0) return kasf_set_error(3, "dgrad_wg: the launcher declined a form that kasf_dgrad_wg_supported accepts");
+    const KasfBf16Reduce red{wpart, dw, np, Kd * 128};
+    if (proj) kasf_launch_proj_finish(s, proj_part, pbrow, np, dproj_w, proj_w, proj_b, proj_ls, dproj_b, dproj_ls, 1, &red);
+    else kasf_launch_bf16_reduce(s, 1, &red);
+    return api_done(ms.finish(s));
 }
 int kasf_op_attention_fwd(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int32_t batch, int32_t n_frames,
                           int32_t mode, void* stream) {

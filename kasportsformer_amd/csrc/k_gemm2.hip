@@ -521,6 +521,10 @@ bool kasf_launch_dgrad_r(hipStream_t s, const void* dY, int Kd, const void* Wt, 
 // (KasfBf16Reduce).  Returns 0 for combinations that are not instantiated (the caller runs the two-kernel sequence).
 // Which (shape, operand) combinations kasf_launch_dgrad_wg has an instantiation for.  The engine asks BEFORE it launches the first of a block's two fused
 // kernels: a first launch that has already registered its dgamma / dbeta rows in the column sink cannot be taken back if the second one then declines.
+int kasf_dgrad_r_rows(int64_t M) {                      // launch_dgrad_r's `active` at the full grid
+    const int64_t tiles = (M + R_BM - 1) / R_BM, grid = tiles < 256 ? tiles : 256, per = (tiles + grid - 1) / grid;
+    return (int)((tiles + per - 1) / per);
+}
 bool kasf_dgrad_wg_supported(int Kd, bool resid, bool accumulate, bool dxn_add, bool dbias, bool proj, int64_t M, int64_t wpart_bytes) {
     if (M <= 0 || wpart_bytes < (int64_t)256 * Kd * 128 * 2) return false;
     if (proj) return Kd == 128 && resid && !accumulate && !dxn_add && !dbias;
@@ -555,6 +559,7 @@ int kasf_launch_dgrad_wg(hipStream_t s, const void* dY, int Kd, const void* Wt, 
 // the weight-gradient finish role.  fin: MlpFinArgs of kasf_launch_mlp_bwd_q (as void* to keep mlp_fin.h out of kernels.h).
 void kasf_launch_mlp_dgrad_fin(hipStream_t s, const void* dZ, const void* W1t, const void* X, const float* gamma, const void* g, void* g_in, float* dgamma, float* dbeta,
                                float* gsum, int64_t M, KasfColSink* sink, const void* fin_args, const float* b2, const float* ls2, float* dls2, bool have_w2) {
+    if (M <= 0) return;
     constexpr int KC = 4, NSTREAM = KC + 2, PLD = 384;
     constexpr size_t fixed = (size_t)R_TILE * 2;
     constexpr int RING = (3 * NSTREAM * R_TILE * 2 + fixed <= 160 * 1024) ? 3 : 2;

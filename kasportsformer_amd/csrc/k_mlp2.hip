@@ -114,6 +114,7 @@ int kasf_mlp_bwd_q_ranges(int64_t M) {
 void kasf_launch_mlp_bwd_q(hipStream_t s, const void* x, const void* xn, const void* g, const float* ln_g, const void* W1, const float* b1,
                            const void* W2ts, const void* W1t, void* dApart, float* partial, float* dW1, float* dW2, float* db1, float* gsum, void* g_in,
                            float* dgamma, float* dbeta, int64_t M, const float* W2, const float* b2, const float* ls2, float* dls2, KasfColSink* sink) {
+    if (M <= 0) return;                                  // (no tile, no range: tpr below would divide by zero)
     int ranges = kasf_mlp_bwd_q_ranges(M);
     const int64_t tiles = (M + Q_BM - 1) / Q_BM;
     { const int nr = kasf_narrow_grid(KASF_NG_MLP_BWD, 64, M); if (ranges > nr) ranges = nr; }

@@ -342,6 +342,7 @@ inline int kasf_narrow_grid(int cls, int full, int64_t tokens) {
 void kasf_launch_mlp_dgrad_fin(hipStream_t s, const void* dZ, const void* W1t, const void* X, const float* gamma, const void* g, void* g_in, float* dgamma, float* dbeta,
                                float* gsum, int64_t M, KasfColSink* sink, const void* fin_args, const float* b2, const float* ls2, float* dls2, bool have_w2);
 struct KasfBf16Reduce { const void* part; float* out; int nparts; int elems; };
+int kasf_dgrad_r_rows(int64_t M);   // workgroups of a full-width k_dgrad_r launch that own a tile: the rows it asks of the column sink (M >= 1)
 bool kasf_dgrad_wg_supported(int Kd, bool resid, bool accumulate, bool dxn_add, bool dbias, bool proj, int64_t M, int64_t wpart_bytes);
 int kasf_launch_dgrad_wg(hipStream_t s, const void* dY, int Kd, const void* Wt, const void* X, const float* gamma, const float* beta, const void* resid, void* out,
                          int accumulate, float* dgamma, float* dbeta, int64_t M, KasfColSink* sink, void* wpart, int64_t wpart_bytes, const void* dxn_add = nullptr,

@@ -109,6 +109,11 @@ _DT = [("dtype", dict(dtype=2))]
 _GCN = _DT + [("mode", dict(mode=2)), ("n_frames", dict(n_frames=3)), ("batch", dict(batch=0)), ("batch_big", dict(batch=2 ** 24, n_frames=256))]
 _SCRATCH = [("scratch_floats", dict(scratch_floats=0)), ("scratch_align", dict(scratch=OFF(4)))]
 
+# kasf_op_dgrad_wg: the eight arguments of its PROJ form, absent and present, and the bytes of 256 bf16 tiles of 128 x 128
+_NO_PROJ = dict(proj_o=None, proj_w=None, proj_b=None, proj_ls=None, dproj_w=None, dproj_b=None, dproj_ls=None, proj_part=None)
+_WG_TILES = 256 * 128 * 128 * 2
+_PROJ = dict({p: BUF for p in _NO_PROJ}, proj_part_bytes=_WG_TILES + 256 * 128 * 4)
+
 ENTRIES = [
     # ---- api_ops.hip: loss, optimizer, data, eval ----
     ("kasf_loss3", dict(losses_floats=12, batch=2, n_frames=3), [("shape", dict(batch=0)), ("shape_T", dict(n_frames=0)), ("losses", dict(losses_floats=11))], ()),
@@ -207,11 +212,18 @@ ENTRIES = [
                     ("state_align", dict(state=OFF(4)))], ("det_count",)),
     # ---- api_ops.hip: the unit-test entries ----
     ("kasf_op_linear", dict(dtype=0, M=1, N=128), _DT + [("N", dict(N=100))], ALL),
+    ("kasf_op_linear_res", dict(dtype=0, M=1), _DT, ()),
     ("kasf_op_mlp_fwd", dict(dtype=0, M=1), _DT, ALL),
     ("kasf_op_mlp_bwd", dict(dtype=0, M=1), _DT, ALL),
     ("kasf_op_mlp_bwd_fused", dict(M=1), [], ("ln_g", "w1", "b1", "w2t_scaled", "w1t", "dgamma", "dbeta")),
     ("kasf_op_wgrad", dict(dtype=0, N=128, K=128, M=1), _DT + [("N", dict(N=100)), ("K", dict(K=100)), ("ln_K", dict(K=256))], ALL),
     ("kasf_op_dgrad_lnbwd", dict(dtype=0, Kd=128, M=1), _DT + [("Kd", dict(Kd=100)), ("beta", dict(beta=None))], ALL),
+    ("kasf_op_dgrad_wg", dict(Kd=128, M=1, wpart_bytes=_WG_TILES, scratch_floats=256, dxn_add=None, dbias=None, **_NO_PROJ),
+     [("proj_together", dict(proj_o=BUF)), ("form", dict(Kd=512)), ("form_resid", dict(resid=None), "form"), ("form_acc", dict(accumulate=1), "form"),
+      ("form_uv", dict(Kd=256, dxn_add=BUF), "form"), ("form_proj", dict(Kd=384, **_PROJ), "form"), ("wpart_bytes", dict(wpart_bytes=_WG_TILES - 1)),
+      ("proj_part_bytes", dict(_PROJ, proj_part_bytes=_WG_TILES + 256 * 128 * 4 - 1)), ("align", dict(wpart=OFF(4))),
+      ("align_proj", dict(**{**_PROJ, "proj_part": OFF(8)}), "align")] + _SCRATCH + [("scratch_small", dict(M=33))],
+     ("dxn_add", "resid", "dbias") + tuple(_NO_PROJ)),
     ("kasf_op_attention_fwd", dict(dtype=0, batch=1, n_frames=4), _DT, ALL),
     ("kasf_op_attention_bwd", dict(dtype=0, batch=1, n_frames=4), _DT, ALL),
     ("kasf_op_attention_fwd_heads", dict(dtype=0, batch=1, n_frames=4, num_heads=8), _DT, ALL),
@@ -237,6 +249,8 @@ ENTRIES = [
 
 # (entry, message) of the refusals that no call from outside the library reaches on a machine without a device, each with its reason
 UNREACHABLE = [
+    ("kasf_op_dgrad_wg", "dgrad_wg: the launcher declined a form that kasf_dgrad_wg_supported accepts",
+     "behind the launcher: the entry has asked kasf_dgrad_wg_supported about the same arguments before, and refuses what it does not accept"),
     ("kasf_detect_boxes", "detect_boxes: the device refused the LDS size of the sort + NMS kernel",
      "comes back from the launcher, after its first kernel is on the stream: every host check has passed by then"),
 ]
