@@ -61,6 +61,8 @@
  *                             order; here the tracker's ids and slots drive the lifter's per-player histories on the device   demo/lib/hrnet/gen_kpts.py:125-170
  *   kasf_one_euro_push, kasf_one_euro_tracked, kasf_one_euro_tracks <- nothing in the reference (its unused revise_kpts, demo/lib/preprocess.py:72-103, patches
  *                             low-score leg joints): the One-Euro filter live pose pipelines put between the pose network and the lift, and behind the lift
+ *   kasf_bone_median, kasf_bone_apply, kasf_bone_push, kasf_bone_tracked <- nothing in the demo; the bone table is get_limb_lens' (utils/loss_calc.py) and the
+ *                             quantity held constant is what loss_limb_var_calc penalises in training: one length per bone per player, re-imposed on every frame
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
  *   kasf_op_gcn_fwd, kasf_op_gcn_bwd <- GCN.forward between its U | V Linear and the residual, and autograd of it   model/modules/graph.py:19-134, KASportsFormer.py:109
  */
@@ -901,6 +903,57 @@ int kasf_one_euro_tracked(const float* x, const int32_t* ids, const int32_t* slo
                           int64_t tick, float* xhat, float* dxhat, int64_t* last, int32_t* owner, float* out, int32_t* row_slot, void* stream);
 int kasf_one_euro_tracks(const float* x, const int64_t* offsets, int64_t N, int32_t P, int32_t J, int32_t C, int32_t has_score,
                          const kasf_one_euro_params* params, float* out, void* stream);
+
+/* ---- constant limb lengths per player (ADDED under ABI 12: additive, kasf_version() stays 12; look the four symbols up by name).  The lift predicts every
+ * window on its own and the One-Euro filter steadies positions, not the skeleton: a thigh still breathes from frame to frame.  This stage, between the lift and
+ * kasf_pose_world, gives every bone of a player one length and re-imposes it on every frame, keeping the directions (so the joint angles) and the root.
+ * Nothing is read back, nothing is allocated, floating-point atomics are not used: the bits are the same from run to run.
+ *
+ * A FRAME is [17][3] fp32 in the Human3.6M order.  BONE k (0..15) joins child joint k + 1 to parent joint (0,1,2,0,4,5,0,7,8,9,8,11,12,8,14,15)[k] (the model's
+ * own table, get_limb_lens of utils/loss_calc.py); a parent has the lower index, so ascending k walks from the root.
+ *
+ * The rule, in fp32, every line one rounded operation (a line with two: left to right); the library is built with -ffp-contract=off and a correctly rounded
+ * divide and square root:
+ *   1. Length of bone k in a frame x:  v = x[child] - x[parent];  l = sqrtf((vx * vx + vy * vy) + vz * vz).  The length is USABLE iff l is finite and l > 0.
+ *      A frame is USABLE iff all its 51 values are finite.
+ *   2. Target length of a track: L[p][k] = the lower median of the usable lengths of bone k over the usable frames of track p, the element of rank
+ *      (n - 1) / 2 (integer division) in ascending order; cnt[p][k] = n; n = 0 gives L = 0, which means "leave this bone alone".  An entry of a table that is
+ *      not > 0 means the same.  An order statistic: its bits do not depend on how it is found.
+ *   3. symmetric: the left / right partner bones 0-3, 1-4, 2-5, 10-13, 11-14, 12-15 each get (La + Lb) * 0.5f; if one of the two is 0, both get the other.
+ *      Applied to the table before use, never stored; applying it twice gives the same bits.
+ *   4. Apply, per usable frame: y[0] = x[0]; for k ascending: if L[k] > 0 and l is usable, s = L[k] / l and y[child] = y[parent] + v * s (multiply, then add);
+ *      otherwise y[child] = y[parent] + v.  A frame that is not usable is copied through bit for bit.
+ *   5. Live: per slot g, len [S][16] fp32 and cnt [S][16] int32 (initially cnt = 0; len needs no initial value).  A usable frame updates every usable bone:
+ *      if cnt == 0, len = l, otherwise len = len + (l - len) / float(min(cnt + 1, window)); then cnt = min(cnt + 1, window): the running mean over the first
+ *      `window` frames, after that an exponential average of weight 1 / window.  The frame is then walked by 4 with the table L[k] = cnt > 0 ? len : 0, after 3
+ *      if symmetric.  A frame that is not usable, or an invalid row, is copied through and leaves len and cnt as they are.  The live form is a mean, not a median.
+ *
+ * kasf_bone_median: poses [N][17][3] packed, track p = frames offsets[p] .. offsets[p + 1] - 1 (device int64 [P + 1], clamped into [0, N] and to a non-negative
+ * length as kasf_one_euro_tracks clamps them) -> lengths [P][16] fp32 and, unless NULL, counts [P][16] int32.  scratch: N * 16 floats of the caller's (the
+ * lengths, bone-major).  Two launches: the lengths over the packed frames, then a radix select over their bit patterns, one workgroup per (track, bone).
+ *
+ * kasf_bone_apply: poses, out [N][17][3].  per_track != 0: lengths [P][16] and offsets [P + 1], which must ascend from 0 to N (as the median's do); a frame of no
+ * track is copied through.  per_track == 0: lengths is one [16] for every frame, offsets and P are not read.  One launch; out and poses are distinct arrays.
+ *
+ * kasf_bone_push: poses, out [K][17][3]; row i goes to slot slots[i] (device int32 [K]), slots = NULL means slot i (K == S), as kasf_one_euro_push.  The ids of
+ * a call are distinct; an id outside [0, S) makes the row a copy-through that touches no state.  One launch, one wavefront per row.
+ *
+ * kasf_bone_tracked: poses, out [streams * R][17][3]; ids, slot, born, count_b, rows_mode, R, owner [streams * track_slots] (initially 0) and row_slot (may be
+ * NULL) are kasf_one_euro_tracked's, and a row's slot, validity and restart are resolved by its rule to the word.  A slot that restarts gets cnt[g][:] = 0 and
+ * owner[g] = id whatever the frame holds; then rule 5 runs.
+ *
+ * P = 0 (median), N = 0 (apply) or K = 0 does nothing.  Error 2, before a device or a device pointer is touched: N or P negative, N >= 2^31; K or S negative,
+ * K > S, NULL slots with 0 < K < S; window outside [1, 2^20]; streams < 1, track_slots outside 1..64, R < 1, streams * R or streams * track_slots beyond 32
+ * bits, a rows_mode that is neither constant; out == poses (apply); a null pointer (counts, slots and row_slot may be NULL; offsets with per_track == 0;
+ * poses and scratch of the median with N == 0).  The inputs are never written. */
+int kasf_bone_median(const float* poses, const int64_t* offsets, int64_t N, int32_t P, float* scratch, float* lengths, int32_t* counts, void* stream);
+int kasf_bone_apply(const float* poses, const int64_t* offsets, int64_t N, int32_t P, const float* lengths, int32_t per_track, int32_t symmetric, float* out,
+                    void* stream);
+int kasf_bone_push(const float* poses, const int32_t* slots, int32_t K, int32_t S, int32_t window, int32_t symmetric, float* len, int32_t* cnt, float* out,
+                   void* stream);
+int kasf_bone_tracked(const float* poses, const int32_t* ids, const int32_t* slot, const int32_t* born, const int32_t* count_b, int32_t streams,
+                      int32_t track_slots, int32_t rows_mode, int32_t R, int32_t window, int32_t symmetric, float* len, int32_t* cnt, int32_t* owner, float* out,
+                      int32_t* row_slot, void* stream);
 
 /* debugging / tests: locate a named activation inside the workspace (see kasf_ws_name()) */
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags);

@@ -116,6 +116,10 @@ SIGNATURES = {
     "kasf_one_euro_push": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(KasfOneEuroParams), _i64, _vp, _vp, _vp, _vp, _vp]),
     "kasf_one_euro_tracked": (_i32, [_vp] * 5 + [_i32] * 7 + [C.POINTER(KasfOneEuroParams), _i64] + [_vp] * 7),
     "kasf_one_euro_tracks": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, C.POINTER(KasfOneEuroParams), _vp, _vp]),
+    "kasf_bone_median": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "kasf_bone_apply": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "kasf_bone_push": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "kasf_bone_tracked": (_i32, [_vp] * 5 + [_i32] * 6 + [_vp] * 6),
     "kasf_coco_h36m": (_i32, [_vp, _i64, _vp, _vp]),
     "kasf_pose_world": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "kasf_heatmap_keypoints": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i32, C.c_double, _i32, _i32, _vp, _vp, _vp]),

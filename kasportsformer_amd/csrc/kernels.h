@@ -230,6 +230,18 @@ void kasf_launch_one_euro_tracked(hipStream_t s, const float* x, const int* ids,
 void kasf_launch_one_euro_tracks(hipStream_t s, const float* x, const int64_t* offsets, int64_t N, int P, int J, int C, int has_score, const KasfOneEuro& p,
                                  float* out);
 
+// ---- k_bones.hip: constant limb lengths per player (kasf.h, kasf_bone_*): frames of [17,3] fp32, 16 bones; scratch [16][N] holds bone k's length in frame f
+// at k * N + f, 0 where it is not usable; lengths / counts [P][16]; the live state len / cnt [S][16]; arguments as checked by the entry points ----
+void kasf_launch_bone_lengths(hipStream_t s, const float* poses, int64_t N, float* scratch);
+// track p = frames [offsets[p], offsets[p+1]) of the packed array; counts may be null
+void kasf_launch_bone_select(hipStream_t s, const float* scratch, const int64_t* offsets, int64_t N, int P, float* lengths, int* counts);
+// per_track: lengths [P][16] by offsets; else one [16] for every frame (offsets unread)
+void kasf_launch_bone_apply(hipStream_t s, const float* poses, const int64_t* offsets, int64_t N, int P, const float* lengths, int per_track, int symmetric,
+                            float* out);
+void kasf_launch_bone_push(hipStream_t s, const float* x, const int* slots, int K, int S, int window, int symmetric, float* len, int* cnt, float* out);
+void kasf_launch_bone_tracked(hipStream_t s, const float* x, const int* ids, const int* slot, const int* born, const int* count_b, int B, int S_t, int rows_mode,
+                              int R, int window, int symmetric, float* len, int* cnt, int* owner, float* out, int* row_slot);
+
 // ---- k_pose.hip: the two ends of the lift (kasf.h, kasf_coco_h36m / kasf_pose_world); frames of [17,3] fp32, src and dst distinct arrays ----
 void kasf_launch_coco_h36m(hipStream_t s, const float* coco, int64_t frames, float* h36m);
 // q [4], t [3]: host arrays, passed by value into the launch

@@ -21,7 +21,8 @@ the forward together (``kasf_lift_windows_ragged`` / ``kasf_lift_stitch_ragged``
 
 ``layout="coco"`` (``--layout coco``) takes the keypoints as a COCO-17 detector writes them and converts them on the device first
 (``kasportsformer_amd.pose.coco_to_h36m``); ``--smooth [--smooth-rate] [--smooth-min-cutoff] [--smooth-beta] [--smooth-min-score]`` sends the keypoints
-through the One-Euro filter first (``kasportsformer_amd.smooth.smooth_tracks``), offline and ``--online`` alike; ``--world [--world-floor] [--world-unit]`` sends the poses through ``poses_to_world`` before they are written.
+through the One-Euro filter first (``kasportsformer_amd.smooth.smooth_tracks``), offline and ``--online`` alike; ``--fix-bones [--fix-bones-symmetric]`` gives every bone of a track one length
+(``kasportsformer_amd.bones.fix_bone_lengths`` over the final poses, before ``--world``); ``--world [--world-floor] [--world-unit]`` sends the poses through ``poses_to_world`` before they are written.
 """
 from __future__ import annotations
 
@@ -351,6 +352,9 @@ def _parse(argv=None):
     ap.add_argument("--smooth-min-cutoff", type=float, default=None, help="--smooth: cutoff at rest in Hz (default 1.0; lower: steadier, more lag)")
     ap.add_argument("--smooth-beta", type=float, default=None, help="--smooth: cutoff gained per pixel / s of speed (default 0.01; higher: less lag in motion)")
     ap.add_argument("--smooth-min-score", type=float, default=None, help="--smooth: a joint scored below this holds (default 0.3)")
+    ap.add_argument("--fix-bones", action="store_true", help="give every bone of a track one length, the track's lower median (kasportsformer_amd.fix_bone_lengths), "
+                                                             "over the final poses and before --world")
+    ap.add_argument("--fix-bones-symmetric", action="store_true", help="--fix-bones: left / right partner bones get their mean")
     ap.add_argument("--out", required=True, help="output .npy of [P,N,17,3] (or [N,17,3]) float32 poses; tracks of different lengths: an .npz "
                                                  "of track_0 ... track_{P-1}")
     args = ap.parse_args(argv)
@@ -360,6 +364,8 @@ def _parse(argv=None):
     for k, v in smooth_defaults.items():
         if getattr(args, k) is None:
             setattr(args, k, v)
+    if args.fix_bones_symmetric and not args.fix_bones:
+        ap.error("--fix-bones-symmetric belongs to --fix-bones")
     if args.online and args.stride is not None:
         ap.error("--online lifts the sliding window of every tick: it takes no --stride")
     if args.lag and not args.online:
@@ -388,6 +394,9 @@ def main(argv=None):
                                   min_score=args.smooth_min_score, device=_model_device(model))
 
     def final(poses):
+        if args.fix_bones:                             # one track [N,17,3], or [P,N,17,3]: every track its own medians
+            from .bones import fix_bone_lengths
+            poses = fix_bone_lengths(poses, symmetric=args.fix_bones_symmetric)
         return poses_to_world(poses, floor=args.world_floor, unit=args.world_unit) if args.world else poses
 
     if args.online:
