@@ -1016,7 +1016,12 @@ int kasf_op_dgrad_wg(const void* dy, int32_t Kd, const void* wt, const void* dxn
                      void* out, int32_t accumulate, float* dgamma, float* dbeta, float* dw, float* dbias, const void* proj_o, const float* proj_w,
                      const float* proj_b, const float* proj_ls, float* dproj_w, float* dproj_b, float* dproj_ls, int64_t M, void* wpart, int64_t wpart_bytes,
                      void* proj_part, int64_t proj_part_bytes, float* scratch, int64_t scratch_floats, void* stream);
-/* attention core (selfattention.py:18-41): q [*,ldq], k/v [*,ldkv] token-major; mode 0 spatial, 1 temporal */
+/* attention core (selfattention.py:18-41): q [*,ldq], k/v [*,ldkv] token-major; mode 0 spatial, 1 temporal; o and d_o are [M,128] (leading dimension 128).
+ * The five kasf_op_attention_* entries refuse (error 2, nothing launched): a mode other than 0 or 1, batch < 0, n_frames < 1, batch * n_frames * 17 * max(384, the
+ * largest leading dimension) >= 2^31 (the kernels index in 32 bits), a leading dimension below 128 (the columns each of q, k, v, dq, dk, dv addresses from its own
+ * pointer) or not a multiple of 8 elements, a NULL pointer, and a pointer that is not 16-byte aligned (rows move in 16-byte pieces in both dtypes).  batch = 0
+ * returns 0 after the checks and launches nothing (kasf_op_attention_bwd_fused_do refuses batch < 1, as it always did).  Columns between 128 and a padded leading
+ * dimension are neither read nor written. */
 int kasf_op_attention_fwd(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int32_t batch, int32_t n_frames,
                           int32_t mode, void* stream);
 int kasf_op_attention_bwd(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* d_o, void* dq, int64_t lddq,
@@ -1035,6 +1040,24 @@ int kasf_op_attention_bwd_heads(int32_t dtype, const void* q, int64_t ldq, const
 int kasf_op_attention_bwd_fused_do(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* g_mid, const void* wproj_t_scaled,
                                    void* dq, int64_t lddq, void* dk, void* dv, int64_t lddkv, int32_t batch, int32_t n_frames, int32_t mode, int32_t form,
                                    const void* o_saved, const float* lse, void* stream);
+/* bf16, 8 heads, groups of <= 96 positions: the forward of one attention block (bone = 0, selfattention.py:18-41) or bone cross-attention block (bone = 1,
+ * bone_crossattention.py:19-41) in one launch, exactly as the engine launches it:
+ *     out = x + ls1 * (proj(softmax(q k^T / 4) v) + bproj),   bone 0: q | k | v = LN(x; ln_g, ln_b) wq^T,            wq [384,128] (rows 0..127 q, 128..255 k, 256..383 v)
+ *                                                             bone 1: q = LN(x) wq^T, wq [128,128];  k | v = LN(x_limb; lnl_g, lnl_b) wkv^T,  wkv [256,128]
+ * x, x_limb, out [M,128] bf16 token-major, M = batch * n_frames * 17 in [batch][frame][joint] order; wq, wkv, wproj [128,128] bf16 row-major [out][in]; the LayerNorm
+ * parameters, bproj and ls1 are fp32 [128].  Head h owns features 16h..16h+15 of q, k and v.  mode 0: a group is the 17 joints of a frame; 1: the n_frames
+ * positions of one (clip, joint) track.
+ * Saves (what a backward pass reads; all NULL in evaluation, when nothing but out is written): q_save [M,384] = q | k | v (bone: [M,128] = q) and o_save [M,128] (the
+ * heads' outputs in front of proj) go together; kv_save [M,256] = k | v is given exactly when bone = 1 and the saves are given; lse_save [M,8] fp32 (log-sum-exp of
+ * the scaled scores per token and head, the operand of kasf_op_attention_bwd_fused_do's key-tile-outer kernel) is optional with the saves and is written only for
+ * groups of 33..96 positions -- for shorter groups it is left untouched.
+ * out must not alias x or x_limb: a workgroup loads the next group's rows while it stores.  Every bf16 pointer is 16-byte aligned.
+ * Refused with error 2, in this order: bone or mode not 0 / 1; batch < 0; n_frames < 1; batch * n_frames * 17 * 384 >= 2^31; groups of more than 96 positions
+ * (mode 1: n_frames > 96); the bone operands (x_limb, lnl_g, lnl_b, wkv) not all given with bone = 1 or not all NULL with bone = 0; the saves not together as above;
+ * a NULL among the other pointers; out aliasing an input; a misaligned bf16 pointer.  batch = 0 returns 0 after the checks and launches nothing. */
+int kasf_op_attn_block_fwd(int32_t bone, const void* x, const void* x_limb, const float* ln_g, const float* ln_b, const float* lnl_g, const float* lnl_b, const void* wq,
+                           const void* wkv, const void* wproj, const float* bproj, const float* ls1, void* q_save, void* kv_save, void* o_save, float* lse_save,
+                           void* out, int32_t batch, int32_t n_frames, int32_t mode, void* stream);
 /* ---- the GCN mixer on its own (ABI 12; modules/graph.py:19-134 between the U | V Linear and the residual of KASportsFormer.py:109) ----
  * M = batch * n_frames * 17 tokens in [batch][frame][joint] order.  mode 0 = spatial (fixed skeleton adjacency, BatchNorm channel = joint, 17 nodes), 1 = temporal
  * (per (clip, joint) track: S = xn xn^T, every frame whose similarity reaches the neighbour_num-th largest of its row is a neighbour -- ties are all kept, so a row's

@@ -2,6 +2,7 @@
 // C++ linkage, inline only: nothing here is exported.  A refuse_* helper returns 0, or sets kasf_last_error() to "who: why" and returns 2; an entry calls them in the
 // order of its own checks (tests/test_refusals_cpu.py holds every message, code and the order to tests/golden/refusals.json).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <string>
 
@@ -67,6 +68,24 @@ inline int refuse_partner(const char* who, const int32_t* pt) {
     for (int j = 0; j < 17; ++j)
         if (pt[pt[j]] != j) return refuse(who, "partner must be an involution (partner[partner[j]] == j)");
     return 0;
+}
+
+// ---- the attention kernels on their own (kasf.h, kasf_op_attention_fwd ... kasf_op_attn_block_fwd) ----
+inline int refuse_attn_mode(const char* who, int32_t mode) { return mode != 0 && mode != 1 ? refuse(who, "mode must be 0 (spatial) or 1 (temporal)") : 0; }
+// the kernels index tokens x leading dimension in 32 bits: one bound for all of them, at the widest row any of them addresses (384, or a padded leading dimension)
+inline bool attn_index_overflows(int32_t batch, int32_t n_frames, int64_t ld = 384) {
+    const int64_t frames = (int64_t)batch * n_frames, row = 17 * (ld < 384 ? 384 : ld > ((int64_t)1 << 31) ? (int64_t)1 << 31 : ld);
+    return frames > (((int64_t)1 << 31) - 1) / row;          // frames * row >= 2^31, without the product
+}
+inline int refuse_attn_shape(const char* who, int32_t mode, int32_t batch, int32_t n_frames, int64_t ld = 384) {
+    if (int rc = refuse_attn_mode(who, mode)) return rc;
+    if (batch < 0) return refuse(who, "batch must be >= 0");
+    if (n_frames < 1) return refuse(who, "n_frames must be >= 1");
+    return attn_index_overflows(batch, n_frames, ld) ? refuse(who, "batch * n_frames * 17 * max(384, leading dimension) must stay below 2^31") : 0;
+}
+// name: "ldq", "ldkv", ...; every row is read and written in 16-byte pieces of 8 (bf16) or 4 (fp32) elements
+inline int refuse_attn_ld(const char* who, const char* name, int64_t ld) {
+    return ld < 128 || ld % 8 != 0 ? refuse(who, std::string(name) + " must be at least 128 (the columns a pointer addresses) and a multiple of 8 elements") : 0;
 }
 
 // ---- the prologue, gate, head and embedding kernels on their own (kasf.h, kasf_op_prologue_fwd ... kasf_op_add) ----

@@ -1,6 +1,7 @@
 // The C entry points around the model (kasf.h): loss, optimizer, data and evaluation, then the kasf_op_* entries that run one kernel family on its own for the
 // unit tests.  The entries that read a kasf_model are in engine.hip.  Every refusal returns before any device call.
 #include <cstring>
+#include <initializer_list>
 
 #include "api_check.h"
 
@@ -181,23 +182,33 @@ int kasf_op_dgrad_wg(const void* dy, int32_t Kd, const void* wt, const void* dxn
     else kasf_launch_bf16_reduce(s, 1, &red);
     return api_done(ms.finish(s));
 }
+// ---- the attention kernels on their own (kasf.h, kasf_op_attention_fwd ... kasf_op_attn_block_fwd): what the five core entries check alike, after their dtype ----
+struct AttnLd { const char* name; int64_t ld; };
+static int attn_core_check(const char* who, int32_t mode, int32_t batch, int32_t n_frames, std::initializer_list<AttnLd> lds, std::initializer_list<const void*> ptrs) {
+    int64_t widest = 384;
+    for (const AttnLd& l : lds) widest = std::max(widest, l.ld);
+    if (int rc = refuse_attn_shape(who, mode, batch, n_frames, widest)) return rc;
+    for (const AttnLd& l : lds)
+        if (int rc = refuse_attn_ld(who, l.name, l.ld)) return rc;
+    for (const void* p : ptrs)
+        if (p == nullptr) return refuse_null();
+    for (const void* p : ptrs)              // every kernel behind these entries moves rows in 16-byte pieces (load8 / store8, bf16x8, f32x4), in both dtypes
+        if (misaligned16(p)) return refuse(who, "every pointer must be 16-byte aligned");
+    return 0;
+}
 int kasf_op_attention_fwd(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int32_t batch, int32_t n_frames,
                           int32_t mode, void* stream) {
-    OP_DT_CHECK(dtype);
-    api_clear_error();
-    kasf_launch_attn_fwd(dtype, (hipStream_t)stream, q, ldq, k, v, ldkv, o, batch, n_frames, mode);
-    return api_done(api_launchers_spoke());
+    return kasf_op_attention_fwd_heads(dtype, q, ldq, k, v, ldkv, o, batch, n_frames, mode, 8, stream);
 }
 int kasf_op_attention_bwd(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* d_o, void* dq, int64_t lddq,
                           void* dk, void* dv, int64_t lddkv, int32_t batch, int32_t n_frames, int32_t mode, void* stream) {
-    OP_DT_CHECK(dtype);
-    api_clear_error();
-    kasf_launch_attn_bwd(dtype, (hipStream_t)stream, q, ldq, k, v, ldkv, d_o, dq, lddq, dk, dv, lddkv, batch, n_frames, mode);
-    return api_done(api_launchers_spoke());
+    return kasf_op_attention_bwd_heads(dtype, q, ldq, k, v, ldkv, d_o, dq, lddq, dk, dv, lddkv, batch, n_frames, mode, 8, stream);
 }
 int kasf_op_attention_fwd_heads(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int32_t batch, int32_t n_frames,
                                 int32_t mode, int32_t num_heads, void* stream) {
     OP_DT_CHECK(dtype);
+    if (int rc = attn_core_check("attention_fwd", mode, batch, n_frames, {{"ldq", ldq}, {"ldkv", ldkv}}, {q, k, v, o})) return rc;
+    if (batch == 0) return 0;
     api_clear_error();
     kasf_launch_attn_fwd(dtype, (hipStream_t)stream, q, ldq, k, v, ldkv, o, batch, n_frames, mode, num_heads);
     return api_done(api_launchers_spoke());
@@ -205,18 +216,55 @@ int kasf_op_attention_fwd_heads(int32_t dtype, const void* q, int64_t ldq, const
 int kasf_op_attention_bwd_heads(int32_t dtype, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* d_o, void* dq, int64_t lddq,
                                 void* dk, void* dv, int64_t lddkv, int32_t batch, int32_t n_frames, int32_t mode, int32_t num_heads, void* stream) {
     OP_DT_CHECK(dtype);
+    if (int rc = attn_core_check("attention_bwd", mode, batch, n_frames, {{"ldq", ldq}, {"ldkv", ldkv}, {"lddq", lddq}, {"lddkv", lddkv}}, {q, k, v, d_o, dq, dk, dv}))
+        return rc;
+    if (batch == 0) return 0;
     api_clear_error();
     kasf_launch_attn_bwd(dtype, (hipStream_t)stream, q, ldq, k, v, ldkv, d_o, dq, lddq, dk, dv, lddkv, batch, n_frames, mode, num_heads);
     return api_done(api_launchers_spoke());
 }
+// (this entry refused batch = 0 before the others learnt to return 0 for it, and keeps doing so: its first three messages and their order are recorded)
 int kasf_op_attention_bwd_fused_do(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* g_mid, const void* wproj_t_scaled, void* dq,
                                    int64_t lddq, void* dk, void* dv, int64_t lddkv, int32_t batch, int32_t n_frames, int32_t mode, int32_t form, const void* o_saved,
                                    const float* lse, void* stream) {
     api_clear_error();
     if (form < 0 || form > 1) return kasf_set_error(2, "form: 0 (persistent) or 1 (one group per workgroup)");
     if (batch < 1 || n_frames < 1 || (int64_t)batch * n_frames * 17 * 384 >= ((int64_t)1 << 31)) return kasf_set_error(2, "batch * n_frames * 17 * 384 must stay below 2^31");
+    if (int rc = refuse_attn_mode("attention_bwd_fused_do", mode)) return rc;
+    const int L = mode == 0 ? 17 : n_frames;
+    const char* group = "fused-d_o attention backward: groups of at most 96 positions (form 1: at most 32); bf16, 8 heads";
+    if (L > 96 || (form == 1 && L > 32)) return kasf_set_error(2, group);
+    if (int rc = attn_core_check("attention_bwd_fused_do", mode, batch, n_frames, {{"ldq", ldq}, {"ldkv", ldkv}, {"lddq", lddq}, {"lddkv", lddkv}},
+                                 {q, k, v, g_mid, wproj_t_scaled, dq, dk, dv}))
+        return rc;
+    if (misaligned16(o_saved) || misaligned16(lse)) return refuse("attention_bwd_fused_do", "every pointer must be 16-byte aligned");
     if (!kasf_launch_attn_bwd_fused_do((hipStream_t)stream, q, ldq, k, v, ldkv, g_mid, wproj_t_scaled, dq, lddq, dk, dv, lddkv, batch, n_frames, mode, form, o_saved, lse))
-        return kasf_set_error(2, "fused-d_o attention backward: groups of at most 96 positions (form 1: at most 32); bf16, 8 heads");
+        return kasf_set_error(2, group);
+    return api_done(api_launchers_spoke());
+}
+// the fused attention block's forward, launched exactly as block_forward (engine.hip) launches it in bf16 mode with 8 heads
+int kasf_op_attn_block_fwd(int32_t bone, const void* x, const void* x_limb, const float* ln_g, const float* ln_b, const float* lnl_g, const float* lnl_b, const void* wq,
+                           const void* wkv, const void* wproj, const float* bproj, const float* ls1, void* q_save, void* kv_save, void* o_save, float* lse_save,
+                           void* out, int32_t batch, int32_t n_frames, int32_t mode, void* stream) {
+    const char* who = "attn_block_fwd";
+    if (bone != 0 && bone != 1) return refuse(who, "bone must be 0 (self-attention) or 1 (bone cross-attention)");
+    if (int rc = refuse_attn_shape(who, mode, batch, n_frames)) return rc;
+    const char* group = "the fused kernels cover groups of at most 96 positions (temporal: n_frames <= 96)";
+    if ((mode == 0 ? 17 : n_frames) > 96) return refuse(who, group);
+    const int nbone = (x_limb != nullptr) + (lnl_g != nullptr) + (lnl_b != nullptr) + (wkv != nullptr);
+    if (nbone != (bone ? 4 : 0)) return refuse(who, "x_limb, lnl_g, lnl_b and wkv are all given with bone = 1 and all NULL with bone = 0");
+    if ((q_save != nullptr) != (o_save != nullptr)) return refuse(who, "q_save and o_save go together");
+    if ((kv_save != nullptr) != (bone && q_save != nullptr)) return refuse(who, "kv_save is given exactly when bone = 1 and q_save / o_save are given");
+    if (lse_save != nullptr && q_save == nullptr) return refuse(who, "lse_save needs q_save and o_save");
+    if (!x || !ln_g || !ln_b || !wq || !wproj || !bproj || !ls1 || !out) return refuse_null();
+    if (out == x || (bone && out == x_limb)) return refuse(who, "out must not alias x or x_limb (a workgroup prefetches the next group's rows while it stores)");
+    for (const void* p : {x, x_limb, wq, wkv, wproj, (const void*)q_save, (const void*)kv_save, (const void*)o_save, (const void*)out})
+        if (misaligned16(p)) return refuse(who, "x, x_limb, wq, wkv, wproj, q_save, kv_save, o_save and out must be 16-byte aligned");
+    if (batch == 0) return 0;
+    api_clear_error();
+    if (!kasf_launch_attn_block_fwd((hipStream_t)stream, bone, x, x_limb, ln_g, ln_b, lnl_g, lnl_b, wq, wkv, wproj, bproj, ls1, q_save, kv_save, o_save, out, batch, n_frames,
+                                    mode, lse_save))
+        return refuse(who, group);             // (the launcher's own `false`: the same bound)
     return api_done(api_launchers_spoke());
 }
 // ---- the GCN mixer on its own (kasf.h, kasf_op_gcn_fwd / kasf_op_gcn_bwd): the launch sequence and `count` of block_forward / block_backward ----

@@ -114,6 +114,18 @@ _NO_PROJ = dict(proj_o=None, proj_w=None, proj_b=None, proj_ls=None, dproj_w=Non
 _WG_TILES = 256 * 128 * 128 * 2
 _PROJ = dict({p: BUF for p in _NO_PROJ}, proj_part_bytes=_WG_TILES + 256 * 128 * 4)
 
+# the attention entries: what kasf_op_attention_* check alike behind their dtype (api_ops.hip, attn_core_check), and the block forward's absent / present operands
+_ATTN_BASE = dict(dtype=0, batch=1, n_frames=4, ldq=128, ldkv=128)
+_ATTN_BWD_BASE = dict(_ATTN_BASE, lddq=128, lddkv=128)
+_ATTN_SHAPE = [("mode", dict(mode=2)), ("batch", dict(batch=-1)), ("n_frames", dict(n_frames=0)), ("big", dict(batch=2 ** 20, n_frames=2 ** 10)),
+               ("big_ld", dict(batch=2 ** 10, n_frames=2 ** 5, ldkv=4096), "big")]
+_ATTN_LD = [("ldq", dict(ldq=120)), ("ldq_8", dict(ldq=132)), ("ldkv", dict(ldkv=64)), ("ldkv_8", dict(ldkv=388)), ("lddq", dict(lddq=0)), ("lddq_8", dict(lddq=129)),
+            ("lddkv", dict(lddkv=-128)), ("lddkv_8", dict(lddkv=260))]
+_ATTN_ALIGN = [("align", dict(q=OFF(8))), ("align_o", dict(o=OFF(4)), "align")]
+_ATTN_FUSED_BASE = {k: v for k, v in _ATTN_BWD_BASE.items() if k != "dtype"}
+_BLK_BASE = dict(bone=0, batch=1, n_frames=4, mode=0, x_limb=None, lnl_g=None, lnl_b=None, wkv=None, q_save=None, kv_save=None, o_save=None, lse_save=None)
+_BLK_BONE = dict(bone=1, x_limb=BUF, lnl_g=BUF, lnl_b=BUF, wkv=BUF)
+
 ENTRIES = [
     # ---- api_ops.hip: loss, optimizer, data, eval ----
     ("kasf_loss3", dict(losses_floats=12, batch=2, n_frames=3), [("shape", dict(batch=0)), ("shape_T", dict(n_frames=0)), ("losses", dict(losses_floats=11))], ()),
@@ -224,13 +236,22 @@ ENTRIES = [
       ("proj_part_bytes", dict(_PROJ, proj_part_bytes=_WG_TILES + 256 * 128 * 4 - 1)), ("align", dict(wpart=OFF(4))),
       ("align_proj", dict(**{**_PROJ, "proj_part": OFF(8)}), "align")] + _SCRATCH + [("scratch_small", dict(M=33))],
      ("dxn_add", "resid", "dbias") + tuple(_NO_PROJ)),
-    ("kasf_op_attention_fwd", dict(dtype=0, batch=1, n_frames=4), _DT, ALL),
-    ("kasf_op_attention_bwd", dict(dtype=0, batch=1, n_frames=4), _DT, ALL),
-    ("kasf_op_attention_fwd_heads", dict(dtype=0, batch=1, n_frames=4, num_heads=8), _DT, ALL),
-    ("kasf_op_attention_bwd_heads", dict(dtype=0, batch=1, n_frames=4, num_heads=8), _DT, ALL),
-    ("kasf_op_attention_bwd_fused_do", dict(batch=1, n_frames=4),
+    ("kasf_op_attention_fwd", _ATTN_BASE, _DT + _ATTN_SHAPE + _ATTN_LD[:4] + _ATTN_ALIGN, ()),
+    ("kasf_op_attention_bwd", _ATTN_BWD_BASE, _DT + _ATTN_SHAPE + _ATTN_LD + [_ATTN_ALIGN[0], ("align_dv", dict(dv=OFF(4)), "align")], ()),
+    ("kasf_op_attention_fwd_heads", dict(_ATTN_BASE, num_heads=8), _DT + _ATTN_SHAPE + _ATTN_LD[:4] + _ATTN_ALIGN, ()),
+    ("kasf_op_attention_bwd_heads", dict(_ATTN_BWD_BASE, num_heads=8), _DT + _ATTN_SHAPE + _ATTN_LD + [_ATTN_ALIGN[0], ("align_dv", dict(dv=OFF(4)), "align")], ()),
+    # (the first five cases are older than the shared checks: this entry refuses batch = 0, and its own messages come first)
+    ("kasf_op_attention_bwd_fused_do", _ATTN_FUSED_BASE,
      [("form", dict(form=2)), ("batch", dict(batch=0)), ("batch_big", dict(batch=2 ** 20, n_frames=2 ** 10)), ("group", dict(mode=1, n_frames=97)),
-      ("group_form1", dict(mode=1, n_frames=33, form=1))], ALL),
+      ("group_form1", dict(mode=1, n_frames=33, form=1)), ("mode", dict(mode=2)), ("big_ld", dict(batch=2 ** 10, n_frames=2 ** 5, lddkv=4096))] + _ATTN_LD
+     + [("align", dict(g_mid=OFF(8))), ("align_lse", dict(lse=OFF(4)), "align")], ("o_saved", "lse")),
+    ("kasf_op_attn_block_fwd", _BLK_BASE,
+     [("bone", dict(bone=2)), ("mode", dict(mode=2)), ("batch", dict(batch=-1)), ("n_frames", dict(n_frames=0)), ("big", dict(batch=2 ** 20, n_frames=2 ** 10)),
+      ("group", dict(mode=1, n_frames=97)), ("bone_operands", dict(bone=1)), ("bone_partial", dict(bone=1, x_limb=BUF, lnl_g=BUF, lnl_b=BUF), "bone_operands"),
+      ("bone_extra", dict(x_limb=BUF), "bone_operands"), ("saves", dict(q_save=BUF)), ("saves_o", dict(q_save=None, o_save=BUF), "saves"),
+      ("kv_save", dict(q_save=BUF, o_save=BUF, kv_save=BUF)), ("kv_save_bone", dict(_BLK_BONE, q_save=BUF, o_save=BUF), "kv_save"), ("lse_save", dict(lse_save=BUF)),
+      ("alias", dict(out=SAME("x"))), ("align", dict(x=OFF(8))), ("align_out", dict(out=OFF(4)), "align"), ("align_save", dict(q_save=OFF(8), o_save=BUF), "align")],
+     ("x_limb", "lnl_g", "lnl_b", "wkv", "q_save", "kv_save", "o_save", "lse_save")),
     ("kasf_op_gcn_fwd", dict(dtype=0, batch=1, n_frames=4, mode=1, neighbour_num=4),
      _GCN + [("neighbour_num", dict(neighbour_num=0)), ("neighbour_num_big", dict(neighbour_num=5))], ()),
     ("kasf_op_gcn_bwd", dict(dtype=0, batch=1, n_frames=4, mode=1), _GCN, ()),
