@@ -875,11 +875,10 @@ int kasf_stream_track_emit(const float* pred, int32_t flip, const int64_t* count
  * a call are distinct; an id outside [0, S) makes the row a copy-through that touches no state.
  *
  * kasf_one_euro_tracked: x, out [streams * R][J][Ct]; ids, slot, born [streams][track_slots] int32 and count_b [streams] int32 are kasf_sort_update's outputs of
- * this tick, read in place.  Row k of stream b is resolved by kasf_stream_track_front's rule to the word: count_b is clamped to [0, track_slots]; the row takes
- * track row r = count_b - 1 - k (rows_mode = KASF_ROWS_PERSONS) or r = k (KASF_ROWS_TRACKS); it is VALID iff k < min(count_b, R), id = ids[b][r] >= 1,
- * s = slot[b][r] is in [0, track_slots) and no lower row of the same stream that passes these three tests has the same s (the lowest row wins a duplicate).  For a
- * valid row, g = b * track_slots + s; when owner[g] != id or born[b][r] != 0 the slot restarts -- every last[g][:] = -1, owner[g] = id -- and then the rule above
- * runs.  An invalid row touches no state and is copied through.  row_slot [streams * R] int32 (may be NULL) receives g, or -1.
+ * this tick, read in place.  Row k of stream b is resolved by the tick rule of kasf_stream_track_front above -- its track row r, whether it is VALID, its entry
+ * g = b * track_slots + s and step 1's test are stated there, once, and computed by the same code.  When step 1's test holds the slot restarts -- every
+ * last[g][:] = -1, owner[g] = id -- and then the rule above runs.  An invalid row touches no state and is copied through.  row_slot [streams * R] int32 (may be
+ * NULL) receives g, or -1.
  *
  * kasf_one_euro_tracks: recorded tracks packed as x, out [N][J][Ct], track t = rows offsets[t] .. offsets[t + 1] - 1 (device int64 [P + 1], as
  * kasf_lift_windows_ragged takes them; clamped into [0, N]).  Each track starts from an empty state and tick = frame index within the track; the state stays in
@@ -939,7 +938,8 @@ int kasf_one_euro_tracks(const float* x, const int64_t* offsets, int64_t N, int3
  * a call are distinct; an id outside [0, S) makes the row a copy-through that touches no state.  One launch, one wavefront per row.
  *
  * kasf_bone_tracked: poses, out [streams * R][17][3]; ids, slot, born, count_b, rows_mode, R, owner [streams * track_slots] (initially 0) and row_slot (may be
- * NULL) are kasf_one_euro_tracked's, and a row's slot, validity and restart are resolved by its rule to the word.  A slot that restarts gets cnt[g][:] = 0 and
+ * NULL) are kasf_one_euro_tracked's, and a row's slot, validity and restart are resolved by the tick rule of kasf_stream_track_front, as there (stated once,
+ * computed by the same code).  A slot that restarts gets cnt[g][:] = 0 and
  * owner[g] = id whatever the frame holds; then rule 5 runs.
  *
  * P = 0 (median), N = 0 (apply) or K = 0 does nothing.  Error 2, before a device or a device pointer is touched: N or P negative, N >= 2^31; K or S negative,

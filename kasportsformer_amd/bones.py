@@ -16,6 +16,9 @@ bones their mean.  A length of 0 in a table means "leave this bone alone"; a fra
 Everything runs on the device and nothing is read back: two launches for the medians (lengths, then a radix select per track and bone), one for the walk, one
 per ``push``.  There is no host path.  The live form is a running mean over the first ``window`` frames and an exponential average after them, not a median,
 and ``window`` is a starting point, not tuned on footage.
+
+The tracker-driven filter resolves its rows by ``TrackedLifter``'s rule, one device function (``csrc/tracked_rows.h``); its slot, stream and recorded-track
+arguments go through ``_tracks.py``, as ``OneEuroFilter``'s and the lifters' do.
 """
 from __future__ import annotations
 
@@ -24,7 +27,7 @@ import torch
 
 from . import _args, _lib
 from ._args import index_in
-from .smooth import check_filter_args, check_push, check_slot_ids, check_stream_ids
+from ._tracks import check_push, filter_slots, pack, recorded_parts, reset_filter, split, track_offsets
 
 BONES, MAX_WINDOW = 16, 1 << 20
 BONE_PARENTS = (0, 1, 2, 0, 4, 5, 0, 7, 8, 9, 8, 11, 12, 8, 14, 15)       # bone k joins joint k + 1 to BONE_PARENTS[k]
@@ -45,37 +48,19 @@ def _bool(v, who: str, name: str) -> bool:
 
 
 def _tracks(poses, offsets, who: str):
-    """``smooth_tracks``' four input forms -> (the parts where they are, offsets int64 [P+1] on the host, as_list); everything that can be refused
-    without a device is refused here, before the device is resolved."""
-    as_list = offsets is None and isinstance(poses, (list, tuple))
-    parts = [_pose_rows(a, who) for a in poses] if as_list else [_pose_rows(poses, who)]
-    for a in parts:
-        if a.dim() > (3 if as_list or offsets is not None else 4):
-            raise ValueError(f"{who}: expected {'tracks of [N,17,3]' if as_list else 'packed tracks [sum N_i,17,3]' if offsets is not None else '[N,17,3] or [P,N,17,3]'}, "
-                             f"got {tuple(a.shape)}")
-    if offsets is not None:
-        n = int(parts[0].shape[0])
-        off = np.asarray(offsets.detach().cpu() if isinstance(offsets, torch.Tensor) else offsets)
-        if off.ndim != 1 or off.size < 1 or off.dtype.kind not in "iu" or off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] != n:
-            raise ValueError(f"{who}: offsets must be integers [P+1] from 0 up to the packed length {n}, non-decreasing")
-        off = off.astype(np.int64)
-    elif as_list:
-        off = np.cumsum([0] + [a.shape[0] for a in parts], dtype=np.int64)
-    else:
-        lead = tuple(parts[0].shape[:-2])
-        P, n = (1, lead[0]) if len(lead) == 1 else lead
-        off = np.arange(P + 1, dtype=np.int64) * n
+    """The four input forms (``_tracks.recorded_parts``) -> (the parts where they are, offsets int64 [P+1] on the host, as_list); everything that can be
+    refused without a device is refused here, before the device is resolved."""
+    parts, as_list = recorded_parts(poses, offsets, who, lambda a: _pose_rows(a, who), "17,3", True)
+    off = track_offsets(parts, offsets, as_list, who)
     if int(off[-1]) >= 2 ** 31:
         raise ValueError(f"{who}: at most 2^31 - 1 frames in a call, got {int(off[-1])}")
     return parts, off, as_list
 
 
 def _packed(parts, as_list, dev) -> torch.Tensor:
-    if as_list:
-        if not parts:
-            return torch.empty((0, 17, 3), dtype=torch.float32, device=dev)
-        return torch.cat([a.to(dev) for a in parts]) if any(a.is_cuda for a in parts) else torch.cat(parts).to(dev)
-    return parts[0].to(dev).contiguous().view(-1, 17, 3)
+    if as_list and not parts:
+        return torch.empty((0, 17, 3), dtype=torch.float32, device=dev)
+    return pack(parts, as_list, dev).view(-1, 17, 3)
 
 
 def _medians(lib, packed, off_d, N: int, P: int, dev, want_counts: bool):
@@ -132,10 +117,7 @@ def fix_bone_lengths(poses, offsets=None, *, lengths=None, symmetric: bool = Fal
         with torch.cuda.device(dev):
             _lib.check(lib.kasf_bone_apply(packed.data_ptr(), off_d.data_ptr(), N, P, table.data_ptr(), int(table.dim() == 2), int(symmetric), out.data_ptr(),
                                            _args.stream()))
-    if as_list:
-        result = [out[a:b] for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
-    else:
-        result = out.view(parts[0].shape)
+    result = split(out, off) if as_list else out.view(parts[0].shape)
     return (result, table) if return_lengths else result
 
 
@@ -152,8 +134,7 @@ class BoneLengthFilter:
     def __init__(self, slots=None, window: int = 64, symmetric: bool = False, device=None, *, streams=None, track_slots=None, rows: str = "persons",
                  num_person: int = 1):
         who = "BoneLengthFilter"
-        (self.tracked, self.slots, _, _, _, self.streams, self.track_slots, self._rows_mode, self.R) = check_filter_args(
-            slots, 17, 3, False, streams, track_slots, rows, num_person, who)
+        self.tracked, self.slots, self.streams, self.track_slots, self._rows_mode, self.R = filter_slots(slots, streams, track_slots, rows, num_person, who)
         self.rows = rows if self.tracked else None
         self.window = index_in(window, who, "window", 1, MAX_WINDOW)
         self.symmetric = _bool(symmetric, who, "symmetric")
@@ -166,27 +147,7 @@ class BoneLengthFilter:
     def reset(self, slots=None, *, streams=None) -> None:
         """The slots (a filter built with ``slots=``; None: all) or every slot of the streams (a tracker-driven filter; None: all; what must accompany
         ``SortTracker.reset`` of the same streams) start again: their counts, and their owners, become 0."""
-        who = "BoneLengthFilter.reset"
-        if self.tracked:
-            if slots is not None:
-                raise TypeError(f"{who}: a tracker-driven filter is reset by streams=, not by slots")
-            idx = check_stream_ids(streams, self.streams, who)
-            if idx is None:
-                self._cnt.zero_()
-                self._owner.zero_()
-                return
-            cnt, owner = self._cnt.view(self.streams, self.track_slots, BONES), self._owner.view(self.streams, self.track_slots)
-            for b in idx:
-                cnt[b].zero_()
-                owner[b].zero_()
-            return
-        if streams is not None:
-            raise TypeError(f"{who}: a filter built with slots= is reset by slots, not by streams=")
-        ids = check_slot_ids(slots, self.slots, who)
-        if ids is None:
-            self._cnt.zero_()
-        elif ids.size:
-            self._cnt.index_fill_(0, torch.from_numpy(ids.astype(np.int64)).to(self.device), 0)
+        reset_filter(self, "BoneLengthFilter.reset", slots, streams, "_cnt", 0)
 
     def push(self, poses, track=None, *, slots=None) -> torch.Tensor:
         """One tick.  A filter built with ``slots=``: ``poses`` [slots,17,3] (every slot, in order) or, with ``slots=`` (distinct host integers), [K,17,3] for

@@ -1,6 +1,6 @@
 // Constant limb lengths per player (kasf.h, kasf_bone_*): the per-track lower median of every bone's length (k_bone_lengths, k_bone_select), the walk from the
 // root that re-imposes a table of lengths on every frame (k_bone_apply), and the live form with a running mean per slot in device memory, its slot named by the
-// host (k_bone_push) or read from the tracker's TrackResult (k_bone_tracked, kasf_one_euro_tracked's row rule restated).  bone_walk / bone_symmetric are the one
+// host (k_bone_push) or read from the tracker's TrackResult (k_bone_tracked, by tracked_rows.h's rule).  bone_walk / bone_symmetric are the one
 // definition of the walk; every fp32 line is the rounded operation(s) kasf.h names, left to right (-ffp-contract=off, correctly rounded divide and square root).
 //
 // The two frame kernels move 204 B per frame in (and out): a workgroup stages BONE_TILE frames in LDS as k_pose.hip does -- global loads and stores are one
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(SELECT_THREADS) void k_bone_select(const float* __r
     const int lane = threadIdx.x & 63;
     for (int64_t item = blockIdx.x; item < (int64_t)P * 16; item += gridDim.x) {
         const int p = (int)(item >> 4), k = (int)(item & 15);
-        const int64_t f0 = one_euro_clamp(offsets[p], 0, N), f1 = one_euro_clamp(offsets[p + 1], f0, N);
+        const int64_t f0 = lift_clamp(offsets[p], 0, N), f1 = lift_clamp(offsets[p + 1], f0, N);
         const float* v = scratch + (int64_t)k * N;
         unsigned prefix = 0, mask = 0;                          // the median's bits found so far, and which bits those are
         int rank = 0, n = 0;                                    // the rank wanted among the values that match prefix under mask
@@ -290,8 +290,7 @@ __global__ __launch_bounds__(64) void k_bone_push(const float* __restrict__ x, c
     }
 }
 
-// x, out [B * R][17][3]; the row's slot from the TrackResult arrays by kasf_one_euro_tracked's rule, restated line by line from k_smooth.hip: count_b clamped,
-// the track row by rows_mode, id >= 1, slot in [0, S_t), the lowest row of a slot wins, restart when the owner differs or born is set.  row_slot may be NULL.
+// x, out [B * R][17][3]; the row's slot from the TrackResult arrays by kasf_stream_track_front's rule (tracked_rows.h).  row_slot may be NULL.
 __global__ __launch_bounds__(64) void k_bone_tracked(const float* __restrict__ x, const int* __restrict__ ids, const int* __restrict__ slot,
                                                      const int* __restrict__ born, const int* __restrict__ count_b, int B, int S_t, int rows_mode, int R, int window,
                                                      int symmetric, float* len, int* cnt, int* owner, float* __restrict__ out, int* __restrict__ row_slot) {
@@ -299,28 +298,13 @@ __global__ __launch_bounds__(64) void k_bone_tracked(const float* __restrict__ x
     const int64_t n_rows = (int64_t)B * R;
     for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
         const int b = (int)(row / R), k = (int)(row - (int64_t)b * R);
-        const int cb = (int)one_euro_clamp(count_b[b], 0, S_t);
-        const int* ids_b = ids + (int64_t)b * S_t;
-        const int* slot_b = slot + (int64_t)b * S_t;
-        bool valid = k < cb;
-        const int r = one_euro_track_row(rows_mode, cb, k, S_t);
-        const int id = ids_b[r], s = slot_b[r];
-        valid = valid && id >= 1 && s >= 0 && s < S_t;
-        bool hit = false;                                          // the lower rows of this stream, one per lane (k < cb <= S_t <= 64)
-        if (valid && (int)threadIdx.x < k) {
-            const int r2 = one_euro_track_row(rows_mode, cb, (int)threadIdx.x, S_t);
-            hit = ids_b[r2] >= 1 && slot_b[r2] == s;
-        }
-        if (__syncthreads_or(hit ? 1 : 0)) valid = false;
-        const int64_t g = (int64_t)b * S_t + (valid ? s : 0);
-        bool restart = false;
-        if (valid) restart = owner[g] != id || born[(int64_t)b * S_t + r] != 0;     // this workgroup alone touches entry g in this launch
+        const TrackedRow tr = tracked_row(ids, slot, born, count_b, b, k, S_t, rows_mode, owner);      // k < R by construction
         __syncthreads();                                           // every lane has the old owner before lane 0 stores the new one
         if (threadIdx.x == 0) {
-            if (valid && restart) owner[g] = id;
-            if (row_slot) row_slot[row] = valid ? (int)g : -1;
+            if (tr.restart) owner[tr.g] = tr.id;
+            if (row_slot) row_slot[row] = tr.valid ? (int)tr.g : -1;
         }
-        bone_live_row(sh, x + row * 51, out + row * 51, valid ? g : -1, restart, window, symmetric, len, cnt);
+        bone_live_row(sh, x + row * 51, out + row * 51, tr.valid ? tr.g : -1, tr.restart, window, symmetric, len, cnt);
     }
 }
 

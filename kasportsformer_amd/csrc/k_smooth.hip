@@ -60,7 +60,7 @@ __global__ __launch_bounds__(64) void k_one_euro_push(const float* __restrict__ 
     }
 }
 
-// x, out [B * R][J][Ct]; the row's slot from the TrackResult arrays by kasf_stream_track_front's rule; row_slot may be NULL.
+// x, out [B * R][J][Ct]; the row's slot from the TrackResult arrays by kasf_stream_track_front's rule (tracked_rows.h); row_slot may be NULL.
 template <int C>
 __global__ __launch_bounds__(64) void k_one_euro_tracked(const float* __restrict__ x, const int* __restrict__ ids, const int* __restrict__ slot,
                                                          const int* __restrict__ born, const int* __restrict__ count_b, int B, int S_t, int rows_mode, int R, int J,
@@ -70,26 +70,12 @@ __global__ __launch_bounds__(64) void k_one_euro_tracked(const float* __restrict
     const int64_t n_rows = (int64_t)B * R;
     for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
         const int b = (int)(row / R), k = (int)(row - (int64_t)b * R);
-        const int cb = (int)one_euro_clamp(count_b[b], 0, S_t);
-        const int* ids_b = ids + (int64_t)b * S_t;
-        const int* slot_b = slot + (int64_t)b * S_t;
-        bool valid = k < cb;                                       // k < R by construction
-        const int r = one_euro_track_row(rows_mode, cb, k, S_t);
-        const int id = ids_b[r], s = slot_b[r];
-        valid = valid && id >= 1 && s >= 0 && s < S_t;
-        // the lower rows of this stream, one per lane (k < cb <= S_t <= 64): the lowest row of a slot wins
-        bool hit = false;
-        if (valid && (int)threadIdx.x < k) {
-            const int r2 = one_euro_track_row(rows_mode, cb, (int)threadIdx.x, S_t);
-            hit = ids_b[r2] >= 1 && slot_b[r2] == s;
-        }
-        if (__syncthreads_or(hit ? 1 : 0)) valid = false;
-        const int64_t g = (int64_t)b * S_t + (valid ? s : 0);
-        bool restart = false;
-        if (valid) restart = owner[g] != id || born[(int64_t)b * S_t + r] != 0;     // this workgroup alone touches entry g in this launch
+        const TrackedRow tr = tracked_row(ids, slot, born, count_b, b, k, S_t, rows_mode, owner);      // k < R by construction
+        const bool valid = tr.valid, restart = tr.restart;
+        const int64_t g = tr.g;
         __syncthreads();                                           // every lane has the old owner before lane 0 stores the new one
         if (threadIdx.x == 0) {
-            if (valid && restart) owner[g] = id;
+            if (restart) owner[g] = tr.id;
             if (row_slot) row_slot[row] = valid ? (int)g : -1;
         }
         const float* xr = x + row * J * Ct;
@@ -112,7 +98,7 @@ __global__ __launch_bounds__(64) void k_one_euro_tracks(const float* __restrict_
                                                         KasfOneEuro p, float* __restrict__ out) {
     const int Ct = C + (has_score ? 1 : 0);
     for (int t = blockIdx.x; t < P; t += gridDim.x) {
-        const int64_t f0 = one_euro_clamp(offsets[t], 0, N), f1 = one_euro_clamp(offsets[t + 1], f0, N);
+        const int64_t f0 = lift_clamp(offsets[t], 0, N), f1 = lift_clamp(offsets[t + 1], f0, N);
         for (int j = threadIdx.x; j < J; j += 64) {
             float xh[C], dxh[C], o[C];
 #pragma unroll
@@ -123,7 +109,7 @@ __global__ __launch_bounds__(64) void k_one_euro_tracks(const float* __restrict_
                 float in[kAhead][C + 1];
 #pragma unroll
                 for (int u = 0; u < kAhead; ++u) {
-                    const float* xj = x + (one_euro_clamp(fb + u, f0, f1 - 1) * J + j) * Ct;
+                    const float* xj = x + (lift_clamp(fb + u, f0, f1 - 1) * J + j) * Ct;
 #pragma unroll
                     for (int c = 0; c < C; ++c) in[u][c] = xj[c];
                     in[u][C] = has_score ? xj[C] : 0.0f;

@@ -2,6 +2,8 @@
 // for slot ids the host uploaded, here for slots, births and deaths read from the TrackResult of k_track.hip -- one launch per tick in front of the model's
 // forward, one behind it, nothing read back.
 //
+// The row rule below is tracked_rows.h's, the one statement the two filters' tracked kernels apply as well.
+//
 // State per stream b and tracker slot s, g = b * S_t + s: ring [B * S_t, T, 17, 3] and count [B * S_t] as k_lift.hip keeps them, owner [B * S_t] the track id
 // whose history the slot holds.  Row k of stream b takes track row r = count_b - 1 - k (rows_mode 0, the order of TrackResult.persons) or r = k (rows_mode 1,
 // the order of TrackResult.boxes), count_b clamped to [0, S_t].  The row is valid iff k < min(count_b, R), id = ids[b][r] >= 1, s = slot[b][r] in [0, S_t) and no
@@ -15,9 +17,6 @@
 #include "kernels.h"
 
 namespace {
-
-// Track row of row k of a stream with cb emitted tracks, k < cb.
-__device__ inline int track_row(int rows_mode, int cb, int k) { return rows_mode == KASF_ROWS_PERSONS ? cb - 1 - k : k; }
 
 // Float e of a clip of the slot whose count is k (>= 1, the new frame included) and window length L.  The window's newest frame is read from the caller's
 // frame, the older ones from ring positions this launch does not write.
@@ -38,26 +37,13 @@ __global__ __launch_bounds__(256) void k_stream_track_front(const float* __restr
     const int clip_floats = T * 51, halves = flip ? 2 : 1;
     for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
         const int b = (int)(row / R), k = (int)(row - (int64_t)b * R);
-        const int cb = (int)lift_clamp(count_b[b], 0, S_t);
-        const int* ids_b = ids + (int64_t)b * S_t;
-        const int* slot_b = slot + (int64_t)b * S_t;
-        bool valid = k < cb;                                       // k < R by construction
-        const int r = (int)lift_clamp(track_row(rows_mode, cb, k), 0, S_t - 1);
-        const int id = ids_b[r], s = slot_b[r];
-        valid = valid && id >= 1 && s >= 0 && s < S_t;
-        // the lower rows of this stream, one per thread (k < cb <= S_t <= 64 where it matters): the lowest row of a slot wins
-        bool hit = false;
-        if (valid && (int)threadIdx.x < k) {
-            const int r2 = (int)lift_clamp(track_row(rows_mode, cb, (int)threadIdx.x), 0, S_t - 1);
-            hit = ids_b[r2] >= 1 && slot_b[r2] == s;
-        }
-        if (__syncthreads_or(hit ? 1 : 0)) valid = false;
-        const int64_t g = (int64_t)b * S_t + (valid ? s : 0);
+        const TrackedRow tr = tracked_row(ids, slot, born, count_b, b, k, S_t, rows_mode, owner);      // k < R by construction
+        const bool valid = tr.valid;
+        const int64_t g = tr.g;
         int64_t k0 = 0;
-        if (valid) {                                               // this workgroup alone touches entry g in this launch
+        if (valid && !tr.restart) {                                // this workgroup alone touches entry g in this launch
             k0 = count[g];
             if (k0 < 0) k0 = 0;
-            if (owner[g] != id || born[(int64_t)b * S_t + r] != 0) k0 = 0;
         }
         __syncthreads();                                           // every thread has the old count and owner before one thread stores the new ones
         const float* frame = frames + row * 51;
@@ -66,7 +52,7 @@ __global__ __launch_bounds__(256) void k_stream_track_front(const float* __restr
             if (threadIdx.x < 51) ring_slot[(k0 % T) * 51 + threadIdx.x] = frame[threadIdx.x];
             if (threadIdx.x == 0) {
                 count[g] = k0 + 1;
-                owner[g] = id;
+                owner[g] = tr.id;
             }
         }
         if (threadIdx.x == 0) row_slot[row] = valid ? (int)g : -1;

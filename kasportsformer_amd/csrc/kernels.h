@@ -208,10 +208,7 @@ void kasf_launch_stream_emit(hipStream_t s, const float* pred, int flip, const i
 
 // ---- k_stream_track.hip: the stream lifter's slots driven by a TrackResult on the device (kasf.h, kasf_stream_track_*): B streams of S_t tracker slots, state
 // ring [B*S_t,T,17,3] / count [B*S_t] / owner [B*S_t], R rows per stream in the order rows_mode names; arguments as checked by the entry points ----
-#ifndef KASF_ROWS_PERSONS
-#define KASF_ROWS_PERSONS 0
-#define KASF_ROWS_TRACKS 1
-#endif
+#include "tracked_rows.h"   // KASF_ROWS_* and the row rule the three tracker-driven kernels share
 void kasf_launch_stream_track_front(hipStream_t s, const float* frames, const int* ids, const int* slot, const int* born, const int* count_b, int B, int S_t,
                                     int rows_mode, int R, int T, float* ring, int64_t* count, int* owner, const float* width, const float* height,
                                     const int* resample_tab, int flip, float* x, int* row_slot);

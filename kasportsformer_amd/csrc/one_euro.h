@@ -1,5 +1,5 @@
-// The One-Euro step (Casiez, Roussel, Vogel, CHI 2012) and the row rule of the tracker-driven entry that the three kernels of k_smooth.hip share
-// (kasf.h, kasf_one_euro_*): one definition of "usable", of the tick distance, of the hold and of the update, so that "a recorded track equals push called
+// The One-Euro step (Casiez, Roussel, Vogel, CHI 2012) that the three kernels of k_smooth.hip share (kasf.h, kasf_one_euro_*; the row rule of the
+// tracker-driven entry is tracked_rows.h's): one definition of "usable", of the tick distance, of the hold and of the update, so that "a recorded track equals push called
 // frame by frame" holds bit for bit.  The library is built with -ffp-contract=off and a correctly rounded divide: every line below is the rounded fp32
 // operation(s) kasf.h names, left to right.
 // Plain C++: HIP device code in the library, g++ behind the stand-in hip/hip_runtime.h of tests/host_emul/ in the CPU tests.
@@ -7,18 +7,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#ifndef KASF_ROWS_PERSONS
-#define KASF_ROWS_PERSONS 0
-#define KASF_ROWS_TRACKS 1
-#endif
-
 // kasf_one_euro_params of kasf.h as the kernels receive it: by value in the launch arguments
 struct KasfOneEuro {
     float dt, min_cutoff, d_cutoff, beta, min_score;
     int max_hold;
 };
-
-__device__ inline int64_t one_euro_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // One joint of one row.  x: the joint's Ct = C + has_score input values; xh, dxh: its estimate and derivative (read only when last >= 0); last: the tick of its
 // last update, < 0 for none.  Writes the C filtered channels to out (the score channel is the caller's copy) and returns whether xh / dxh / last changed: they
@@ -72,9 +65,4 @@ __device__ inline bool one_euro_joint(const KasfOneEuro& p, bool has_score, cons
     }
     last = tick;
     return true;
-}
-
-// kasf_stream_track_front's row rule, restated: the track row of row k of a stream with cb emitted tracks (cb already clamped to [0, S_t]), clamped into the arrays.
-__device__ inline int one_euro_track_row(int rows_mode, int cb, int k, int S_t) {
-    return (int)one_euro_clamp(rows_mode == KASF_ROWS_PERSONS ? cb - 1 - k : k, 0, S_t - 1);
 }

@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from . import _args, _lib
+from ._tracks import float_rows, pack, recorded_parts, split, track_offsets
 from .pose import check_layout, convert_frames, poses_to_world
 
 
@@ -98,25 +99,8 @@ def _model_device(model, who: str = "lift_track") -> torch.device:
     return dev
 
 
-def _as_tensor(keypoints, device, who: str) -> torch.Tensor:
-    """float32 keypoints as a tensor on the host or on ``device``, not moved (a numpy array is shared, not copied)."""
-    if isinstance(keypoints, np.ndarray):
-        if keypoints.dtype != np.float32:
-            raise TypeError(f"{who}: keypoints must be float32, got {keypoints.dtype}")
-        return torch.from_numpy(np.ascontiguousarray(keypoints))
-    if isinstance(keypoints, torch.Tensor):
-        if keypoints.dtype != torch.float32:
-            raise TypeError(f"{who}: keypoints must be float32, got {keypoints.dtype}")
-        if keypoints.is_cuda and keypoints.device != device:
-            raise RuntimeError(f"{who}: keypoints are on {keypoints.device}, the model on {device}")
-        if not keypoints.is_cuda and keypoints.device.type != "cpu":
-            raise RuntimeError(f"{who}: keypoints on unsupported device {keypoints.device}")
-        return keypoints.detach()
-    raise TypeError(f"{who}: keypoints must be a numpy array or a torch tensor, got {type(keypoints).__name__}")
-
-
 def _track(keypoints, device) -> torch.Tensor:
-    kp = _as_tensor(keypoints, device, "lift_track")
+    kp = float_rows(keypoints, device, "lift_track")
     if kp.dim() not in (3, 4) or tuple(kp.shape[-2:]) != (17, 3):
         raise ValueError(f"lift_track: expected keypoints [N,17,3] or [P,N,17,3], got {tuple(kp.shape)}")
     return kp.to(device).contiguous()            # a copy when it comes from the host; on the device the kernels only read it
@@ -234,21 +218,8 @@ def lift_tracks(model, tracks, width, height, *, stride=None, flip: bool = True,
     device = _model_device(model, "lift_tracks")
     T = int(model.n_frames)
     stride = _stride(T, stride, max_windows, "lift_tracks")
-    if offsets is None:
-        parts = [_as_tensor(a, device, "lift_tracks") for a in tracks]
-        for a in parts:
-            if a.dim() != 3 or tuple(a.shape[1:]) != (17, 3):
-                raise ValueError(f"lift_tracks: expected tracks of [N,17,3], got {tuple(a.shape)}")
-        off = np.cumsum([0] + [a.shape[0] for a in parts], dtype=np.int64)
-    else:
-        packed = _as_tensor(tracks, device, "lift_tracks")
-        if packed.dim() != 3 or tuple(packed.shape[1:]) != (17, 3):
-            raise ValueError(f"lift_tracks: expected packed tracks [sum N_i,17,3], got {tuple(packed.shape)}")
-        off = np.asarray(offsets.detach().cpu() if isinstance(offsets, torch.Tensor) else offsets)
-        if (off.ndim != 1 or off.size < 1 or off.dtype.kind not in "iu" or off[0] != 0 or np.any(np.diff(off) < 0)
-                or off[-1] != packed.shape[0]):
-            raise ValueError(f"lift_tracks: offsets must be integers [P+1] from 0 up to the packed length {packed.shape[0]}, non-decreasing")
-        off = off.astype(np.int64)
+    parts, as_list = recorded_parts(tracks, offsets, "lift_tracks", lambda a: float_rows(a, device, "lift_tracks"), "17,3", False, exact=True)
+    off = track_offsets(parts, offsets, as_list, "lift_tracks")
     P = len(off) - 1
     w32, h32 = _per_row(width, P, "width", "lift_tracks", "track"), _per_row(height, P, "height", "lift_tracks", "track")
     lengths = np.diff(off)
@@ -259,15 +230,9 @@ def lift_tracks(model, tracks, width, height, *, stride=None, flip: bool = True,
     if (lib.kasf_lift_ragged_plan(lengths.ctypes.data, P, T, stride, c_first.ctypes.data) != windows
             or not np.array_equal(c_first, win_first)):
         raise _lib.KasfError("lift_tracks: the library's window plan disagrees with ragged_plan (stale build?)")
-    if offsets is None:
-        if P == 0:
-            return []
-        if any(a.is_cuda for a in parts):
-            packed = torch.cat([a.to(device) for a in parts])
-        else:
-            packed = torch.cat(parts).to(device)                  # packed on the host, one upload
-    else:
-        packed = packed.to(device).contiguous()
+    if as_list and P == 0:
+        return []
+    packed = pack(parts, as_list, device)
     poses = torch.empty((frames, 17, 3), dtype=torch.float32, device=device)
     if windows > 0:
         off_d, wf_d, w_d, h_d, r_d, fp_d = _upload(device, off, win_first, w32, h32, resample, first_pos)
@@ -281,9 +246,7 @@ def lift_tracks(model, tracks, width, height, *, stride=None, flip: bool = True,
             pred = _forward_windows(model, x, windows, halves, int(max_windows))
             _lib.check(lib.kasf_lift_stitch_ragged(pred.data_ptr(), int(flip), off_d.data_ptr(), wf_d.data_ptr(), P, frames, windows, T, stride,
                                                    fp_d.data_ptr(), poses.data_ptr(), _args.stream()))
-    if offsets is not None:
-        return poses
-    return [poses[a:b] for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
+    return split(poses, off) if as_list else poses
 
 
 class _KeypointUnpickler(pickle.Unpickler):

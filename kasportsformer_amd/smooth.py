@@ -20,6 +20,9 @@ The state (``xhat``, ``dxhat`` [S,J,C], ``last`` [S,J] int64, ``owner`` [S] int3
 integer, +1 per push (``ticks=n`` for a push after n - 1 dropped frames).  Nothing synchronises with the host and nothing is read back: one launch per push.
 There is no host path.  The parameters are in the units of the data (pixels for keypoints, model units for poses); the defaults are a starting point, not
 tuned on footage.  Per-person normalisation of ``beta`` is out of scope.
+
+A tracker-driven filter resolves its rows by ``TrackedLifter``'s rule, which is one device function (``csrc/tracked_rows.h``); slot ids, stream indices, the
+forms of recorded tracks and ``reset`` are handled by ``_tracks.py``, the layer the lifters and ``BoneLengthFilter`` use as well.
 """
 from __future__ import annotations
 
@@ -30,8 +33,8 @@ import torch
 
 from . import _args, _lib
 from ._args import index_in
-from .tracked import ROWS, check_tracked_tick
-from .track import MAX_PERSONS, MAX_SLOTS, MAX_STREAMS
+from ._tracks import check_push, filter_slots, pack, recorded_parts, reset_filter, split, track_offsets
+from ._tracks import slot_ids as check_slot_ids, stream_ids as check_stream_ids     # noqa: F401 -- the names these two are known by here
 
 MAX_JOINTS, MAX_CHANNELS, MAX_HOLD = 256, 4, 1 << 20       # J, C and max_hold of the kasf_one_euro_* entries
 _LO, _HI = np.float32(1e-6), np.float32(1e6)
@@ -65,62 +68,8 @@ def check_filter_args(slots, joints, channels, score, streams, track_slots, rows
     Cn = index_in(channels, who, "channels", 1, MAX_CHANNELS)
     if not isinstance(score, (bool, np.bool_)):
         raise TypeError(f"{who}: score must be a bool, got {type(score).__name__}")
-    Ct = Cn + (1 if score else 0)
-    tracked = streams is not None or track_slots is not None
-    if tracked and slots is not None:
-        raise ValueError(f"{who}: give slots= (host slot ids, as StreamLifter) or streams= and track_slots= (a TrackResult, as TrackedLifter), not both")
-    if not tracked:
-        if slots is None:
-            raise ValueError(f"{who}: give slots= (host slot ids, as StreamLifter) or streams= and track_slots= (a TrackResult, as TrackedLifter)")
-        S = index_in(slots, who, "slots", 1, 2 ** 31 - 1)
-        return False, S, J, Cn, Ct, None, None, None, None
-    if rows not in ROWS:
-        raise ValueError(f"{who}: rows must be one of {ROWS}, got {rows!r}")
-    streams = index_in(1 if streams is None else streams, who, "streams", 1, MAX_STREAMS)
-    track_slots = index_in(32 if track_slots is None else track_slots, who, "track_slots", 1, MAX_SLOTS)
-    num_person = index_in(num_person, who, "num_person", 1, MAX_PERSONS)
-    R = num_person if rows == "persons" else track_slots
-    return True, streams * track_slots, J, Cn, Ct, streams, track_slots, (_lib.ROWS_PERSONS if rows == "persons" else _lib.ROWS_TRACKS), R
-
-
-def _rows_tensor(x, device, who: str) -> torch.Tensor:
-    """float32 rows as a tensor on the host or on ``device``, not moved (``_args.as_tensor``; a tensor on another GPU is refused, as the lifters refuse it)."""
-    t = _args.as_tensor(x, who, "rows", _args.FLOAT32)
-    if t.is_cuda and t.device != device:
-        raise RuntimeError(f"{who}: rows are on {t.device}, the filter on {device}")
-    return t
-
-
-def check_slot_ids(slots, S: int, who: str):
-    """``slots=`` of a call -> distinct int32 ids [K] in [0, S) on the host (None: every slot in order), refused as ``StreamLifter`` refuses them."""
-    if slots is None:
-        return None
-    if isinstance(slots, torch.Tensor):
-        if slots.is_cuda:
-            raise RuntimeError(f"{who}: slot ids are host integers, got a tensor on {slots.device}")
-        slots = slots.numpy()
-    ids = np.asarray(slots)
-    if ids.size == 0:
-        ids = ids.astype(np.int64)
-    if ids.ndim != 1 or ids.dtype.kind not in "iu":
-        raise ValueError(f"{who}: slots must be a 1-D sequence of integers, got shape {ids.shape} {ids.dtype}")
-    if ids.size and (ids.min() < 0 or ids.max() >= S):
-        raise ValueError(f"{who}: slot ids must be in [0, {S}), got {ids.tolist()}")
-    if len(np.unique(ids)) != ids.size:
-        raise ValueError(f"{who}: slot ids must be distinct, got {ids.tolist()}")
-    return ids.astype(np.int32)
-
-
-def check_stream_ids(streams, B: int, who: str):
-    """``streams=`` of ``reset`` -> a list of stream indices (None: all of them), refused as ``TrackedLifter.reset`` refuses them."""
-    if streams is None:
-        return None
-    idx = np.atleast_1d(np.asarray(streams))
-    if idx.dtype.kind not in "iu" or idx.ndim != 1:
-        raise TypeError(f"{who}: streams must be an index or a sequence of indices, got {streams!r}")
-    if idx.size and (idx.min() < 0 or idx.max() >= B):
-        raise ValueError(f"{who}: streams must be in [0, {B}), got {idx.min()} .. {idx.max()}")
-    return idx.tolist()
+    tracked, S, *driven = filter_slots(slots, streams, track_slots, rows, num_person, who)
+    return (tracked, S, J, Cn, Cn + (1 if score else 0), *driven)
 
 
 class OneEuroFilter:
@@ -150,27 +99,7 @@ class OneEuroFilter:
     def reset(self, slots=None, *, streams=None) -> None:
         """The slots (a filter built with ``slots=``; None: all) or every slot of the streams (a tracker-driven filter; None: all; what must accompany
         ``SortTracker.reset`` of the same streams) start again: their ``last`` entries become -1 and their owners 0.  ``xhat`` needs no clearing."""
-        who = "OneEuroFilter.reset"
-        if self.tracked:
-            if slots is not None:
-                raise TypeError(f"{who}: a tracker-driven filter is reset by streams=, not by slots")
-            idx = check_stream_ids(streams, self.streams, who)
-            if idx is None:
-                self._last.fill_(-1)
-                self._owner.zero_()
-                return
-            last, owner = self._last.view(self.streams, self.track_slots, self.joints), self._owner.view(self.streams, self.track_slots)
-            for b in idx:
-                last[b].fill_(-1)
-                owner[b].zero_()
-            return
-        if streams is not None:
-            raise TypeError(f"{who}: a filter built with slots= is reset by slots, not by streams=")
-        ids = check_slot_ids(slots, self.slots, who)
-        if ids is None:
-            self._last.fill_(-1)
-        elif ids.size:
-            self._last.index_fill_(0, torch.from_numpy(ids.astype(np.int64)).to(self.device), -1)
+        reset_filter(self, "OneEuroFilter.reset", slots, streams, "_last", -1)
 
     def push(self, x, track=None, *, slots=None, ticks: int = 1) -> torch.Tensor:
         """One tick.  A filter built with ``slots=``: ``x`` [slots,J,Ct] (every slot, in order) or, with ``slots=`` (distinct host integers), [K,J,Ct] for
@@ -199,30 +128,6 @@ class OneEuroFilter:
         return out
 
 
-def check_push(f, x, track, slots, ticks, who: str = "OneEuroFilter.push"):
-    """Everything ``push`` can refuse without a launch, for a filter (or any object) with ``tracked``, ``slots``, ``joints``, ``_Ct``, ``streams``,
-    ``track_slots``, ``R`` and ``device`` -> ``(x as a float32 tensor where it is, host slot ids or None, the TrackResult's four tensors or None, ticks)``."""
-    xt = _rows_tensor(x, f.device, who)
-    ticks = index_in(ticks, who, "ticks", 1, 2 ** 40)
-    J, Ct = f.joints, f._Ct
-    if f.tracked:
-        if slots is not None:
-            raise TypeError(f"{who}: a tracker-driven filter takes the tick's TrackResult, not slots=")
-        B, R = f.streams, f.R
-        if tuple(xt.shape) not in ((B, R, J, Ct), (B * R, J, Ct)):
-            raise ValueError(f"{who}: expected rows [{B},{R},{J},{Ct}] or [{B * R},{J},{Ct}] (one frame per row), got {tuple(xt.shape)}")
-        if track is None:
-            raise TypeError(f"{who}: track (the TrackResult of this tick) is required")
-        return xt, None, check_tracked_tick(track, B, f.track_slots, f.device, who), ticks
-    if track is not None:
-        raise TypeError(f"{who}: a filter built with slots= takes slots=, not a TrackResult")
-    ids = check_slot_ids(slots, f.slots, who)
-    K = f.slots if ids is None else int(ids.size)
-    if tuple(xt.shape) != (K, J, Ct):
-        raise ValueError(f"{who}: expected rows [{K},{J},{Ct}] (one frame per pushed slot), got {tuple(xt.shape)}")
-    return xt, ids, None, ticks
-
-
 def _track_rows(a, who: str) -> torch.Tensor:
     t = _args.as_tensor(a, who, "tracks", _args.FLOAT32)
     if t.dim() < 3:
@@ -241,12 +146,7 @@ def smooth_tracks(tracks, offsets=None, *, score: bool = True, rate: float = 30.
     params = one_euro_params(rate, min_cutoff, beta, d_cutoff, min_score, max_hold, who)
     if not isinstance(score, (bool, np.bool_)):
         raise TypeError(f"{who}: score must be a bool, got {type(score).__name__}")
-    as_list = offsets is None and isinstance(tracks, (list, tuple))
-    parts = [_track_rows(a, who) for a in tracks] if as_list else [_track_rows(tracks, who)]
-    for a in parts:
-        if a.dim() > (3 if as_list or offsets is not None else 4):
-            raise ValueError(f"{who}: expected {'tracks of [N,J,Ct]' if as_list else 'packed tracks [sum N_i,J,Ct]' if offsets is not None else '[N,J,Ct] or [P,N,J,Ct]'}, "
-                             f"got {tuple(a.shape)}")
+    parts, as_list = recorded_parts(tracks, offsets, who, lambda a: _track_rows(a, who), "J,Ct", True)
     if as_list and not parts:
         return []
     J, Ct = int(parts[0].shape[-2]), int(parts[0].shape[-1])
@@ -255,29 +155,13 @@ def smooth_tracks(tracks, offsets=None, *, score: bool = True, rate: float = 30.
     Cn = Ct - (1 if score else 0)
     if not 1 <= J <= MAX_JOINTS or not 1 <= Cn <= MAX_CHANNELS:
         raise ValueError(f"{who}: need J in [1, {MAX_JOINTS}] and {'Ct - 1' if score else 'Ct'} in [1, {MAX_CHANNELS}], got rows [{J},{Ct}]")
-    if offsets is not None:
-        n = int(parts[0].shape[0])
-        off = np.asarray(offsets.detach().cpu() if isinstance(offsets, torch.Tensor) else offsets)
-        if off.ndim != 1 or off.size < 1 or off.dtype.kind not in "iu" or off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] != n:
-            raise ValueError(f"{who}: offsets must be integers [P+1] from 0 up to the packed length {n}, non-decreasing")
-        off = off.astype(np.int64)
-    elif as_list:
-        off = np.cumsum([0] + [a.shape[0] for a in parts], dtype=np.int64)
-    else:
-        lead = tuple(parts[0].shape[:-2])
-        P, n = (1, lead[0]) if len(lead) == 1 else lead
-        off = np.arange(P + 1, dtype=np.int64) * n
+    off = track_offsets(parts, offsets, as_list, who)
     dev = _args.resolve_device(parts, device, who)
-    if as_list:
-        packed = torch.cat([a.to(dev) for a in parts]) if any(a.is_cuda for a in parts) else torch.cat(parts).to(dev)
-    else:
-        packed = parts[0].to(dev).contiguous()
+    packed = pack(parts, as_list, dev)
     out = torch.empty_like(packed)
     P, N = len(off) - 1, int(off[-1])
     if P > 0 and N > 0:
         off_d = torch.from_numpy(off).to(dev)
         with torch.cuda.device(dev):
             _lib.check(_lib.load().kasf_one_euro_tracks(packed.data_ptr(), off_d.data_ptr(), N, P, J, Cn, int(score), C.byref(params), out.data_ptr(), _args.stream()))
-    if as_list:
-        return [out[a:b] for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
-    return out
+    return split(out, off) if as_list else out

@@ -23,7 +23,8 @@ import torch
 from . import _args, _lib
 from .heatmap import check_decode_args, check_flip_args, check_heatmap_args, decode
 from .pose import check_layout, convert_frames
-from .lift import _as_tensor, _forward_windows, _model_device, _per_row, _upload, window_plan
+from .lift import _forward_windows, _model_device, _per_row, _upload, window_plan
+from ._tracks import float_rows, slot_ids
 
 
 def stream_tables(T: int):
@@ -92,25 +93,6 @@ class StreamLifter:
         """Frames pushed since reset, per slot: a copy of the host mirror (no device read)."""
         return self._counts.copy()
 
-    def _ids(self, slots, who: str):
-        """``slots=`` of a call -> int32 ids [K] on the host (None: every slot in order)."""
-        if slots is None:
-            return None
-        if isinstance(slots, torch.Tensor):
-            if slots.is_cuda:
-                raise RuntimeError(f"{who}: slot ids are host integers, got a tensor on {slots.device}")
-            slots = slots.numpy()
-        ids = np.asarray(slots)
-        if ids.size == 0:
-            ids = ids.astype(np.int64)
-        if ids.ndim != 1 or ids.dtype.kind not in "iu":
-            raise ValueError(f"{who}: slots must be a 1-D sequence of integers, got shape {ids.shape} {ids.dtype}")
-        if ids.size and (ids.min() < 0 or ids.max() >= self.slots):
-            raise ValueError(f"{who}: slot ids must be in [0, {self.slots}), got {ids.tolist()}")
-        if len(np.unique(ids)) != ids.size:
-            raise ValueError(f"{who}: slot ids must be distinct, got {ids.tolist()}")
-        return ids.astype(np.int32)
-
     def _lift(self, ids_d, K: int, back: int, n_out: int) -> torch.Tensor:
         """Current windows of the K slots -> one forward -> rows ``clamp(L - 1 - back + r, 0, L - 1)``, r < n_out, of each: [K, n_out, 17, 3]."""
         lib, T, S, halves = self._lib, self.T, self.slots, (2 if self.flip else 1)
@@ -128,8 +110,8 @@ class StreamLifter:
         """One new frame per slot: ``keypoints`` [slots,17,3] (every slot, in order) or, with ``slots=`` (distinct host integers), [K,17,3] for those
         slots; float32 pixel x, y, confidence, numpy or torch, CPU or on the model's GPU.  Returns CUDA fp32 [K,17,3]: per pushed slot, frame
         ``max(L - 1 - lag, 0)`` of its current window's lift (while the slot has at most ``lag`` frames that is its first frame, not final yet)."""
-        kp = _as_tensor(keypoints, self.device, "StreamLifter.push")
-        ids = self._ids(slots, "StreamLifter.push")
+        kp = float_rows(keypoints, self.device, "StreamLifter.push")
+        ids = slot_ids(slots, self.slots, "StreamLifter.push")
         K = self.slots if ids is None else int(ids.size)
         if kp.dim() != 3 or tuple(kp.shape) != (K, 17, 3):
             raise ValueError(f"StreamLifter.push: expected keypoints [{K},17,3] (one frame per pushed slot), got {tuple(kp.shape)}")
@@ -161,7 +143,7 @@ class StreamLifter:
         hm, parts, kind, aspect = check_heatmap_args(heatmaps, center, scale, boxes, aspect, who)
         flip = check_flip_args(hm, flipped, shift, pairs, who)
         dark = check_decode_args(hm, decode, kernel, sigma, udp, refine, who)
-        ids = self._ids(slots, who)
+        ids = slot_ids(slots, self.slots, who)
         K = self.slots if ids is None else int(ids.size)
         if hm.dim() != 4 or hm.shape[0] != K:
             raise ValueError(f"{who}: expected heatmaps [{K},17,H,W] (one person per pushed slot), got {tuple(hm.shape)}")
@@ -170,7 +152,7 @@ class StreamLifter:
     def tail(self, slots=None) -> torch.Tensor:
         """The ``lag`` frames ``push`` has not emitted yet, from the current windows, for the end of a track: [K,lag,17,3], row r = frame
         ``clamp(L - lag + r, 0, L - 1)`` of the window's lift.  One forward, state unchanged; ``lag == 0`` gives an empty [K,0,17,3] without a forward."""
-        ids = self._ids(slots, "StreamLifter.tail")
+        ids = slot_ids(slots, self.slots, "StreamLifter.tail")
         K = self.slots if ids is None else int(ids.size)
         if np.any((self._counts if ids is None else self._counts[ids]) < 1):
             raise ValueError("StreamLifter.tail: a slot without frames has no window (push first)")
@@ -182,7 +164,7 @@ class StreamLifter:
 
     def reset(self, slots=None) -> None:
         """The slots start a new history (``reset()``: all of them).  Only the counts are zeroed: every ring position a window reads is written first."""
-        ids = self._ids(slots, "StreamLifter.reset")
+        ids = slot_ids(slots, self.slots, "StreamLifter.reset")
         if ids is None:
             self._count.zero_()
             self._counts[:] = 0
@@ -195,7 +177,7 @@ class StreamLifter:
         lag (its live slots are not touched): CUDA fp32 of the track's shape, frame f taken from the window after push number ``min(f + lag + 1, N)``.
         For N <= T and lag = T - 1 that is ``lift_track(model, track, ...)``.  The resolution is the lifter's when it was built with one value; otherwise
         ``width=`` and ``height=`` (one value or one per track) are required."""
-        kp = _as_tensor(track, self.device, "StreamLifter.replay")
+        kp = float_rows(track, self.device, "StreamLifter.replay")
         if kp.dim() not in (3, 4) or tuple(kp.shape[-2:]) != (17, 3):
             raise ValueError(f"StreamLifter.replay: expected a track [N,17,3] or [P,N,17,3], got {tuple(kp.shape)}")
         if (width is None) != (height is None):

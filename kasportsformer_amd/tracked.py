@@ -24,23 +24,23 @@ with the forward in flight), decide births and deaths, and upload slot ids.  Her
 * an invalid row touches no state; its pose is zero, ``valid`` 0, ``ids`` 0, ``frames`` 0.
 
 ``tail`` and ``replay`` are not offered: both need to know on the host which tracks ended.
+
+On the device the rule is one function, ``csrc/tracked_rows.h``, which this lifter's kernel and the tracked kernels of ``OneEuroFilter`` and
+``BoneLengthFilter`` all call; on the host the rows, streams and ``TrackResult`` arguments of all three are checked by ``_tracks.py``.
 """
 from __future__ import annotations
 
 from typing import NamedTuple
 
-import numpy as np
 import torch
 
 from . import _args, _lib
 from ._args import index_in
 from .heatmap import check_decode_args, check_flip_args, check_heatmap_args
-from .lift import _as_tensor, _forward_windows, _model_device, _per_row, _upload
+from .lift import _forward_windows, _model_device, _per_row, _upload
 from .pose import check_layout, convert_frames
 from .stream import _checked_tables, _decode_on
-from .track import MAX_PERSONS, MAX_SLOTS, MAX_STREAMS
-
-ROWS = ("persons", "tracks")
+from ._tracks import ROWS, check_tracked_tick, fill_streams, float_rows, rows_mode, stream_ids, track_shape     # noqa: F401 -- ROWS and check_tracked_tick are offered here as before
 
 
 class TrackedTick(NamedTuple):
@@ -54,41 +54,14 @@ def check_tracked_args(T, width, height, streams, track_slots, rows, num_person,
     """Everything the constructor can refuse without a device -> ``(T, width [B] float32, height [B] float32, streams, track_slots, rows mode, R, lag,
     whether the layout is COCO)``."""
     coco = check_layout(layout, who)
-    if rows not in ROWS:
-        raise ValueError(f"{who}: rows must be one of {ROWS}, got {rows!r}")
+    mode = rows_mode(rows, who)
     T = int(T)
     if T < 1:
         raise ValueError(f"{who}: the model's n_frames must be >= 1, got {T}")
-    streams = index_in(streams, who, "streams", 1, MAX_STREAMS)
-    track_slots = index_in(track_slots, who, "track_slots", 1, MAX_SLOTS)
-    num_person = index_in(num_person, who, "num_person", 1, MAX_PERSONS)
+    streams, track_slots, R = track_shape(streams, track_slots, num_person, mode, who)
     lag = index_in(lag, who, "lag", 0, T - 1)
     w32, h32 = _per_row(width, streams, "width", who, "stream"), _per_row(height, streams, "height", who, "stream")
-    R = num_person if rows == "persons" else track_slots
-    return T, w32, h32, streams, track_slots, (_lib.ROWS_PERSONS if rows == "persons" else _lib.ROWS_TRACKS), R, lag, coco
-
-
-_TRACK_FIELDS = (("ids", 2), ("slot", 2), ("born", 2), ("count", 1))
-
-
-def check_tracked_tick(track, streams: int, track_slots: int, device, who: str = "TrackedLifter.push"):
-    """Everything ``push`` can refuse about a ``TrackResult`` without a device -> ``(ids, slot, born, count)``: int32 tensors [streams, track_slots] /
-    [streams] on ``device``, taken as they are -- their contents are read by the kernel only, checking them here would synchronise."""
-    out = []
-    for name, dims in _TRACK_FIELDS:
-        a = getattr(track, name, None)
-        if not isinstance(a, torch.Tensor):
-            raise TypeError(f"{who}: expected a TrackResult (SortTracker.update's), its {name} is {type(a).__name__}")
-        if a.dtype != torch.int32:
-            raise TypeError(f"{who}: TrackResult.{name} must be int32, got {a.dtype}")
-        want = (streams, track_slots)[:dims]
-        if tuple(a.shape) != want:
-            raise ValueError(f"{who}: the lifter has {streams} streams of {track_slots} track slots, got TrackResult.{name} {tuple(a.shape)}")
-        out.append(a.detach())
-    for (name, _), a in zip(_TRACK_FIELDS, out):
-        if a.device != device:
-            raise RuntimeError(f"{who}: TrackResult.{name} is on {a.device}, the lifter on {device} (the tracker's output is read in place)")
-    return tuple(out)
+    return T, w32, h32, streams, track_slots, mode, R, lag, coco
 
 
 def check_tracked_frames(kp: torch.Tensor, streams: int, R: int, who: str = "TrackedLifter.push"):
@@ -126,19 +99,8 @@ class TrackedLifter:
     def reset(self, streams=None) -> None:
         """Zeroes count and owner of every slot of the given streams (an index or a sequence of indices; None: all of them): what must accompany
         ``SortTracker.reset`` of the same streams.  The ring needs no clearing: every position a window reads is written first."""
-        if streams is None:
-            self._count.zero_()
-            self._owner.zero_()
-            return
-        idx = np.atleast_1d(np.asarray(streams))
-        if idx.dtype.kind not in "iu" or idx.ndim != 1:
-            raise TypeError(f"TrackedLifter.reset: streams must be an index or a sequence of indices, got {streams!r}")
-        if idx.size and (idx.min() < 0 or idx.max() >= self.streams):
-            raise ValueError(f"TrackedLifter.reset: streams must be in [0, {self.streams}), got {idx.min()} .. {idx.max()}")
-        count, owner = self._count.view(self.streams, self.track_slots), self._owner.view(self.streams, self.track_slots)
-        for b in idx.tolist():
-            count[b].zero_()
-            owner[b].zero_()
+        idx = stream_ids(streams, self.streams, "TrackedLifter.reset")
+        fill_streams(((self._count, 0), (self._owner, 0)), idx, self.streams, self.track_slots)
 
     def push(self, keypoints, track) -> TrackedTick:
         """One tick: ``keypoints`` [B,R,17,3] or [B*R,17,3] float32 pixel x, y, confidence -- row k of stream b belongs to the track the rule above names
@@ -147,7 +109,7 @@ class TrackedLifter:
         CUDA int32 ``ids`` / ``slot`` / ``born`` [B,track_slots] and ``count`` [B]), read in place.  Returns ``TrackedTick``.  Two launches and one
         eval-mode forward of ``(1 + flip) * B * R`` clips, the same shape every tick."""
         who = "TrackedLifter.push"
-        kp = _as_tensor(keypoints, self.device, who)
+        kp = float_rows(keypoints, self.device, who)
         check_tracked_frames(kp, self.streams, self.R, who)
         ids, slot, born, count_b = check_tracked_tick(track, self.streams, self.track_slots, self.device, who)
         B, R, T, n = self.streams, self.R, self.T, self.streams * self.R

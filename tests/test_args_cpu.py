@@ -12,10 +12,10 @@ from kasportsformer_amd import _args
 
 PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "kasportsformer_amd")
 
-# the lift family shares lift logic through private names; everything else goes through _lib and _args
+# the lift family shares lift logic through private names; everything else goes through _lib, _args and _tracks
 ALLOWED_PRIVATE_IMPORTS = {
-    ("stream", "lift"): {"_as_tensor", "_forward_windows", "_model_device", "_per_row", "_upload"},
-    ("tracked", "lift"): {"_as_tensor", "_forward_windows", "_model_device", "_per_row", "_upload"},
+    ("stream", "lift"): {"_forward_windows", "_model_device", "_per_row", "_upload"},
+    ("tracked", "lift"): {"_forward_windows", "_model_device", "_per_row", "_upload"},
     ("tracked", "stream"): {"_checked_tables", "_decode_on"},
 }
 
