@@ -61,6 +61,8 @@
  *                             order; here the tracker's ids and slots drive the lifter's per-player histories on the device   demo/lib/hrnet/gen_kpts.py:125-170
  *   kasf_one_euro_push, kasf_one_euro_tracked, kasf_one_euro_tracks <- nothing in the reference (its unused revise_kpts, demo/lib/preprocess.py:72-103, patches
  *                             low-score leg joints): the One-Euro filter live pose pipelines put between the pose network and the lift, and behind the lift
+ *   kasf_tracks_refine     <- nothing in the reference: what offline pose tooling puts in front of the lift for a file, interpolation across occlusion gaps and
+ *                             a symmetric, zero-phase smoother
  *   kasf_bone_median, kasf_bone_apply, kasf_bone_push, kasf_bone_tracked <- nothing in the demo; the bone table is get_limb_lens' (utils/loss_calc.py) and the
  *                             quantity held constant is what loss_limb_var_calc penalises in training: one length per bone per player, re-imposed on every frame
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
@@ -902,6 +904,57 @@ int kasf_one_euro_tracked(const float* x, const int32_t* ids, const int32_t* slo
                           int64_t tick, float* xhat, float* dxhat, int64_t* last, int32_t* owner, float* out, int32_t* row_slot, void* stream);
 int kasf_one_euro_tracks(const float* x, const int64_t* offsets, int64_t N, int32_t P, int32_t J, int32_t C, int32_t has_score,
                          const kasf_one_euro_params* params, float* out, void* stream);
+
+/* ---- recorded tracks: gaps filled and a zero-phase smoothing (ADDED under ABI 12: additive, kasf_version() stays 12; look the symbol up by name).  A recorded
+ * track knows the frames after a gap, which the causal One-Euro filter cannot use: a joint that is not usable is interpolated between its usable neighbours
+ * instead of held, and the smoother is symmetric, so it does not lag.  Nothing is read back, nothing is allocated, no atomics: the same bits from run to run.
+ *
+ * Rows are the One-Euro entries' rows [J][Ct], Ct = C + has_score.  Tracks are packed as x, out [N][J][Ct]; track p = rows offsets[p] .. offsets[p + 1] - 1 =
+ * [lo, hi) (device int64 [P + 1], ascending; clamped into [0, N] and to a non-negative length exactly as kasf_one_euro_tracks clamps them: lo = clamp(offsets[p],
+ * 0, N), hi = clamp(offsets[p + 1], lo, N)).  A frame n belongs to the last track whose lo is <= n, if n < its hi.  A track never sees another track's frames.
+ *
+ * Parameters (host values, passed by value into the launch): min_score, max_gap in [0, 64] frames, radius in [0, 32] frames and weights[33], weights[k] = w[k]
+ * the weight at distance k frames; entries above radius are ignored.  The kernel calls no transcendental: the weights are the host's (a Gaussian in
+ * kasportsformer_amd/refine.py; any non-negative table with w[0] > 0 is taken).
+ *
+ * The rule, per (track, joint j), in fp32, every line one rounded operation (a line with two: left to right); the library is built with -ffp-contract=off and a
+ * correctly rounded divide:
+ *   1. Joint j of frame n is USABLE by step 1 of the One-Euro rule above, the same code: every one of its C values satisfies |v| <= 1e12f (a NaN fails) and, with
+ *      a score, x[n][j][C] >= min_score (a NaN fails).
+ *   2. Fill.  A frame that is not usable has a = the nearest usable frame of joint j in [lo, n) and b = the nearest in (n, hi), where they exist.  Its STATE:
+ *        0 usable        the joint is usable:                                                      y = x
+ *        1 interpolated  a and b exist and b - a - 1 <= max_gap:   t = float(n - a) / float(b - a);  y[c] = x[a][c] + (x[b][c] - x[a][c]) * t
+ *        2 held          a leading run, no usable frame in [lo, n), and b - lo <= max_gap:          y = x[b]
+ *                        a trailing run, no usable frame in (n, hi), and hi - 1 - a <= max_gap:      y = x[a]
+ *        3 left          everything else (a track without a usable frame included):                 the joint is UNKNOWN, y is not used
+ *      A joint of state 0, 1 or 2 is KNOWN.  States 1 and 2 need every frame of the run to be within max_gap frames of n, so every search reaches at most
+ *      max_gap frames each way and stops at the track's end; max_gap = 0 fills nothing.
+ *   3. Smooth, for a known joint: r = min(radius, n - lo, hi - 1 - n) -- the window is symmetric, so the ends of a track get a narrower window, never a
+ *      one-sided one.  num[c] = 0, den = 0; for k = -r .. r ascending with m = n + k, if joint j of frame m is known:
+ *        num[c] = num[c] + w[|k|] * (y[m][c] - y[n][c])       (subtract, multiply, add)
+ *        den    = den + w[|k|]
+ *      and the output is y[n][c] + num[c] / den.  w[0] > 0 and frame n itself is known, so den > 0.  The incremental form returns a constant input bit for
+ *      bit and the first and last frame of a track as they are (r = 0); on a linear ramp of known joints the symmetric terms cancel.  radius = 0 smooths
+ *      nothing: the output is the filled y.
+ *   4. An unknown joint is copied through bit for bit.  The score channel is copied through in every case (a filled joint keeps its low score).
+ *   5. state [N][J] uint8 (may be NULL) receives 0 / 1 / 2 / 3 per joint.
+ *   6. Rows of x outside every track are not written, in out and in state, as in kasf_one_euro_tracks.
+ *
+ * kasf_tracks_refine: one launch; a workgroup owns a tile of consecutive packed frames (which may span several short tracks) and a chunk of joints, with the
+ * filled y of the tile and of radius frames either side in LDS; no intermediate in global memory.  Every index formed from a device value (the offsets) is
+ * clamped; with offsets that do not ascend every access still stays inside the arrays, which rows are written is then unspecified.  A track's result does not
+ * depend on the other tracks of the launch.  x is only read; out and state do not overlap x.
+ *
+ * P = 0 or N = 0 does nothing.  Error 2, before a device or a device pointer is touched: J outside [1, 256] or C outside [1, 4]; P or N negative; max_gap outside
+ * [0, 64]; radius outside [0, 32]; a non-finite min_score; a weight of weights[0 .. radius] that is not finite, is negative or is above 1e6; weights[0] not > 0; a null
+ * pointer (params included; state may be NULL). */
+typedef struct kasf_refine_params {
+    float min_score;
+    int32_t max_gap, radius;
+    float weights[33];
+} kasf_refine_params;
+int kasf_tracks_refine(const float* x, const int64_t* offsets, int64_t N, int32_t P, int32_t J, int32_t C, int32_t has_score, const kasf_refine_params* params,
+                       float* out, uint8_t* state, void* stream);
 
 /* ---- constant limb lengths per player (ADDED under ABI 12: additive, kasf_version() stays 12; look the four symbols up by name).  The lift predicts every
  * window on its own and the One-Euro filter steadies positions, not the skeleton: a thigh still breathes from frame to frame.  This stage, between the lift and

@@ -56,6 +56,9 @@ Public surface mirrors the reference's interface for this path:
                                         (Casiez et al., CHI 2012) over 2-D keypoints in front of the lift and 3-D poses behind it, state on the device, driven
                                         by host slot ids or by `TrackResult`, score-gated so that an occluded joint holds; one launch per tick, no read-back
                                         (`python -m kasportsformer_amd.lift --smooth`)
+  refine_tracks                         not in the demo: what offline pose tooling does to a recorded track in front of the lift -- a joint that is not usable is
+                                        interpolated between its usable neighbours (short leading and trailing runs hold), then a symmetric, zero-phase Gaussian
+                                        over the known joints; parallel over frames, one launch (`python -m kasportsformer_amd.lift --refine`)
   fix_bone_lengths, bone_lengths,       not in the demo: one length per bone per player (the lower median over the track, or a measured table), re-imposed on every
   BoneLengthFilter                      frame by a walk from the root that keeps directions and the root; the bone table is utils/loss_calc.py:30-40's, the quantity
                                         what `loss_limb_var_calc` penalises; recorded tracks in three launches, live rows with a running mean per slot in one,
@@ -89,6 +92,7 @@ from .draw import draw_poses, bgr_to_nv12, poses_to_panel, DrawResult
 from .track import SortTracker, TrackResult, TrackState
 from .tracked import TrackedLifter, TrackedTick
 from .smooth import OneEuroFilter, smooth_tracks
+from .refine import refine_tracks
 from .bones import fix_bone_lengths, bone_lengths, BoneLengthFilter
 
 __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_stream", "set_deterministic", "is_deterministic", "set_fused_attention_backward", "is_fused_attention_backward", "loss3", "loss7", "LOSS7_NAMES", "FusedAdamW", "AdamW", "plan_chunks", "DataParallel", "joint_flip", "predict_flip_tta", "clip_metrics", "Evaluator",
@@ -97,4 +101,4 @@ __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_strea
            "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample",
            "lift_track", "lift_tracks", "window_plan", "StreamLifter", "coco_to_h36m", "poses_to_world", "DEMO_CAMERA_ROTATION", "heatmaps_to_keypoints", "gaussian_weights",
            "detections_to_boxes", "yolo_heads_to_boxes", "DetectResult", "YOLOV3_ANCHORS", "YOLOV3_MASKS", "crop_persons", "CropResult", "letterbox_frames", "LetterboxResult", "yuv_to_bgr", "nv12_to_bgr", "i420_to_bgr", "SortTracker", "TrackResult", "TrackState",
-           "TrackedLifter", "TrackedTick", "OneEuroFilter", "smooth_tracks", "fix_bone_lengths", "bone_lengths", "BoneLengthFilter", "draw_poses", "bgr_to_nv12", "poses_to_panel", "DrawResult"]
+           "TrackedLifter", "TrackedTick", "OneEuroFilter", "smooth_tracks", "refine_tracks", "fix_bone_lengths", "bone_lengths", "BoneLengthFilter", "draw_poses", "bgr_to_nv12", "poses_to_panel", "DrawResult"]

@@ -55,6 +55,10 @@ class KasfOneEuroParams(C.Structure):     # kasf_one_euro_params: host values, p
     _fields_ = [("dt", C.c_float), ("min_cutoff", C.c_float), ("d_cutoff", C.c_float), ("beta", C.c_float), ("min_score", C.c_float), ("max_hold", C.c_int32)]
 
 
+class KasfRefineParams(C.Structure):      # kasf_refine_params: host values, passed by value into the launch; weights[k] = the weight at distance k frames
+    _fields_ = [("min_score", C.c_float), ("max_gap", C.c_int32), ("radius", C.c_int32), ("weights", C.c_float * 33)]
+
+
 class KasfError(RuntimeError):
     pass
 
@@ -116,6 +120,7 @@ SIGNATURES = {
     "kasf_one_euro_push": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(KasfOneEuroParams), _i64, _vp, _vp, _vp, _vp, _vp]),
     "kasf_one_euro_tracked": (_i32, [_vp] * 5 + [_i32] * 7 + [C.POINTER(KasfOneEuroParams), _i64] + [_vp] * 7),
     "kasf_one_euro_tracks": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, C.POINTER(KasfOneEuroParams), _vp, _vp]),
+    "kasf_tracks_refine": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, C.POINTER(KasfRefineParams), _vp, _vp, _vp]),
     "kasf_bone_median": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "kasf_bone_apply": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp]),
     "kasf_bone_push": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

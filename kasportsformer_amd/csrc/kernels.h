@@ -227,6 +227,12 @@ void kasf_launch_one_euro_tracked(hipStream_t s, const float* x, const int* ids,
 void kasf_launch_one_euro_tracks(hipStream_t s, const float* x, const int64_t* offsets, int64_t N, int P, int J, int C, int has_score, const KasfOneEuro& p,
                                  float* out);
 
+// ---- k_refine.hip: recorded tracks with their gaps filled and a zero-phase smoothing (kasf.h, kasf_tracks_refine): x, out [N,J,C + has_score] packed as for
+// kasf_launch_one_euro_tracks, state [N,J] bytes or null; C in [1, 4], J in [1, 256] and the parameters as checked by the entry point, p passed by value ----
+#include "track_refine.h"    // KasfRefine and the rule's device functions
+void kasf_launch_tracks_refine(hipStream_t s, const float* x, const int64_t* offsets, int64_t N, int P, int J, int C, int has_score, const KasfRefine& p, float* out,
+                               unsigned char* state);
+
 // ---- k_bones.hip: constant limb lengths per player (kasf.h, kasf_bone_*): frames of [17,3] fp32, 16 bones; scratch [16][N] holds bone k's length in frame f
 // at k * N + f, 0 where it is not usable; lengths / counts [P][16]; the live state len / cnt [S][16]; arguments as checked by the entry points ----
 void kasf_launch_bone_lengths(hipStream_t s, const float* poses, int64_t N, float* scratch);

@@ -13,6 +13,17 @@ struct KasfOneEuro {
     int max_hold;
 };
 
+// Whether a joint can be used: x: its Ct = C + has_score values.  Every one of the C values finite and within 1e12, and (with a score) the score at least
+// min_score.  The one statement of the test for the One-Euro step and for the recorded-track refinement (track_refine.h).
+template <int C>
+__device__ inline bool joint_usable(const float* x, bool has_score, float min_score) {
+    bool usable = true;
+#pragma unroll
+    for (int c = 0; c < C; ++c) usable = usable && fabsf(x[c]) <= 1e12f;       // false for a NaN and for an infinity as well: finite and within 1e12
+    if (has_score) usable = usable && x[C] >= min_score;           // a NaN score fails the comparison
+    return usable;
+}
+
 // One joint of one row.  x: the joint's Ct = C + has_score input values; xh, dxh: its estimate and derivative (read only when last >= 0); last: the tick of its
 // last update, < 0 for none.  Writes the C filtered channels to out (the score channel is the caller's copy) and returns whether xh / dxh / last changed: they
 // are to be stored exactly then, a held joint's state stays as it is.
@@ -20,13 +31,9 @@ template <int C>
 __device__ inline bool one_euro_joint(const KasfOneEuro& p, bool has_score, const float* x, int64_t tick, float (&xh)[C], float (&dxh)[C], int64_t& last,
                                       float (&out)[C]) {
     float m[C];
-    bool usable = true;
 #pragma unroll
-    for (int c = 0; c < C; ++c) {
-        m[c] = x[c];
-        usable = usable && fabsf(m[c]) <= 1e12f;                   // false for a NaN and for an infinity as well: finite and within 1e12
-    }
-    if (has_score) usable = usable && x[C] >= p.min_score;         // a NaN score fails the comparison
+    for (int c = 0; c < C; ++c) m[c] = x[c];
+    const bool usable = joint_usable<C>(x, has_score, p.min_score);
     int64_t k = tick - last;
     if (k < 1) k = 1;
     const bool have = last >= 0 && k - 1 <= (int64_t)p.max_hold;   // an estimate older than max_hold missed ticks is dropped

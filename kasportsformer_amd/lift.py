@@ -21,7 +21,9 @@ the forward together (``kasf_lift_windows_ragged`` / ``kasf_lift_stitch_ragged``
 
 ``layout="coco"`` (``--layout coco``) takes the keypoints as a COCO-17 detector writes them and converts them on the device first
 (``kasportsformer_amd.pose.coco_to_h36m``); ``--smooth [--smooth-rate] [--smooth-min-cutoff] [--smooth-beta] [--smooth-min-score]`` sends the keypoints
-through the One-Euro filter first (``kasportsformer_amd.smooth.smooth_tracks``), offline and ``--online`` alike; ``--fix-bones [--fix-bones-symmetric]`` gives every bone of a track one length
+through the One-Euro filter first (``kasportsformer_amd.smooth.smooth_tracks``), offline and ``--online`` alike; ``--refine [--refine-min-score] [--refine-max-gap] [--refine-sigma]`` takes that place for a recorded
+track (``kasportsformer_amd.refine.refine_tracks``: occlusion gaps filled from both sides, then a zero-phase Gaussian; not with ``--smooth``, not with ``--online``)
+and ``--refine-poses`` runs the same over the lifted poses, before ``--fix-bones``; ``--fix-bones [--fix-bones-symmetric]`` gives every bone of a track one length
 (``kasportsformer_amd.bones.fix_bone_lengths`` over the final poses, before ``--world``); ``--world [--world-floor] [--world-unit]`` sends the poses through ``poses_to_world`` before they are written.
 """
 from __future__ import annotations
@@ -315,6 +317,14 @@ def _parse(argv=None):
     ap.add_argument("--smooth-min-cutoff", type=float, default=None, help="--smooth: cutoff at rest in Hz (default 1.0; lower: steadier, more lag)")
     ap.add_argument("--smooth-beta", type=float, default=None, help="--smooth: cutoff gained per pixel / s of speed (default 0.01; higher: less lag in motion)")
     ap.add_argument("--smooth-min-score", type=float, default=None, help="--smooth: a joint scored below this holds (default 0.3)")
+    ap.add_argument("--refine", action="store_true", help="fill the gaps of joints scored below --refine-min-score from the frames on both sides and smooth with a "
+                                                          "zero-phase Gaussian (kasportsformer_amd.refine_tracks) over the keypoints before the lift; a recorded "
+                                                          "track only: not with --smooth, not with --online")
+    ap.add_argument("--refine-min-score", type=float, default=None, help="--refine: a joint scored below this is filled (default 0.3)")
+    ap.add_argument("--refine-max-gap", type=int, default=None, help="--refine: the longest run of frames that is filled, in [0, 64] (default 15)")
+    ap.add_argument("--refine-sigma", type=float, default=None, help="--refine: the Gaussian's sigma in frames (default 2.0; a starting point, not tuned on footage)")
+    ap.add_argument("--refine-poses", action="store_true", help="run refine_tracks over the lifted poses as well (no score: only a NaN gates a joint), before "
+                                                                "--fix-bones; not with --online")
     ap.add_argument("--fix-bones", action="store_true", help="give every bone of a track one length, the track's lower median (kasportsformer_amd.fix_bone_lengths), "
                                                              "over the final poses and before --world")
     ap.add_argument("--fix-bones-symmetric", action="store_true", help="--fix-bones: left / right partner bones get their mean")
@@ -327,6 +337,16 @@ def _parse(argv=None):
     for k, v in smooth_defaults.items():
         if getattr(args, k) is None:
             setattr(args, k, v)
+    refine_defaults = dict(refine_min_score=0.3, refine_max_gap=15, refine_sigma=2.0)
+    if not args.refine and any(getattr(args, k) is not None for k in refine_defaults):
+        ap.error("--refine-min-score, --refine-max-gap and --refine-sigma belong to --refine")
+    for k, v in refine_defaults.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v)
+    if args.refine and args.smooth:
+        ap.error("--refine and --smooth both clean up the keypoints before the lift: give one of them")
+    if (args.refine or args.refine_poses) and args.online:
+        ap.error("--refine and --refine-poses are zero-phase: they need the frames after, which --online does not have (--smooth is the live filter)")
     if args.fix_bones_symmetric and not args.fix_bones:
         ap.error("--fix-bones-symmetric belongs to --fix-bones")
     if args.online and args.stride is not None:
@@ -355,8 +375,15 @@ def main(argv=None):
         from .smooth import smooth_tracks
         keypoints = smooth_tracks(keypoints, score=True, rate=args.smooth_rate, min_cutoff=args.smooth_min_cutoff, beta=args.smooth_beta,
                                   min_score=args.smooth_min_score, device=_model_device(model))
+    if args.refine:                                # in the place --smooth has: one launch over every track, on the model's GPU
+        from .refine import refine_tracks
+        keypoints = refine_tracks(keypoints, score=True, min_score=args.refine_min_score, max_gap=args.refine_max_gap, sigma=args.refine_sigma,
+                                  device=_model_device(model))
 
     def final(poses):
+        if args.refine_poses:                          # poses carry no score: only a joint that is not finite is filled
+            from .refine import refine_tracks
+            poses = refine_tracks(poses, score=False)
         if args.fix_bones:                             # one track [N,17,3], or [P,N,17,3]: every track its own medians
             from .bones import fix_bone_lengths
             poses = fix_bone_lengths(poses, symmetric=args.fix_bones_symmetric)
