@@ -65,6 +65,8 @@
  *                             a symmetric, zero-phase smoother
  *   kasf_bone_median, kasf_bone_apply, kasf_bone_push, kasf_bone_tracked <- nothing in the demo; the bone table is get_limb_lens' (utils/loss_calc.py) and the
  *                             quantity held constant is what loss_limb_var_calc penalises in training: one length per bone per player, re-imposed on every frame
+ *   kasf_pose_place        <- nothing in the reference (its demo plots one person at the origin): the root translation that re-projects a root-relative pose
+ *                             onto its keypoints through the camera's intrinsics, so that several players stand where they stood
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
  *   kasf_op_gcn_fwd, kasf_op_gcn_bwd <- GCN.forward between its U | V Linear and the residual, and autograd of it   model/modules/graph.py:19-134, KASportsFormer.py:109
  */
@@ -1007,6 +1009,68 @@ int kasf_bone_push(const float* poses, const int32_t* slots, int32_t K, int32_t 
 int kasf_bone_tracked(const float* poses, const int32_t* ids, const int32_t* slot, const int32_t* born, const int32_t* count_b, int32_t streams,
                       int32_t track_slots, int32_t rows_mode, int32_t R, int32_t window, int32_t symmetric, float* len, int32_t* cnt, int32_t* owner, float* out,
                       int32_t* row_slot, void* stream);
+
+/* ---- lifted poses placed in camera space (ADDED under ABI 12: additive, kasf_version() stays 12; look the symbol up by name).  The lift returns every pose
+ * root-relative, joint 0 at the origin, so every player stands on the same spot.  With the 2-D keypoints the pose came from and the camera's intrinsics, the
+ * root translation T that makes the pose re-project onto its keypoints is a 3 x 3 linear least-squares problem per frame; this stage solves it on the device.
+ * Frames are independent of one another: a recorded track and one live tick are the same call.  Nothing is read back, nothing is allocated, no atomics: the
+ * same bits from run to run.  The camera is a pinhole, (fx, fy, cx, cy) in pixels: THERE IS NO DISTORTION MODEL; undistort the keypoints first where the lens
+ * needs it.
+ *
+ * Per frame: the pose P [17][3] fp32, root-relative, in any one unit; the keypoints k [17][3] fp32, pixel x, pixel y, score, in the Human3.6M-17 layout; the
+ * camera (fx, fy, cx, cy) fp32.  ALL ARITHMETIC BELOW IS IN FP64 (on players at 4 - 40 m with f = 1500 px the system's condition number reaches 4e4), joints
+ * and bones in ascending order, every line one rounded operation (a line with several: by its parentheses, then left to right); the library is built with
+ * -ffp-contract=off and a correctly rounded divide and square root.  An fp32 input enters by an exact conversion; results are rounded to fp32 once, at the store.
+ *   1. Joint j is USABLE when its keypoint passes step 1 of the One-Euro rule above with C = 2 and a score, the same code (|x|, |y| <= 1e12f and score >=
+ *      min_score; a NaN fails) and its three pose values are finite.  n = the number of usable joints.
+ *   2. scale.  Without a bone table, scale = 1.  With a table L [16] fp32 in metres (bone b joins joint b + 1 to its parent, kasf_bone_median's table; an entry
+ *      that is not > 0 means "skip this bone"): sumL = 0, sumP = 0; for b ascending with L[b] > 0: d = P[b + 1] - P[parent(b)];
+ *      sumL = sumL + L[b]; sumP = sumP + sqrt((dx * dx + dy * dy) + dz * dz); then scale = sumL / sumP.  p[j] = P[j] * scale for every joint.  The model's unit is
+ *      image pixels, so a player's size in pose units changes with depth: the scale is per frame.  (The other route to metres: kasf_bone_apply with the table
+ *      first, then this entry without one.)  A table with no entry > 0 gives 0 / 0, which is state 3.
+ *   3. The fit.  Weights w0[j] = score[j] when weighted, else 1; w = w0 in pass 0.  S = Sx = Sy = Sq = b0 = b1 = b2 = 0; for each usable j ascending:
+ *        xh = (u - cx) / fx;  yh = (v - cy) / fy;  q1 = xh * pz - px;  q2 = yh * pz - py        (the rows [1, 0, -xh] T = q1 and [0, 1, -yh] T = q2)
+ *        S = S + w;  Sx = Sx + w * xh;  Sy = Sy + w * yh;  Sq = Sq + w * (xh * xh + yh * yh)
+ *        b0 = b0 + w * q1;  b1 = b1 + w * q2;  b2 = b2 + w * (xh * q1 + yh * q2)
+ *      The normal matrix is A = [[S, 0, -Sx], [0, S, -Sy], [-Sx, -Sy, Sq]] with the right-hand side (b0, b1, -b2).  It is solved by eliminating the first two
+ *      unknowns (Cholesky's pivots without the square roots):
+ *        D = Sq - (Sx * Sx + Sy * Sy) / S
+ *        Tz = ((Sx * b0 + Sy * b1) / S - b2) / D;  Tx = (b0 + Sx * Tz) / S;  Ty = (b1 + Sy * Tz) / S
+ *      THE PIVOT TEST: A counts as positive definite when S > 0 and D > 1e-9 * Sq (a NaN fails): keypoints that spread over less than about 3e-5 of the
+ *      focal length, a twentieth of a pixel at f = 1500, do not fix a depth.
+ *   4. Re-weighting, `iterations` times (in [0, 8]): for each usable j: X = px + Tx, Y = py + Ty, Z = pz + Tz;
+ *        du = (fx * (X / Z) + cx) - u;  dv = (fy * (Y / Z) + cy) - v;  r2 = du * du + dv * dv;  w = w0 / (1 + r2 / (delta * delta))
+ *      (Cauchy weights: no square root), then step 3's sums and solve again with these w.  delta is in pixels; delta * delta is the product of the two fp32
+ *      values in fp64.
+ *   5. Outputs, with r2 of step 4 at the final T:  num = num + w0 * r2 and den = den + w0 over the usable joints;
+ *        out[j] = fp32(P[j] * scale + T) for all 17 joints (a joint whose pose value is not finite stays not finite),  root = fp32(T),
+ *        residual = fp32(sqrt(num / den)) in pixels,  scale = fp32(scale), stored whatever the state.
+ *   6. state, uint8, the first that applies:
+ *        1  n < min_joints (min_joints in [2, 17])
+ *        3  scale is not finite and positive (a pose value that is not finite on a bone of the table, a table without an entry > 0, coincident joints)
+ *        2  a degenerate fit: in any pass the pivot test fails, or Tx, Ty or Tz is not finite, or a usable joint has Z = pz + Tz <= 0 at any T
+ *        0  placed
+ *      A frame whose state is not 0 gets NaN (0x7fc00000) in all of out, in root and in residual: kasf_tracks_refine over the roots (has_score = 0) then
+ *      interpolates it from its neighbours.
+ *
+ * kasf_pose_place: poses, keypoints, out [frames][17][3]; camera one row [4] for every frame, or with camera_per_frame != 0 [frames][4]; lengths NULL for no
+ * table, one row [16], or with lengths_per_frame != 0 [frames][16]; root [frames][3], residual [frames], scale [frames] and state [frames] may each be NULL.
+ * All device pointers.  One launch: a workgroup stages a tile of 64 frames of both inputs in LDS (float4 where poses, keypoints and out are 16-byte aligned),
+ * one lane owns one frame with its accumulators in fp64 registers, the placed pose leaves as whole rows.  The inputs are only read; out is an array of its own.
+ *
+ * frames = 0 does nothing.  Error 2, before a device or a device pointer is touched: frames negative; a non-finite min_score; weighted neither 0 nor 1;
+ * iterations outside [0, 8]; delta not finite or not > 0; min_joints outside [2, 17]; out == poses or out == keypoints; a null pointer (params included;
+ * lengths, root, residual, scale and state may be NULL).  The defaults of kasportsformer_amd/place.py (min_score 0.3, weighted, 4 iterations, delta 3 px,
+ * 4 joints) are a starting point, not tuned on footage. */
+typedef struct kasf_place_params {
+    float min_score;
+    int32_t weighted, iterations;
+    float delta;
+    int32_t min_joints;
+} kasf_place_params;
+int kasf_pose_place(const float* poses, const float* keypoints, int64_t frames, const float* camera, int32_t camera_per_frame, const float* lengths,
+                    int32_t lengths_per_frame, const kasf_place_params* params, float* out, float* root, float* residual, float* scale, uint8_t* state,
+                    void* stream);
 
 /* debugging / tests: locate a named activation inside the workspace (see kasf_ws_name()) */
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags);

@@ -55,6 +55,10 @@ class KasfOneEuroParams(C.Structure):     # kasf_one_euro_params: host values, p
     _fields_ = [("dt", C.c_float), ("min_cutoff", C.c_float), ("d_cutoff", C.c_float), ("beta", C.c_float), ("min_score", C.c_float), ("max_hold", C.c_int32)]
 
 
+class KasfPlaceParams(C.Structure):       # kasf_place_params: host values, passed by value into the launch
+    _fields_ = [("min_score", C.c_float), ("weighted", C.c_int32), ("iterations", C.c_int32), ("delta", C.c_float), ("min_joints", C.c_int32)]
+
+
 class KasfRefineParams(C.Structure):      # kasf_refine_params: host values, passed by value into the launch; weights[k] = the weight at distance k frames
     _fields_ = [("min_score", C.c_float), ("max_gap", C.c_int32), ("radius", C.c_int32), ("weights", C.c_float * 33)]
 
@@ -125,6 +129,7 @@ SIGNATURES = {
     "kasf_bone_apply": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp]),
     "kasf_bone_push": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "kasf_bone_tracked": (_i32, [_vp] * 5 + [_i32] * 6 + [_vp] * 6),
+    "kasf_pose_place": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i32, C.POINTER(KasfPlaceParams)] + [_vp] * 6),
     "kasf_coco_h36m": (_i32, [_vp, _i64, _vp, _vp]),
     "kasf_pose_world": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "kasf_heatmap_keypoints": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i32, C.c_double, _i32, _i32, _vp, _vp, _vp]),

@@ -13,20 +13,13 @@
 // that holds the rank.  The median is an order statistic: its bits do not depend on the order the counts arrive in, so the result is the same from run to run.
 // Every index formed from a device value (offset, slot id, count_b, slot) is clamped into the arrays the host sized.  Inputs are only read.
 #include "kernels.h"
+#include "bone_table.h"
 
 namespace {
 
 constexpr int BONE_TILE = 128;                                  // frames per workgroup pass = threads per workgroup; 128 * 204 B = 25.5 KiB of LDS
 constexpr int BONE_TILE_FLOATS = BONE_TILE * 51;                // a multiple of 4: every full tile starts 16-byte aligned when the array does
 constexpr int SELECT_THREADS = 256;                             // = the bins of a pass
-
-// bone k joins child k + 1 to parent (0,1,2,0,4,5,0,7,8,9,8,11,12,8,14,15)[k]; its left / right partner is (3,4,5,0,1,2,-,-,-,-,13,14,15,10,11,12)[k], itself
-// where it has none: four bits per entry, so that a lane can look its own bone up without a table in memory
-__host__ __device__ constexpr int bone_parent(int k) { return (int)((0xFE8CB89870540210ull >> (4 * k)) & 15); }
-__host__ __device__ constexpr int bone_partner(int k) { return (int)((0xCBAFED9876210543ull >> (4 * k)) & 15); }
-static_assert(bone_parent(0) == 0 && bone_parent(3) == 0 && bone_parent(5) == 5 && bone_parent(6) == 0 && bone_parent(10) == 8 && bone_parent(12) == 12 &&
-              bone_parent(13) == 8 && bone_parent(15) == 15, "the bone table of kasf.h");
-static_assert(bone_partner(0) == 3 && bone_partner(5) == 2 && bone_partner(7) == 7 && bone_partner(10) == 13 && bone_partner(15) == 12, "the partners of kasf.h");
 
 __device__ inline bool bone_finite(float v) { return fabsf(v) <= 3.4028235e38f; }                // false for a NaN and for an infinity
 __device__ inline bool bone_usable(float l) { return l > 0.0f && l <= 3.4028235e38f; }

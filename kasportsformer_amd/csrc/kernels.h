@@ -250,6 +250,17 @@ void kasf_launch_coco_h36m(hipStream_t s, const float* coco, int64_t frames, flo
 // q [4], t [3]: host arrays, passed by value into the launch
 void kasf_launch_pose_world(hipStream_t s, const float* poses, int64_t frames, const float* q, const float* t, int floor, int unit, float* out);
 
+// ---- k_place.hip: lifted poses placed in camera space (kasf.h, kasf_pose_place); poses, keypoints, out [frames][17][3] fp32, out a distinct array; camera [4]
+// or [frames][4], lengths null, [16] or [frames][16], selected by the two flags; root [frames][3], residual, scale [frames] and state [frames] bytes may be
+// null; the parameters as the entry point checked them, passed by value into the launch ----
+struct KasfPlace {
+    float min_score, delta;
+    int weighted, iterations, min_joints;
+};
+void kasf_launch_pose_place(hipStream_t s, const float* poses, const float* keypoints, int64_t frames, const float* camera, int camera_per_frame,
+                            const float* lengths, int lengths_per_frame, const KasfPlace& p, float* out, float* root, float* residual, float* scale,
+                            unsigned char* state);
+
 // ---- k_heatmap.hip: pose-network heatmaps hm [n,17,H,W] (dtype KASF_F32 / KASF_F16 / KASF_BF16) -> out [n,17,3] fp32 image x, y, score in COCO order (kasf.h,
 // kasf_heatmap_keypoints); geom [n,4] fp32: kind 0 = center x, y, scale x, y; kind 1 = box x1, y1, x2, y2 widened to `aspect`; H * W <= 2^24 ----
 void kasf_launch_heatmap_keypoints(hipStream_t s, const void* hm, int dtype, int64_t n, int H, int W, const float* geom, int geom_kind, double aspect,

@@ -24,7 +24,9 @@ the forward together (``kasf_lift_windows_ragged`` / ``kasf_lift_stitch_ragged``
 through the One-Euro filter first (``kasportsformer_amd.smooth.smooth_tracks``), offline and ``--online`` alike; ``--refine [--refine-min-score] [--refine-max-gap] [--refine-sigma]`` takes that place for a recorded
 track (``kasportsformer_amd.refine.refine_tracks``: occlusion gaps filled from both sides, then a zero-phase Gaussian; not with ``--smooth``, not with ``--online``)
 and ``--refine-poses`` runs the same over the lifted poses, before ``--fix-bones``; ``--fix-bones [--fix-bones-symmetric]`` gives every bone of a track one length
-(``kasportsformer_amd.bones.fix_bone_lengths`` over the final poses, before ``--world``); ``--world [--world-floor] [--world-unit]`` sends the poses through ``poses_to_world`` before they are written.
+(``kasportsformer_amd.bones.fix_bone_lengths`` over the final poses, before ``--world``); ``--place --camera FX,FY,CX,CY [--place-lengths table.npy]
+[--place-iterations] [--place-delta]`` then puts every pose where its player stood in front of the camera (``kasportsformer_amd.place.place_poses``, after
+``--fix-bones`` and ``--refine-poses``, before ``--world``; not with ``--world-unit``; an ``.npz`` output also gets ``root_i`` and ``place_state_i`` per track); ``--world [--world-floor] [--world-unit]`` sends the poses through ``poses_to_world`` before they are written.
 """
 from __future__ import annotations
 
@@ -328,6 +330,12 @@ def _parse(argv=None):
     ap.add_argument("--fix-bones", action="store_true", help="give every bone of a track one length, the track's lower median (kasportsformer_amd.fix_bone_lengths), "
                                                              "over the final poses and before --world")
     ap.add_argument("--fix-bones-symmetric", action="store_true", help="--fix-bones: left / right partner bones get their mean")
+    ap.add_argument("--place", action="store_true", help="place every pose in camera space from its keypoints and --camera (kasportsformer_amd.place_poses), "
+                                                         "after --refine-poses and --fix-bones, before --world; an .npz output also gets root_i and place_state_i")
+    ap.add_argument("--camera", default=None, help="--place: the pinhole intrinsics FX,FY,CX,CY in pixels (no lens distortion is modelled)")
+    ap.add_argument("--place-lengths", default=None, help="--place: an .npy of the sixteen bone lengths in metres (0 skips a bone): the roots come out in metres")
+    ap.add_argument("--place-iterations", type=int, default=None, help="--place: rounds of Cauchy re-weighting, in [0, 8] (default 4)")
+    ap.add_argument("--place-delta", type=float, default=None, help="--place: the re-weighting's scale in pixels (default 3.0; a starting point, not tuned on footage)")
     ap.add_argument("--out", required=True, help="output .npy of [P,N,17,3] (or [N,17,3]) float32 poses; tracks of different lengths: an .npz "
                                                  "of track_0 ... track_{P-1}")
     args = ap.parse_args(argv)
@@ -355,11 +363,37 @@ def _parse(argv=None):
         ap.error("--lag belongs to --online")
     if (args.world_floor or args.world_unit) and not args.world:
         ap.error("--world-floor and --world-unit belong to --world")
+    place_defaults = dict(place_iterations=4, place_delta=3.0)
+    if not args.place and (args.camera is not None or args.place_lengths is not None or any(getattr(args, k) is not None for k in place_defaults)):
+        ap.error("--camera, --place-lengths, --place-iterations and --place-delta belong to --place")
+    for k, v in place_defaults.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v)
+    if args.place:
+        if args.camera is None:
+            ap.error("--place needs --camera FX,FY,CX,CY")
+        if args.world_unit:
+            ap.error("--place is refused with --world-unit, which divides every frame by its largest value: the placement would be divided away")
+        try:
+            camera = [float(v) for v in args.camera.split(",")]
+        except ValueError:
+            camera = []
+        if len(camera) != 4 or not all(np.isfinite(np.float32(v)) for v in camera) or not (camera[0] > 0 and camera[1] > 0):
+            ap.error(f"--camera must be four finite numbers FX,FY,CX,CY with FX, FY > 0, got {args.camera!r}")
+        args.camera = np.array(camera, np.float32)
+        if not 0 <= args.place_iterations <= 8:
+            ap.error("--place-iterations must be in [0, 8]")
+        if not (np.isfinite(args.place_delta) and args.place_delta > 0):
+            ap.error("--place-delta must be finite and > 0 pixels")
     return args
 
 
 def main(argv=None):
     args = _parse(argv)
+    place_table = None
+    if args.place_lengths is not None:                 # refused before the model is loaded
+        from .place import load_bone_table
+        place_table = load_bone_table(args.place_lengths)
 
     import yaml
     from .checkpoint import checkpoint_load
@@ -380,34 +414,45 @@ def main(argv=None):
         keypoints = refine_tracks(keypoints, score=True, min_score=args.refine_min_score, max_gap=args.refine_max_gap, sigma=args.refine_sigma,
                                   device=_model_device(model))
 
-    def final(poses):
+    extras = {}                                        # --place: root_i and place_state_i of an .npz output
+
+    def final(poses, kp, i=None):
+        """The stages behind the lift over one track's poses; kp: the keypoints they were lifted from, as the lift took them."""
         if args.refine_poses:                          # poses carry no score: only a joint that is not finite is filled
             from .refine import refine_tracks
             poses = refine_tracks(poses, score=False)
         if args.fix_bones:                             # one track [N,17,3], or [P,N,17,3]: every track its own medians
             from .bones import fix_bone_lengths
             poses = fix_bone_lengths(poses, symmetric=args.fix_bones_symmetric)
+        if args.place:                                 # the keypoints in the layout the model saw; frames that cannot be placed come out NaN
+            from .place import place_poses
+            from .pose import coco_to_h36m
+            placed = place_poses(poses, coco_to_h36m(kp, device=poses.device) if args.layout == "coco" else kp, args.camera, metric_lengths=place_table,
+                                 iterations=args.place_iterations, delta=args.place_delta, device=poses.device)
+            poses = placed.poses
+            if i is not None:
+                extras[f"root_{i}"], extras[f"place_state_{i}"] = placed.root.cpu().numpy(), placed.state.cpu().numpy()
         return poses_to_world(poses, floor=args.world_floor, unit=args.world_unit) if args.world else poses
 
     if args.online:
         from .stream import StreamLifter
         lifter = StreamLifter(model, args.width, args.height, slots=1, flip=not args.no_flip, lag=args.lag, layout=args.layout)
         if isinstance(keypoints, list):
-            np.savez(args.out, **{f"track_{i}": final(lifter.replay(k)).cpu().numpy() for i, k in enumerate(keypoints)})
+            np.savez(args.out, **{f"track_{i}": final(lifter.replay(k), k, i).cpu().numpy() for i, k in enumerate(keypoints)}, **extras)
             print(f"replayed {len(keypoints)} tracks ({sum(len(k) for k in keypoints)} frames) tick by tick, lag {args.lag} -> {args.out}")
             return
-        poses = final(lifter.replay(keypoints))
+        poses = final(lifter.replay(keypoints), keypoints)
         np.save(args.out, poses.cpu().numpy())
         print(f"replayed {keypoints.shape} tick by tick, lag {args.lag} -> {tuple(poses.shape)}: {args.out}")
         return
     if isinstance(keypoints, list):
         poses = lift_tracks(model, keypoints, args.width, args.height, stride=args.stride, flip=not args.no_flip, max_windows=args.max_windows,
                             layout=args.layout)
-        np.savez(args.out, **{f"track_{i}": final(p).cpu().numpy() for i, p in enumerate(poses)})
+        np.savez(args.out, **{f"track_{i}": final(p, keypoints[i], i).cpu().numpy() for i, p in enumerate(poses)}, **extras)
         print(f"lifted {len(keypoints)} tracks ({sum(len(k) for k in keypoints)} frames) -> {args.out}")
         return
     poses = final(lift_track(model, keypoints, args.width, args.height, stride=args.stride, flip=not args.no_flip, max_windows=args.max_windows,
-                             layout=args.layout))
+                             layout=args.layout), keypoints)
     np.save(args.out, poses.cpu().numpy())
     print(f"lifted {keypoints.shape} -> {tuple(poses.shape)}: {args.out}")
 
