@@ -1133,6 +1133,28 @@ int kasf_op_dgrad_wg(const void* dy, int32_t Kd, const void* wt, const void* dxn
                      void* out, int32_t accumulate, float* dgamma, float* dbeta, float* dw, float* dbias, const void* proj_o, const float* proj_w,
                      const float* proj_b, const float* proj_ls, float* dproj_w, float* dproj_b, float* dproj_ls, int64_t M, void* wpart, int64_t wpart_bytes,
                      void* proj_part, int64_t proj_part_bytes, float* scratch, int64_t scratch_floats, void* stream);
+/* bf16 only: up to three weight gradients of one block in one streaming launch and one finishing launch, exactly the launch a backward stage makes for an
+ * attention or bone block (and nothing else):  dw[j] [N[j],128] fp32 += g[j]^T x[j],  g[j] [M,N[j]] and x[j] [M,128] bf16 token-major, N[j] in {128, 256, 384, 512},
+ * njobs in 1..3; g, x, N, dw and dbias are host arrays of njobs entries.  Each token split leaves one bf16 partial tile per job; the finishing launch adds them in a
+ * fixed order.
+ *   fin_job (-1, or a job index with N = 128): that job is the layer-scaled proj weight.  With G = g^T x and c = colsum(g):  dw += fin_ls[n] G[n][:],
+ *       dls [128] += <fin_w[n], G[n]> + fin_bias[n] c[n],  dbias[fin_job] [128] += fin_ls[n] c[n].  fin_w [128,128], fin_bias, fin_ls, dls and dbias[fin_job] are all
+ *       needed; dbias[j] of every other job must be NULL.
+ *   nred in 0..2 reductions ride in the finishing launch:  red_out[k][e] += sum over z < red_nparts[k] of red_part[k][z][e], e < red_elems[k] (bf16 parts, a multiple
+ *       of 128 elements); red_part, red_out, red_nparts, red_elems are host arrays of nred entries (NULL with nred = 0).
+ *   ext_part (optional; needs fin_job = -1 and njobs <= 2): the proj job when its ext_nparts >= 1 partial tiles [128][128] bf16 and rows ext_brow [ext_nparts][128] fp32
+ *       (colsum per tile) were left by another kernel: the algebra above with G = sum of the tiles, c = sum of the rows, into ext_dw, dls and ext_db; it needs the four
+ *       fin_* vectors.
+ *   partial: fp32-typed scratch of partial_floats >= sum over jobs of splits * N[j] * 128 (+ splits * 128 for the fin job), where tiles = sum N[j] / 128,
+ *       splits0 = min(ceil(248 / tiles), ceil(M / 128)), slice = ceil(ceil(M / splits0) / 128) * 128 and splits = ceil(M / slice).
+ * Every array is 16-byte aligned.  Error 2, nothing launched, in this order: njobs, nred or fin_job out of range; M >= 2^31; a NULL host array; N[j] not one of the four;
+ * a NULL or misaligned array; dbias on a job other than fin_job; a fin job with N != 128, or without its vectors or its dbias; ext_part together with fin_job >= 0 or
+ * njobs > 2; ext_part without ext_brow, ext_nparts >= 1, ext_dw, ext_db and the fin vectors (or one of those without ext_part); red_nparts < 1 or red_elems not a
+ * positive multiple of 128; partial_floats too small (M > 0).  M <= 0 returns 0 after the other checks. */
+int kasf_op_wgrad_jobs(int32_t njobs, const void* const* g, const void* const* x, const int32_t* N, float* const* dw, float* const* dbias, int32_t fin_job,
+                       const float* fin_w, const float* fin_bias, const float* fin_ls, float* dls, int64_t M, float* partial, int64_t partial_floats, int32_t nred,
+                       const void* const* red_part, float* const* red_out, const int32_t* red_nparts, const int32_t* red_elems, const void* ext_part,
+                       const float* ext_brow, int32_t ext_nparts, float* ext_dw, float* ext_db, void* stream);
 /* attention core (selfattention.py:18-41): q [*,ldq], k/v [*,ldkv] token-major; mode 0 spatial, 1 temporal; o and d_o are [M,128] (leading dimension 128).
  * The five kasf_op_attention_* entries refuse (error 2, nothing launched): a mode other than 0 or 1, batch < 0, n_frames < 1, batch * n_frames * 17 * max(384, the
  * largest leading dimension) >= 2^31 (the kernels index in 32 bits), a leading dimension below 128 (the columns each of q, k, v, dq, dk, dv addresses from its own
@@ -1175,6 +1197,25 @@ int kasf_op_attention_bwd_fused_do(const void* q, int64_t ldq, const void* k, co
 int kasf_op_attn_block_fwd(int32_t bone, const void* x, const void* x_limb, const float* ln_g, const float* ln_b, const float* lnl_g, const float* lnl_b, const void* wq,
                            const void* wkv, const void* wproj, const float* bproj, const float* ls1, void* q_save, void* kv_save, void* o_save, float* lse_save,
                            void* out, int32_t batch, int32_t n_frames, int32_t mode, void* stream);
+/* bf16, 8 heads, groups of <= 32 positions: the backward of one attention block (bone = 0) or bone cross-attention block (bone = 1) from x (, x_limb) and
+ * g_mid = d(loss)/d(x_mid) in one launch, finished as the engine finishes it (the streaming weight gradient with the proj job's tiles, then the column sink's flush):
+ *   xn_a = LN(x) (bone: xn_b = LN_limb(x_limb)) [M,128];  dq = dq | dk | dv [M,384] (bone: dq [M,128], dkv = dk | dv [M,256]) of the attention core on
+ *   q | k | v re-formed from xn and d_o = g_mid wproj_t_scaled^T;  out = g_mid + LNbwd(dq | dk | dv . wq) (bone: out_limb += LNbwd_limb(dk | dv . wkv));
+ *   dgamma, dbeta (dgamma_l, dbeta_l) += the LayerNorms' parameter gradients;  dw_mix [384,128] (bone [128,128]; dw_kv [256,128]) += dq^T xn;
+ *   with G = g_mid^T o and c = colsum(g_mid):  dproj_w += ls1[n] G[n][:],  dproj_b += ls1 . c,  dls1 += <proj_w[n], G[n]> + proj_b . c.
+ * wq: forward layout [384,128] (bone [128,128]), wkv [256,128], wq_t = wq^T [128,128] (bone only), wproj_t_scaled = (ls1 . Wproj)^T [128 in][128 out], all bf16;
+ * proj_w [128,128], proj_b, ls1 and the LayerNorm vectors fp32.  The eleven bone arguments (x_limb, lnl_g, lnl_b, wkv, wq_t, out_limb, dkv, xn_b, dgamma_l, dbeta_l,
+ * dw_kv) are all given with bone = 1 and all NULL with bone = 0.  out must not alias x or x_limb.
+ * Scratch, 16-byte aligned: partial, partial_floats >= splits * 384 * 128 (splits as kasf_op_wgrad_jobs states it, for M = batch * n_frames * 17 and three tiles);
+ * proj_part, proj_part_bytes >= 256 * 128 * 128 * 2 + 256 * 128 * 4 (as kasf_op_dgrad_wg); scratch, scratch_floats >= active * (bone ? 512 : 256) rounded up to 64,
+ * active = ceil(groups / ceil(groups / min(groups, 256))) workgroups that own a group: with less the call returns error 6 and launches nothing.
+ * Error 2 in this order: bone, mode, batch < 0, n_frames < 1, the 2^31 index bound, groups of more than 32 positions, the bone arguments, a NULL pointer, out
+ * aliasing an input, alignment, scratch_floats < 1, proj_part_bytes, partial_floats.  batch = 0 returns 0 after the checks. */
+int kasf_op_attn_block_bwd(int32_t bone, const void* x, const void* x_limb, const void* g_mid, const float* ln_g, const float* ln_b, const float* lnl_g, const float* lnl_b,
+                           const void* wq, const void* wkv, const void* wq_t, const void* wproj_t_scaled, const float* proj_w, const float* proj_b, const float* ls1,
+                           void* out, void* out_limb, void* dq, void* dkv, void* xn_a, void* xn_b, float* dgamma, float* dbeta, float* dgamma_l, float* dbeta_l,
+                           float* dw_mix, float* dw_kv, float* dproj_w, float* dproj_b, float* dls1, float* partial, int64_t partial_floats, void* proj_part,
+                           int64_t proj_part_bytes, float* scratch, int64_t scratch_floats, int32_t batch, int32_t n_frames, int32_t mode, void* stream);
 /* ---- the GCN mixer on its own (ABI 12; modules/graph.py:19-134 between the U | V Linear and the residual of KASportsFormer.py:109) ----
  * M = batch * n_frames * 17 tokens in [batch][frame][joint] order.  mode 0 = spatial (fixed skeleton adjacency, BatchNorm channel = joint, 17 nodes), 1 = temporal
  * (per (clip, joint) track: S = xn xn^T, every frame whose similarity reaches the neighbour_num-th largest of its row is a neighbour -- ties are all kept, so a row's

@@ -158,12 +158,14 @@ SIGNATURES = {
     "kasf_op_wgrad": (_i32, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
     "kasf_op_dgrad_lnbwd": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
     "kasf_op_dgrad_wg": (_i32, [_vp, _i32] + [_vp] * 7 + [_i32] + [_vp] * 11 + [_i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "kasf_op_wgrad_jobs": (_i32, [_i32] + [_vp] * 5 + [_i32] + [_vp] * 4 + [_i64, _vp, _i64, _i32] + [_vp] * 6 + [_i32, _vp, _vp, _vp]),
     "kasf_op_attention_fwd": (_i32, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _vp]),
     "kasf_op_attention_bwd": (_i32, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "kasf_op_attention_fwd_heads": (_i32, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp]),
     "kasf_op_attention_bwd_heads": (_i32, [_i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "kasf_op_attention_bwd_fused_do": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "kasf_op_attn_block_fwd": (_i32, [_i32] + [_vp] * 16 + [_i32, _i32, _i32, _vp]),
+    "kasf_op_attn_block_bwd": (_i32, [_i32] + [_vp] * 30 + [_i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp]),
     "kasf_op_gcn_fwd": (_i32, [_i32] + [_vp] * 13 + [_i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "kasf_op_gcn_bwd": (_i32, [_i32] + [_vp] * 12 + [_i32, _i32, _i32, _i32, _vp]),
     "kasf_op_misc_scratch_floats": (_i64, [_i32, _i64]),

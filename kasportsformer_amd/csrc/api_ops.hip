@@ -182,6 +182,64 @@ int kasf_op_dgrad_wg(const void* dy, int32_t Kd, const void* wt, const void* dxn
     else kasf_launch_bf16_reduce(s, 1, &red);
     return api_done(ms.finish(s));
 }
+// the streaming weight-gradient launch of an attention / bone block and its finish (engine.hip, block_backward: kasf_launch_wgrad_jobs and nothing else).  The launcher
+// returns false for what it cannot run; every such call is refused here first, with the launcher's own split arithmetic restated for the scratch size.
+int kasf_op_wgrad_jobs(int32_t njobs, const void* const* g, const void* const* x, const int32_t* N, float* const* dw, float* const* dbias, int32_t fin_job,
+                       const float* fin_w, const float* fin_bias, const float* fin_ls, float* dls, int64_t M, float* partial, int64_t partial_floats, int32_t nred,
+                       const void* const* red_part, float* const* red_out, const int32_t* red_nparts, const int32_t* red_elems, const void* ext_part,
+                       const float* ext_brow, int32_t ext_nparts, float* ext_dw, float* ext_db, void* stream) {
+    const char* who = "wgrad_jobs";
+    if (njobs < 1 || njobs > 3) return refuse(who, "njobs must be in 1..3");
+    if (nred < 0 || nred > 2) return refuse(who, "nred must be in 0..2");
+    if (fin_job < -1 || fin_job >= njobs) return refuse(who, "fin_job must be -1 or the index of a job");
+    if (M >= ((int64_t)1 << 31)) return refuse(who, "M must stay below 2^31");
+    if (!g || !x || !N || !dw || !dbias || !partial || (nred > 0 && (!red_part || !red_out || !red_nparts || !red_elems))) return refuse_null();
+    int tiles = 0;
+    for (int j = 0; j < njobs; ++j) {
+        if (N[j] != 128 && N[j] != 256 && N[j] != 384 && N[j] != 512) return refuse(who, "N[j] must be 128, 256, 384 or 512");
+        tiles += N[j] / 128;
+    }
+    for (int j = 0; j < njobs; ++j)
+        if (!g[j] || !x[j] || !dw[j]) return refuse_null();
+    for (int k = 0; k < nred; ++k)
+        if (!red_part[k] || !red_out[k]) return refuse_null();
+    const char* align = "g[j], x[j], dw[j], dbias[j], the fin vectors, partial, red_part[k], red_out[k] and the ext arrays must be 16-byte aligned";
+    for (int j = 0; j < njobs; ++j)
+        if (misaligned16(g[j]) || misaligned16(x[j]) || misaligned16(dw[j]) || misaligned16(dbias[j])) return refuse(who, align);
+    for (int k = 0; k < nred; ++k)
+        if (misaligned16(red_part[k]) || misaligned16(red_out[k])) return refuse(who, align);
+    for (const void* p : {(const void*)fin_w, (const void*)fin_bias, (const void*)fin_ls, (const void*)dls, (const void*)partial, ext_part, (const void*)ext_brow,
+                          (const void*)ext_dw, (const void*)ext_db})
+        if (misaligned16(p)) return refuse(who, align);
+    for (int j = 0; j < njobs; ++j)
+        if (dbias[j] != nullptr && j != fin_job) return refuse(who, "dbias[j] is given on the fin job only (a bias gradient is finished with the layer-scale algebra)");
+    if (fin_job >= 0 && (N[fin_job] != 128 || !fin_w || !fin_bias || !fin_ls || !dls || !dbias[fin_job]))
+        return refuse(who, "a fin job has N = 128 and needs fin_w, fin_bias, fin_ls, dls and its dbias");
+    if (ext_part != nullptr && (fin_job >= 0 || njobs > 2)) return refuse(who, "ext_part goes with fin_job = -1 and at most two jobs");
+    const int next = (ext_part != nullptr) + (ext_brow != nullptr) + (ext_nparts >= 1) + (ext_dw != nullptr) + (ext_db != nullptr);
+    if (next != 0 && (next != 5 || !fin_w || !fin_bias || !fin_ls || !dls))
+        return refuse(who, "ext_part, ext_brow, ext_nparts >= 1, ext_dw and ext_db go together, with fin_w, fin_bias, fin_ls and dls");
+    for (int k = 0; k < nred; ++k) {
+        if (red_nparts[k] < 1) return refuse(who, "red_nparts[k] must be >= 1");
+        if (red_elems[k] < 128 || red_elems[k] % 128 != 0) return refuse(who, "red_elems[k] must be a positive multiple of 128");
+    }
+    if (M <= 0) return 0;
+    // kasf_launch_wgrad_jobs at full width: fewest token splits that fill the chip, slices of whole 128-row tiles
+    int64_t splits = (248 + tiles - 1) / tiles;
+    splits = std::min(splits, (M + 127) / 128);
+    const int64_t slice = ((M + splits - 1) / splits + 127) / 128 * 128;
+    splits = (M + slice - 1) / slice;
+    int64_t need = 0;
+    for (int j = 0; j < njobs; ++j) need += splits * N[j] * 128 + (dbias[j] != nullptr ? splits * N[j] : 0);
+    if (partial_floats < need) return refuse(who, "partial_floats is below splits * N[j] * 128 per job (+ splits * 128 for the fin job)");
+    KasfBf16Reduce red[2];
+    for (int k = 0; k < nred; ++k) red[k] = KasfBf16Reduce{red_part[k], red_out[k], red_nparts[k], red_elems[k]};
+    const int Ns[3] = {N[0], njobs > 1 ? N[1] : 0, njobs > 2 ? N[2] : 0};
+    if (!kasf_launch_wgrad_jobs((hipStream_t)stream, njobs, g, x, Ns, dw, dbias, fin_job, fin_w, fin_bias, fin_ls, dls, M, partial, partial_floats, nred, red, ext_part,
+                                ext_brow, ext_nparts, ext_dw, ext_db))
+        return kasf_set_error(3, "wgrad_jobs: the launcher declined a call that passed every check");
+    return api_done();
+}
 // ---- the attention kernels on their own (kasf.h, kasf_op_attention_fwd ... kasf_op_attn_block_fwd): what the five core entries check alike, after their dtype ----
 struct AttnLd { const char* name; int64_t ld; };
 static int attn_core_check(const char* who, int32_t mode, int32_t batch, int32_t n_frames, std::initializer_list<AttnLd> lds, std::initializer_list<const void*> ptrs) {
@@ -266,6 +324,63 @@ int kasf_op_attn_block_fwd(int32_t bone, const void* x, const void* x_limb, cons
                                     mode, lse_save))
         return refuse(who, group);             // (the launcher's own `false`: the same bound)
     return api_done(api_launchers_spoke());
+}
+// the fused attention block's backward with the launches that finish it, exactly as block_backward (engine.hip) sequences them in bf16 mode with 8 heads:
+// kasf_launch_attn_block_bwd on a local sink, kasf_launch_wgrad_jobs with the ext operands it left, the sink's flush on the same stream
+int kasf_op_attn_block_bwd(int32_t bone, const void* x, const void* x_limb, const void* g_mid, const float* ln_g, const float* ln_b, const float* lnl_g, const float* lnl_b,
+                           const void* wq, const void* wkv, const void* wq_t, const void* wproj_t_scaled, const float* proj_w, const float* proj_b, const float* ls1,
+                           void* out, void* out_limb, void* dq, void* dkv, void* xn_a, void* xn_b, float* dgamma, float* dbeta, float* dgamma_l, float* dbeta_l,
+                           float* dw_mix, float* dw_kv, float* dproj_w, float* dproj_b, float* dls1, float* partial, int64_t partial_floats, void* proj_part,
+                           int64_t proj_part_bytes, float* scratch, int64_t scratch_floats, int32_t batch, int32_t n_frames, int32_t mode, void* stream) {
+    const char* who = "attn_block_bwd";
+    if (bone != 0 && bone != 1) return refuse(who, "bone must be 0 (self-attention) or 1 (bone cross-attention)");
+    if (int rc = refuse_attn_shape(who, mode, batch, n_frames)) return rc;
+    const int L = mode == 0 ? 17 : n_frames;
+    if (L > 32) return refuse(who, "the fused backward covers groups of at most 32 positions (temporal: n_frames <= 32)");
+    const int nbone = (x_limb != nullptr) + (lnl_g != nullptr) + (lnl_b != nullptr) + (wkv != nullptr) + (wq_t != nullptr) + (out_limb != nullptr) + (dkv != nullptr) +
+                      (xn_b != nullptr) + (dgamma_l != nullptr) + (dbeta_l != nullptr) + (dw_kv != nullptr);
+    if (nbone != (bone ? 11 : 0))
+        return refuse(who, "x_limb, lnl_g, lnl_b, wkv, wq_t, out_limb, dkv, xn_b, dgamma_l, dbeta_l and dw_kv are all given with bone = 1 and all NULL with bone = 0");
+    if (!x || !g_mid || !ln_g || !ln_b || !wq || !wproj_t_scaled || !proj_w || !proj_b || !ls1 || !out || !dq || !xn_a || !dgamma || !dbeta || !dw_mix || !dproj_w ||
+        !dproj_b || !dls1 || !partial || !proj_part || !scratch)
+        return refuse_null();
+    if (out == x || (bone && out == x_limb)) return refuse(who, "out must not alias x or x_limb (a workgroup prefetches the next group's rows while it stores)");
+    for (const void* p : {x, x_limb, g_mid, wq, wkv, wq_t, wproj_t_scaled, (const void*)proj_w, (const void*)out, (const void*)out_limb, (const void*)dq, (const void*)dkv,
+                          (const void*)xn_a, (const void*)xn_b, (const void*)dw_mix, (const void*)dw_kv, (const void*)dproj_w, (const void*)partial, (const void*)proj_part})
+        if (misaligned16(p)) return refuse(who, "every bf16 array, proj_w, dw_mix, dw_kv, dproj_w, partial and proj_part must be 16-byte aligned");
+    if (int rc = misc_scratch_check(scratch, scratch_floats)) return rc;
+    const int64_t proj_tile_bytes = (int64_t)256 * 128 * 128 * 2;
+    if (proj_part_bytes < proj_tile_bytes + 256 * 128 * 4) return refuse(who, "proj_part_bytes must be at least 256 * 128 * 128 * 2 + 256 * 128 * 4");
+    // kasf_launch_wgrad_jobs at full width over the block's streaming jobs (self: dq | dk | dv, 3 tiles; bone: dq and dk | dv, 1 + 2 tiles), no fin job
+    const int64_t M = (int64_t)batch * n_frames * 17;
+    int64_t splits = std::min<int64_t>((248 + 2) / 3, (M + 127) / 128);
+    if (splits > 0) {
+        const int64_t slice = ((M + splits - 1) / splits + 127) / 128 * 128;
+        splits = (M + slice - 1) / slice;
+    }
+    if (partial_floats < splits * 384 * 128) return refuse(who, "partial_floats is below splits * 384 * 128, the streaming weight gradient's partial tiles");
+    if (batch == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    MiscSink ms(scratch, scratch_floats);
+    float* pbrow = (float*)((char*)proj_part + proj_tile_bytes);
+    api_clear_error();
+    const int np = kasf_launch_attn_block_bwd(s, bone, x, x_limb, g_mid, ln_g, ln_b, lnl_g, lnl_b, wq, wkv, wq_t, wproj_t_scaled, out, out_limb, dq, dkv, xn_a, xn_b, dgamma,
+                                              dbeta, dgamma_l, dbeta_l, ms.p, proj_part, pbrow, batch, n_frames, mode);
+    if (np <= 0) {
+        if (ms.sink.overflow) return ms.finish(s);      // scratch below one row of dgamma | dbeta (| the limb pair) per active workgroup: error 6, nothing launched
+        return kasf_set_error(3, "attn_block_bwd: the launcher declined a call that passed every check");
+    }
+    const void* Gs[2] = {dq, dkv};
+    const void* Xs[2] = {xn_a, xn_b};
+    const int Ns[2] = {bone ? 128 : 384, 256};
+    float* dWs[2] = {dw_mix, dw_kv};
+    float* dbs[2] = {nullptr, nullptr};
+    if (!kasf_launch_wgrad_jobs(s, bone ? 2 : 1, Gs, Xs, Ns, dWs, dbs, -1, proj_w, proj_b, ls1, dls1, M, partial, partial_floats, 0, nullptr, proj_part, pbrow, np, dproj_w,
+                                dproj_b)) {
+        ms.finish(s);
+        return kasf_set_error(3, "attn_block_bwd: the weight-gradient launcher declined a call that passed every check");
+    }
+    return api_done(ms.finish(s));
 }
 // ---- the GCN mixer on its own (kasf.h, kasf_op_gcn_fwd / kasf_op_gcn_bwd): the launch sequence and `count` of block_forward / block_backward ----
 static_assert(KASF_GCN_STAT_WORDS == KASF_STAT_SLOTS * KASF_STAT_LD * KASF_STAT_WORDS, "kasf.h and kernels.h disagree on the size of a statistics buffer");

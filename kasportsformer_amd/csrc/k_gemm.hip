@@ -841,7 +841,9 @@ void kasf_launch_bf16_reduce(hipStream_t s, int nred, const KasfBf16Reduce* red)
 
 // Up to three bf16 weight gradients  dW_j[N_j][128] += G_j^T X_j  (dense operands: ldg = N_j, ldx = 128) in one streaming launch plus one
 // finishing launch.  fin_* of job j (optional): the layer-scale algebra of k_finalize_ls applied to that job (the proj weight).
-// Returns false (nothing launched) when the scratch is too small.
+// Returns false (nothing launched) when the scratch is too small, and for arguments the two kernels cannot run: njobs, nred or M out of range; a bias gradient on a job
+// that is not the fin job; fin_job >= njobs, a fin job with N != 128, without its dbias or without one of fin_W / fin_bias / fin_ls / fin_dls; ext_part with a fin
+// job, with three jobs or without ext_brow, ext_nparts >= 1, ext_dW and ext_db.
 bool kasf_launch_wgrad_jobs(hipStream_t s, int njobs, const void* const* G, const void* const* X, const int* N, float* const* dW, float* const* dbias,
                             int fin_job, const float* fin_W, const float* fin_bias, const float* fin_ls, float* fin_dls, int64_t M, float* partial,
                             int64_t partial_floats, int nred, const KasfBf16Reduce* red, const void* ext_part, const float* ext_brow, int ext_nparts,
@@ -850,6 +852,9 @@ bool kasf_launch_wgrad_jobs(hipStream_t s, int njobs, const void* const* G, cons
     // workgroup): it takes no part in the streaming launch and is finished -- fin_W / fin_bias / fin_ls / fin_dls are then ITS layer-scale algebra -- by the same finish launch
     if (njobs < 1 || njobs > 3 || M <= 0 || nred < 0 || nred > 2) return false;
     if (ext_part != nullptr && (njobs > 2 || fin_job >= 0 || ext_brow == nullptr || ext_nparts < 1 || ext_dW == nullptr || ext_db == nullptr)) return false;
+    // a fin job's finishing workgroups read its brow rows, W, bias and ls and write its db and dls whenever W is given: all of them, or no fin job
+    if (fin_job >= njobs) return false;
+    if (fin_job >= 0 && (N[fin_job] != 128 || dbias[fin_job] == nullptr || fin_W == nullptr || fin_bias == nullptr || fin_ls == nullptr || fin_dls == nullptr)) return false;
     int tiles = 0;
     for (int j = 0; j < njobs; ++j) tiles += N[j] / 128;
     const int target = kasf_narrow_grid(KASF_NG_WGRAD, 248, M);

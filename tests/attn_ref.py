@@ -54,6 +54,8 @@ BAR32 = {
     "fused_do.dq": 4e-5, "fused_do.dk": 4e-5, "fused_do.dv": 7e-5,
     "kt.dq": 2e-5, "kt.dk": 2e-5, "kt.dv": 6e-5,
     "block.q": 3e-5, "block.k": 3e-5, "block.v": 3e-5, "block.o": 5e-5, "block.lse": 2e-6, "block.x_mid": 8e-6,
+    # the block backward, stage by stage (measure_bwd: every listed shape, both forms)
+    "bwd.xn": 3e-6, "bwd.dq": 8e-6, "bwd.dk": 8e-6, "bwd.dv": 6e-6, "bwd.out": 2e-5, "bwd.dgamma": 4e-6, "bwd.dw": 4e-6, "bwd.dproj": 6e-6, "bwd.dproj_b": 1e-6,
 }
 # (two digits where one would lift c16 past 3e-2.  lse and x_mid have no 16-bit point in front of them once q | k | v and o are taken as stored: their c is the fp32 bar)
 DIST16 = {
@@ -62,6 +64,8 @@ DIST16 = {
     "fused_do.dq": 1.2e-2, "fused_do.dk": 1.1e-2, "fused_do.dv": 9e-3,
     "kt.dq": 1.5e-2, "kt.dk": 1.1e-2, "kt.dv": 8e-3,
     "block.q": 4e-3, "block.k": 4e-3, "block.v": 4e-3, "block.o": 3e-3, "block.lse": 0.0, "block.x_mid": 0.0,
+    # (xn and dproj_b = ls1 . colsum(g_mid) have no 16-bit point in front of them)
+    "bwd.xn": 0.0, "bwd.dq": 1.4e-2, "bwd.dk": 1.3e-2, "bwd.dv": 1e-2, "bwd.out": 3e-3, "bwd.dgamma": 5e-3, "bwd.dw": 3e-3, "bwd.dproj": 7e-3, "bwd.dproj_b": 0.0,
 }
 
 
@@ -398,6 +402,150 @@ def block_ref(i, B, T, mode, dtype=F64, R=Exact, chunk=2048, given=None):
                 x_mid=x + c("ls1") * ((given["o"].to(dtype) if "o" in given else o) @ c("wproj").T + c("bproj")))
 
 
+# ------------------------------------------------------------------------------------------------ block backward (k_attn_bwd_f.hip through kasf_op_attn_block_bwd)
+def block_bwd_grid(B, T, mode):
+    """kasf_launch_attn_block_bwd at full width: -> (grid, groups per workgroup, workgroups that own a group: the sink's rows and the proj job's tiles)"""
+    groups = n_groups(B, T, mode)
+    grid = min(groups, 256)
+    per = (groups + grid - 1) // grid
+    return grid, per, (groups + per - 1) // per
+
+
+def bwd_planted_groups(B, T, mode):
+    """first group, last group, and the second group of workgroup 0's walk"""
+    groups = n_groups(B, T, mode)
+    return sorted({0, groups - 1} | ({1} if block_bwd_grid(B, T, mode)[1] > 1 else set()))
+
+
+@functools.lru_cache(maxsize=2)
+def block_bwd_inputs(bone, mode, B, T):
+    """The operands of the block backward.  No peaked or offset head (as the hand-over cases): zero-query head 3, zero-key head 4, v x 100 head 5; the q and k weight
+    rows carry a score scale of 0.5 (with unit-variance q and k the `Rounded` dq | dk | dv alone are 1.7e-2 / 1.8e-2 / 1.3e-2 from fp64: 2 x that is past the 3e-2
+    cap).  LayerNorm plants as block_inputs; groups shorter than 8 positions carry two planted rows (constant, zero) instead of five: four planted rows of four give
+    equal keys and nearly cancelling terms (dk 6.9e-2 away)."""
+    g = gen(24, bone, mode, B, T)
+    M, L = B * T * J, group_len(T, mode)
+    r = lambda *s: torch.randn(*s, generator=g)
+    x, xl = r(M, 128), r(M, 128)
+    last = n_groups(B, T, mode) - 1
+    n_plants = min(5, L) if L >= 8 else min(2, L)
+    rows = [token_of(G, L - 1 - p if G == last and G > 0 else p, T, mode) for G in bwd_planted_groups(B, T, mode) for p in range(n_plants)]
+    where = plant_rows(x, rows, g)
+    where_l = plant_rows(xl, rows[::-1], g)
+    ln_g, ln_b = ln_params(g)
+    lnl_g, lnl_b = ln_params(g)
+    wq, wkv = r(128 if bone else 384, 128) * 128 ** -0.5, r(256, 128) * 128 ** -0.5
+    kw, ko, vo = (wkv, 0, 128) if bone else (wq, 128, 256)
+    wq[:128] *= 0.5 ** 0.5                                   # q and k share the score scale of 0.5
+    kw[ko:ko + 128] *= 0.5 ** 0.5
+    wq[16 * 3:16 * 4] = 0.0
+    kw[ko + 16 * 4:ko + 16 * 5] = 0.0
+    kw[vo + 16 * 5:vo + 16 * 6] *= 100.0
+    proj_w, ls1 = r(128, 128) * 128 ** -0.5, 0.5 + torch.rand(128, generator=g)
+    return dict(x=x, xl=xl if bone else None, ln_g=ln_g, ln_b=ln_b, lnl_g=lnl_g if bone else None, lnl_b=lnl_b if bone else None, wq=wq, wkv=wkv if bone else None,
+                proj_w=proj_w, proj_b=0.5 * r(128), ls1=ls1, wts=(ls1[:, None] * proj_w).T.contiguous(), g_mid=r(M, 128), outl0=r(M, 128) if bone else None,
+                where=where, where_l=where_l, _model=("x", "xl", "wq", "wkv", "wts", "g_mid", "outl0"))
+
+
+def block_bwd_ref(i, B, T, mode, dtype=F64, R=Exact, given=None):
+    """Every output of kasf_op_attn_block_bwd, stage by stage.  16-bit points: LN(x) (LN_limb(x_limb)) as stored and as operand; q | k | v and d_o = g_mid wts^T as
+    the core's operands; core_bwd's P and dS; dq | dk | dv as stored and as operands; the data gradient's staging tile bf16(dq | dk | dv . W) in front of the LayerNorm
+    backward; one bf16 tile per token split of the streaming weight gradient (dense_ref.jobs_splits); o = bf16(P v) as the proj gradient's operand and one bf16 tile
+    of G = g_mid^T o per workgroup (block_bwd_grid).  given: {"xn", "xnl"} and / or {"dq", "dk", "dv"} [M, 128] as a device stored them: the later stages then run
+    on those (the earlier outputs are returned as computed all the same)."""
+    from tests.dense_ref import jobs_splits, ln_bwd, ls_algebra
+    given = given or {}
+    c = lambda n: i[n].to(dtype) if i.get(n) is not None else None
+    take = lambda n, t: given[n].to(dtype) if n in given else R.bf(t)
+    bone = i["xl"] is not None
+    x, g, wq, wkv = c("x"), c("g_mid"), c("wq"), c("wkv")
+    out = dict(xn=ln(x, c("ln_g"), c("ln_b")))
+    xn = take("xn", out["xn"])
+    if bone:
+        out["xnl"] = ln(c("xl"), c("lnl_g"), c("lnl_b"))
+        xnl = take("xnl", out["xnl"])
+        q, (k, v) = R.bf(xn @ wq.T), R.bf(xnl @ wkv.T).split(128, dim=1)
+    else:
+        q, k, v = R.bf(xn @ wq.T).split(128, dim=1)
+    qg, kg, vg, dog = (to_groups(t, B, T, mode) for t in (q, k, v, R.bf(g @ c("wts").T)))
+    gr = core_bwd(qg, kg, vg, dog, 8, R)
+    for n in ("dq", "dk", "dv"):
+        out[n] = from_groups(gr[n], B, T, mode)
+    dq, dk, dv = (take(n, out[n]) for n in ("dq", "dk", "dv"))
+    if bone:
+        dxn, dkv = R.bf(dq @ wq), torch.cat([dk, dv], 1)
+        dxl, out["dgamma_l"], out["dbeta_l"] = ln_bwd(R.bf(dkv @ wkv), c("xl"), c("lnl_g"))
+        out["out_limb"] = c("outl0") + dxl
+    else:
+        dxn = R.bf(torch.cat([dq, dk, dv], 1) @ wq)
+    dx, out["dgamma"], out["dbeta"] = ln_bwd(dxn, x, c("ln_g"))
+    out["out"] = g + dx
+    splits, sl = jobs_splits(x.shape[0], (128, 256) if bone else (384,))
+    tn = lambda A, Bm: sum(R.bf(A[z * sl:(z + 1) * sl].T @ Bm[z * sl:(z + 1) * sl]) for z in range(splits)) if R.rounded else A.T @ Bm
+    if bone:
+        out["dw_mix"], out["dw_kv"] = tn(dq, xn), tn(dkv, xnl)
+    else:
+        out["dw_mix"] = tn(torch.cat([dq, dk, dv], 1), xn)
+    og = R.bf(_merge(R.bf(torch.softmax(_scores(qg, kg, 8), -1)) @ _heads(vg, 8)))
+    gg = to_groups(g, B, T, mode)
+    _, per, active = block_bwd_grid(B, T, mode)
+    tile = lambda a, b: torch.einsum("glk,glc->kc", a, b)
+    Gm = sum(R.bf(tile(gg[w * per:(w + 1) * per], og[w * per:(w + 1) * per])) for w in range(active)) if R.rounded else tile(gg, og)
+    out["dproj_w"], out["dproj_b"], out["dls1"] = ls_algebra(Gm, g.sum(0), c("proj_w"), c("proj_b"), c("ls1"))
+    return out
+
+
+# block backward: name -> [(mode, B, T)]; spatial is listed by frames (257 frames: per = 2, 129 active workgroups and 127 that return at once; 513: per = 3);
+# 272 and 527 temporal groups: the second and third walk, a short last range and empty workgroups
+BLOCK_BWD = {
+    "spatial": [(0, f, 1) for f in (1, 2, 255, 256, 257, 513)],
+    "t9": [(1, 1, T) for T in (4, 9, 16, 17)] + [(1, 16, 17)],
+    "t16": [(1, 1, T) for T in (18, 27, 31, 32)] + [(1, 16, 27), (1, 31, 32)],
+}
+BWD_STAGES = {"xn": ("xn", "xnl"), "dq": ("dq",), "dk": ("dk",), "dv": ("dv",), "out": ("out", "out_limb"), "dgamma": ("dgamma", "dbeta", "dgamma_l", "dbeta_l"),
+              "dw": ("dw_mix", "dw_kv"), "dproj": ("dproj_w", "dls1"), "dproj_b": ("dproj_b",)}
+BWD_STAGE_PASS = {"xn": 0, "dq": 1, "dk": 1, "dv": 1}          # the pass in which a stage is judged: 0 from x, 1 on the stored LN(x), 2 on the stored LN(x) and dq | dk | dv
+MEASURE_BWD = sorted({c for cases in BLOCK_BWD.values() for c in cases})          # every listed shape: the whole measurement takes 15 s
+
+
+def bwd_errs(a, b, B, T, mode, excess):
+    """{output: distance} of two evaluations in the measures of the GPU test: dq | dk | dv per (token, head), the token-major outputs per row (`excess`: over the
+    stored output's own bf16 ulp), the reductions per tensor"""
+    from tests.dense_ref import rel_err
+    z = handover_zero(B, T, mode)
+    out = {}
+    for n in b:
+        if n in ("dq", "dk", "dv"):
+            out[n] = head_err(to_groups(a[n], B, T, mode), to_groups(b[n], B, T, mode), 8, z.get(n), excess=excess)[0]
+        elif n in ("xn", "xnl", "out", "out_limb"):
+            out[n] = (row_excess if excess else row_err)(a[n], b[n])[0]
+        else:
+            out[n] = rel_err(a[n], b[n])
+    return out
+
+
+def measure_bwd(which):
+    """bwd.<stage> -> the worst distance over MEASURE_BWD and both forms, each stage on what the stage before stored (the `Rounded` evaluation's values in bf16)"""
+    f32 = which == "fp32"
+    lo, R = (torch.float32, Exact) if f32 else (F64, Rounded)
+    out = {}
+    for mode, B, T in MEASURE_BWD:
+        for bone in (0, 1):
+            i = stored(block_bwd_inputs(bone, mode, B, T), "bf16")
+            st = {}
+            for k, names in enumerate((("xn", "xnl"), ("dq", "dk", "dv"), ())):
+                a, b = block_bwd_ref(i, B, T, mode, lo, R, st), block_bwd_ref(i, B, T, mode, given=st)
+                e = bwd_errs(a, b, B, T, mode, excess=not f32)
+                for stage, outs in BWD_STAGES.items():
+                    if BWD_STAGE_PASS.get(stage, 2) == k:
+                        for n in outs:
+                            if n in e:
+                                out[f"bwd.{stage}"] = max(out.get(f"bwd.{stage}", 0.0), e[n])
+                dev = a if not f32 else block_bwd_ref(i, B, T, mode, F64, Rounded, st)
+                st = dict(st, **{n: dev[n].to(torch.bfloat16).to(F64) for n in names if n in dev})
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ the CPU measurements behind BAR32 and DIST16
 # the largest listed shapes, and the shortest groups (few keys: the least averaging)
 MEASURE_CORE = {"fp32": [(8, 1, CORE_B, 256), (2, 1, CORE_B, 157), (16, 1, CORE_B, 81), (4, 1, CORE_B, 81), (8, 1, CORE_B, 4), (16, 1, CORE_B, 4), (4, 1, CORE_B, 4), (2, 1, CORE_B, 4)],
@@ -461,4 +609,5 @@ def measure(which):
             st["o"] = a["o"].to(torch.bfloat16).to(F64)                                    # stage 3: the projection and the residual on the stored o
             a, b = block_ref(i, B, T, mode, lo, R, given=st), block_ref(i, B, T, mode, given=st)
             worst("block.x_mid", row_err(a["x_mid"], b["x_mid"])[0])
+    out.update(measure_bwd(which))
     return out

@@ -83,6 +83,16 @@ def ptrs(*bufs):
     return out
 
 
+def aptrs(*offsets):
+    """A host array of pointers (kasf_op_wgrad_jobs' per-job arrays): entry k points `offsets[k]` bytes behind a 64-byte boundary of a fresh buffer, or is NULL for None."""
+    out = (C.c_void_p * len(offsets))()
+    for k, off in enumerate(offsets):
+        if off is not None:
+            _KEEP.append(C.create_string_buffer(BUF_BYTES + 64))
+            out[k] = (C.addressof(_KEEP[-1]) + 63) // 64 * 64 + off
+    return out
+
+
 COCO_PAIRS = (0, 2, 1, 4, 3, 6, 5, 8, 7, 10, 9, 12, 11, 14, 13, 16, 15)
 NOT_INVOLUTION = (1, 2, 0) + tuple(range(3, 17))
 _PARTNER = [("partner_range", dict(partner=i32(17, *COCO_PAIRS[1:]))), ("partner_neg", dict(partner=i32(-1, *COCO_PAIRS[1:]))),
@@ -114,6 +124,15 @@ _NO_PROJ = dict(proj_o=None, proj_w=None, proj_b=None, proj_ls=None, dproj_w=Non
 _WG_TILES = 256 * 128 * 128 * 2
 _PROJ = dict({p: BUF for p in _NO_PROJ}, proj_part_bytes=_WG_TILES + 256 * 128 * 4)
 
+# kasf_op_wgrad_jobs: one job of N = 128 without a fin job (its host arrays hold three entries, so that a case may raise njobs), the fin job's and the ext job's
+# arguments, and one reduction
+_JOBS_BASE = dict(njobs=1, g=aptrs(0, 0, 0), x=aptrs(0, 0, 0), N=i32(128, 128, 128), dw=aptrs(0, 0, 0), dbias=aptrs(None, None, None), fin_job=-1, M=1,
+                  partial_floats=128 * 128, nred=0, fin_w=None, fin_bias=None, fin_ls=None, dls=None, red_part=None, red_out=None, red_nparts=None, red_elems=None,
+                  ext_part=None, ext_brow=None, ext_nparts=0, ext_dw=None, ext_db=None)
+_JOBS_FIN = dict(fin_job=0, dbias=aptrs(0, None, None), fin_w=BUF, fin_bias=BUF, fin_ls=BUF, dls=BUF)
+_JOBS_EXT = dict(ext_part=BUF, ext_brow=BUF, ext_nparts=1, ext_dw=BUF, ext_db=BUF)
+_JOBS_RED = dict(nred=1, red_part=aptrs(0), red_out=aptrs(0), red_nparts=i32(1), red_elems=i32(128))
+
 # the attention entries: what kasf_op_attention_* check alike behind their dtype (api_ops.hip, attn_core_check), and the block forward's absent / present operands
 _ATTN_BASE = dict(dtype=0, batch=1, n_frames=4, ldq=128, ldkv=128)
 _ATTN_BWD_BASE = dict(_ATTN_BASE, lddq=128, lddkv=128)
@@ -125,6 +144,10 @@ _ATTN_ALIGN = [("align", dict(q=OFF(8))), ("align_o", dict(o=OFF(4)), "align")]
 _ATTN_FUSED_BASE = {k: v for k, v in _ATTN_BWD_BASE.items() if k != "dtype"}
 _BLK_BASE = dict(bone=0, batch=1, n_frames=4, mode=0, x_limb=None, lnl_g=None, lnl_b=None, wkv=None, q_save=None, kv_save=None, o_save=None, lse_save=None)
 _BLK_BONE = dict(bone=1, x_limb=BUF, lnl_g=BUF, lnl_b=BUF, wkv=BUF)
+# kasf_op_attn_block_bwd: one spatial frame of the self-attention form (68 tokens: one split), the eleven arguments of the bone form absent
+_BWD_BONE_ARGS = ("x_limb", "lnl_g", "lnl_b", "wkv", "wq_t", "out_limb", "dkv", "xn_b", "dgamma_l", "dbeta_l", "dw_kv")
+_BWD_BASE = dict({p: None for p in _BWD_BONE_ARGS}, bone=0, batch=1, n_frames=4, mode=0, partial_floats=384 * 128, proj_part_bytes=_WG_TILES + 256 * 128 * 4,
+                 scratch_floats=256)
 
 ENTRIES = [
     # ---- api_ops.hip: loss, optimizer, data, eval ----
@@ -236,6 +259,17 @@ ENTRIES = [
       ("proj_part_bytes", dict(_PROJ, proj_part_bytes=_WG_TILES + 256 * 128 * 4 - 1)), ("align", dict(wpart=OFF(4))),
       ("align_proj", dict(**{**_PROJ, "proj_part": OFF(8)}), "align")] + _SCRATCH + [("scratch_small", dict(M=33))],
      ("dxn_add", "resid", "dbias") + tuple(_NO_PROJ)),
+    ("kasf_op_wgrad_jobs", _JOBS_BASE,
+     [("njobs", dict(njobs=0)), ("njobs_big", dict(njobs=4), "njobs"), ("nred", dict(nred=3)), ("fin_job", dict(fin_job=1)), ("fin_job_neg", dict(fin_job=-2), "fin_job"),
+      ("M_big", dict(M=2 ** 31)), ("null_red", dict(nred=1)), ("N", dict(N=i32(100, 128, 128))), ("N_640", dict(N=i32(640, 128, 128)), "N"),
+      ("null_g_j", dict(g=aptrs(None)), "null_red"), ("null_red_k", dict(_JOBS_RED, red_part=aptrs(None)), "null_red"), ("align", dict(g=aptrs(8))),
+      ("align_dbias", dict(dbias=aptrs(4)), "align"), ("align_partial", dict(partial=OFF(4)), "align"), ("align_ext", dict(ext_part=OFF(8)), "align"),
+      ("dbias_job", dict(dbias=aptrs(0))), ("fin_vectors", dict(fin_job=0, dbias=aptrs(0))), ("fin_dbias", dict(_JOBS_FIN, dbias=aptrs(None)), "fin_vectors"),
+      ("fin_N", dict(_JOBS_FIN, N=i32(256, 128, 128)), "fin_vectors"), ("ext_fin", dict(_JOBS_FIN, ext_part=BUF)), ("ext_njobs", dict(njobs=3, ext_part=BUF), "ext_fin"),
+      ("ext_together", dict(ext_part=BUF)), ("ext_fin_vectors", dict(_JOBS_EXT), "ext_together"), ("ext_alone", dict(ext_nparts=1), "ext_together"),
+      ("red_nparts", dict(_JOBS_RED, red_nparts=i32(0))), ("red_elems", dict(_JOBS_RED, red_elems=i32(100))), ("red_elems_0", dict(_JOBS_RED, red_elems=i32(0)), "red_elems"),
+      ("partial_floats", dict(partial_floats=128 * 128 - 1)), ("partial_floats_fin", dict(_JOBS_FIN, partial_floats=128 * 128 + 127), "partial_floats")],
+     ("fin_w", "fin_bias", "fin_ls", "dls", "red_part", "red_out", "red_nparts", "red_elems", "ext_part", "ext_brow", "ext_dw", "ext_db")),
     ("kasf_op_attention_fwd", _ATTN_BASE, _DT + _ATTN_SHAPE + _ATTN_LD[:4] + _ATTN_ALIGN, ()),
     ("kasf_op_attention_bwd", _ATTN_BWD_BASE, _DT + _ATTN_SHAPE + _ATTN_LD + [_ATTN_ALIGN[0], ("align_dv", dict(dv=OFF(4)), "align")], ()),
     ("kasf_op_attention_fwd_heads", dict(_ATTN_BASE, num_heads=8), _DT + _ATTN_SHAPE + _ATTN_LD[:4] + _ATTN_ALIGN, ()),
@@ -252,6 +286,11 @@ ENTRIES = [
       ("kv_save", dict(q_save=BUF, o_save=BUF, kv_save=BUF)), ("kv_save_bone", dict(_BLK_BONE, q_save=BUF, o_save=BUF), "kv_save"), ("lse_save", dict(lse_save=BUF)),
       ("alias", dict(out=SAME("x"))), ("align", dict(x=OFF(8))), ("align_out", dict(out=OFF(4)), "align"), ("align_save", dict(q_save=OFF(8), o_save=BUF), "align")],
      ("x_limb", "lnl_g", "lnl_b", "wkv", "q_save", "kv_save", "o_save", "lse_save")),
+    ("kasf_op_attn_block_bwd", _BWD_BASE,
+     [("bone", dict(bone=2)), ("mode", dict(mode=2)), ("batch", dict(batch=-1)), ("n_frames", dict(n_frames=0)), ("big", dict(batch=2 ** 20, n_frames=2 ** 10)),
+      ("group", dict(mode=1, n_frames=33)), ("bone_operands", dict(bone=1)), ("bone_extra", dict(x_limb=BUF), "bone_operands"), ("alias", dict(out=SAME("x"))),
+      ("align", dict(x=OFF(8))), ("align_dw", dict(dw_mix=OFF(4)), "align")] + _SCRATCH +
+     [("proj_part_bytes", dict(proj_part_bytes=_WG_TILES + 256 * 128 * 4 - 1)), ("partial_floats", dict(partial_floats=384 * 128 - 1))], _BWD_BONE_ARGS),
     ("kasf_op_gcn_fwd", dict(dtype=0, batch=1, n_frames=4, mode=1, neighbour_num=4),
      _GCN + [("neighbour_num", dict(neighbour_num=0)), ("neighbour_num_big", dict(neighbour_num=5))], ()),
     ("kasf_op_gcn_bwd", dict(dtype=0, batch=1, n_frames=4, mode=1), _GCN, ()),
@@ -272,6 +311,12 @@ ENTRIES = [
 UNREACHABLE = [
     ("kasf_op_dgrad_wg", "dgrad_wg: the launcher declined a form that kasf_dgrad_wg_supported accepts",
      "behind the launcher: the entry has asked kasf_dgrad_wg_supported about the same arguments before, and refuses what it does not accept"),
+    ("kasf_op_wgrad_jobs", "wgrad_jobs: the launcher declined a call that passed every check",
+     "behind the launcher: the entry restates the launcher's own conditions and split arithmetic, and refuses what it would decline"),
+    ("kasf_op_attn_block_bwd", "attn_block_bwd: the launcher declined a call that passed every check",
+     "behind the launcher: the entry has refused groups of more than 32 positions and every missing pointer before; a short sink is error 6, not this"),
+    ("kasf_op_attn_block_bwd", "attn_block_bwd: the weight-gradient launcher declined a call that passed every check",
+     "behind the second launcher: the entry restates its split arithmetic for partial_floats and passes it no fin job"),
     ("kasf_detect_boxes", "detect_boxes: the device refused the LDS size of the sort + NMS kernel",
      "comes back from the launcher, after its first kernel is on the stream: every host check has passed by then"),
 ]

@@ -36,6 +36,61 @@ def test_an_empty_batch_returns_0_after_the_checks(lib):
     assert lib.kasf_op_attention_bwd_fused_do(p, 384, p, p, 384, p, p, p, 384, p, p, 384, 0, 4, 1, 0, None, None, None) == 2      # (this one always refused it)
 
 
+def test_block_bwd_symbol_and_empty_batch(lib):
+    import ctypes as C
+    from kasportsformer_amd import _lib
+    sig = _lib.SIGNATURES["kasf_op_attn_block_bwd"][1]
+    assert lib.kasf_op_attn_block_bwd.argtypes == sig and len(sig) == 40
+    buf = C.create_string_buffer(8192 + 64)
+    p = C.c_void_p((C.addressof(buf) + 63) // 64 * 64)
+    o = C.c_void_p(p.value + 4096)
+    self_form = [0, p, None, p, p, p, None, None, p, None, None, p, p, p, p, o, None, p, None, p, None, p, p, None, None, p, None, p, p, p]
+    assert lib.kasf_op_attn_block_bwd(*self_form, p, 0, p, 256 * 128 * 128 * 2 + 256 * 128 * 4, p, 64, 0, 4, 1, None) == 0          # batch = 0: after the checks, no launch
+
+
+def test_block_bwd_tables_meet_the_grid():
+    """the shapes of tests/test_gpu_attn.py::test_block_bwd against kasf_launch_attn_block_bwd's arithmetic as attn_ref.block_bwd_grid restates it"""
+    g = lambda mode, B, T: R.block_bwd_grid(B, T, mode)
+    assert g(0, 1, 1) == (1, 1, 1) and g(0, 255, 1) == (255, 1, 255) and g(0, 256, 1) == (256, 1, 256)
+    assert g(0, 257, 1) == (256, 2, 129)                                  # 129 active workgroups, 127 that return at once; the last owns one group
+    assert g(0, 513, 1) == (256, 3, 171)                                  # a third walk
+    assert g(1, 16, 17) == (256, 2, 136) and g(1, 16, 27) == (256, 2, 136) and g(1, 31, 32) == (256, 3, 176) and 31 * 17 - 175 * 3 == 2      # a short last range
+    assert g(1, 1, 4) == (17, 1, 17)
+    cases = [c for v in R.BLOCK_BWD.values() for c in v]
+    assert len(cases) == 17 and all(R.group_len(T, m) <= 32 for m, B, T in cases)
+    assert {R.group_len(T, m) for m, B, T in R.BLOCK_BWD["t9"]} == {4, 9, 16, 17} and {R.group_len(T, m) for m, B, T in R.BLOCK_BWD["t16"]} == {18, 27, 31, 32}
+    assert {g(*c)[1] for c in cases} == {1, 2, 3}
+    for bone in (0, 1):                                                    # groups shorter than 8 positions carry two planted rows each, the others five
+        i = R.block_bwd_inputs(bone, 1, 1, 4)
+        rows = sorted(r for v in i["where"].values() for r in v)
+        assert R.bwd_planted_groups(1, 4, 1) == [0, 16] and rows == [0, 17, 16 + 2 * 17, 16 + 3 * 17]            # positions 0, 1 of track 0; positions 3, 2 of track 16
+        assert i["where"]["const"] == [0] and i["where"]["zero"] == [17]
+        i = R.block_bwd_inputs(bone, 1, 16, 17)
+        assert R.bwd_planted_groups(16, 17, 1) == [0, 1, 271] and sum(len(v) for v in i["where"].values()) == 15
+        assert bool((i["wq"][48:64] == 0).all()) and float(i["g_mid"].abs().max()) > 0
+
+
+def test_block_bwd_reference_is_autograd_of_the_block_forward():
+    """block_bwd_ref (no rounding) against fp64 autograd of block_ref's forward for the upstream gradient g_mid, both forms"""
+    for bone in (0, 1):
+        mode, B, T = 1, 2, 9
+        i = {k: (v.double() if torch.is_tensor(v) else v) for k, v in R.block_bwd_inputs(bone, mode, B, T).items()}
+        i["wts"] = (i["ls1"][:, None] * i["proj_w"]).T.contiguous()          # (the operand is this product formed in fp32: formed in fp64 here)
+        leaf = {n: i[n].clone().requires_grad_(True) for n in ("x", "xl", "ln_g", "ln_b", "lnl_g", "lnl_b", "wq", "wkv", "proj_w", "proj_b", "ls1") if i[n] is not None}
+        f = dict(i, **leaf, wproj=leaf["proj_w"], bproj=leaf["proj_b"])
+        R.block_ref(f, B, T, mode)["x_mid"].backward(i["g_mid"])
+        r = R.block_bwd_ref(i, B, T, mode)
+        e = lambda got, want: float((got - want).abs().max() / want.abs().max())
+        pairs = [(r["out"], leaf["x"].grad), (r["dgamma"], leaf["ln_g"].grad), (r["dbeta"], leaf["ln_b"].grad), (r["dproj_w"], leaf["proj_w"].grad),
+                 (r["dproj_b"], leaf["proj_b"].grad), (r["dls1"], leaf["ls1"].grad)]
+        if bone:
+            pairs += [(r["out_limb"] - i["outl0"], leaf["xl"].grad), (r["dgamma_l"], leaf["lnl_g"].grad), (r["dbeta_l"], leaf["lnl_b"].grad), (r["dw_mix"], leaf["wq"].grad),
+                      (r["dw_kv"], leaf["wkv"].grad)]
+        else:
+            pairs += [(r["dw_mix"], leaf["wq"].grad)]
+        assert all(e(a, b) < 1e-9 for a, b in pairs), [e(a, b) for a, b in pairs]
+
+
 @pytest.fixture(scope="module")
 def measured():
     return {w: R.measure(w) for w in ("fp32", "bf16")}

@@ -1,5 +1,5 @@
-"""CPU-side checks of the linear / data-gradient / weight-gradient / MLP operator entries (include/kasf.h, kasf_op_linear ... kasf_op_cast): the two entries
-tests/test_gpu_dense.py adds, the measurements its bars are derived from (tests/dense_ref.py: BAR32, DIST16), and the hand-written backward formulas of the
+"""CPU-side checks of the linear / data-gradient / weight-gradient / MLP operator entries (include/kasf.h, kasf_op_linear ... kasf_op_cast): the three entries
+tests/test_gpu_dense.py adds, the launcher checks and shape tables of kasf_op_wgrad_jobs, the measurements its bars are derived from (tests/dense_ref.py: BAR32, DIST16), and the hand-written backward formulas of the
 reference against fp64 autograd of the forward.  No GPU."""
 import pytest
 import torch
@@ -19,7 +19,99 @@ def test_symbols_and_prototypes(lib):
         assert n in _lib.SIGNATURES and hasattr(lib, n), n
         assert getattr(lib, n).argtypes == _lib.SIGNATURES[n][1]
     assert len(_lib.SIGNATURES["kasf_op_dgrad_wg"][1]) == 29
+    assert "kasf_op_wgrad_jobs" in _lib.SIGNATURES and lib.kasf_op_wgrad_jobs.argtypes == _lib.SIGNATURES["kasf_op_wgrad_jobs"][1]
+    assert len(_lib.SIGNATURES["kasf_op_wgrad_jobs"][1]) == 25
     assert _lib.ABI_VERSION == 12 and lib.kasf_version() == 12          # additive under ABI 12
+
+
+def test_wgrad_jobs_returns_zero_without_tokens(lib):
+    """M = 0 passes the checks and returns 0 before any device call (host memory stands in for the arrays)"""
+    import ctypes as C
+    buf = C.create_string_buffer(4096 + 64)
+    p = (C.addressof(buf) + 63) // 64 * 64
+    arr, none, n = (C.c_void_p * 1)(p), (C.c_void_p * 1)(), (C.c_int32 * 1)(384)
+    a = lambda t: C.addressof(t)
+    assert lib.kasf_op_wgrad_jobs(1, a(arr), a(arr), a(n), a(arr), a(none), -1, None, None, None, None, 0, p, 0, 0, None, None, None, None, None, None, 0, None, None, None) == 0
+
+
+def test_wgrad_jobs_launcher_declines_an_incomplete_fin_job(lib):
+    """kasf_launch_wgrad_jobs (kernels.h; reached here through its C++ symbol, Itanium-mangled from that declaration) returns false, before any device call, for a fin
+    job whose finishing workgroups would read or write through NULL: no dbias[fin_job] (its rows `brow` and `db`), one of fin_W / fin_bias / fin_ls / fin_dls missing,
+    fin_job >= njobs, or N != 128 (fin_W is [128][128]).  The entry refuses all of these earlier (tests/refusal_cases.py); the engine never makes them."""
+    import ctypes as C
+    # The mangled name spells the launcher's parameter types, so it stands for the argtypes below: a change of the declaration in kernels.h changes the name, and this
+    # lookup fails instead of calling with stale types.  Then take the new name from `nm -D --defined-only kasportsformer_amd/libkasf_hip.so | grep
+    # kasf_launch_wgrad_jobs` and bring `argtypes` and `call` below in line with the new declaration.
+    name = "_Z22kasf_launch_wgrad_jobsP12ihipStream_tiPKPKvS4_PKiPKPfS9_iPKfSB_SB_S7_lS7_liPK14KasfBf16ReduceS2_SB_iS7_S7_"
+    assert hasattr(lib, name), "kasf_launch_wgrad_jobs is not exported under the name of its declaration in kernels.h (changed parameters, or a hidden symbol): see above"
+    fn = getattr(lib, name)
+    vp = C.c_void_p
+    fn.restype = C.c_bool
+    fn.argtypes = [vp, C.c_int] + [vp] * 5 + [C.c_int] + [vp] * 4 + [C.c_int64, vp, C.c_int64, C.c_int, vp, vp, vp, C.c_int, vp, vp]
+    buf = C.create_string_buffer(1 << 16)
+    p = (C.addressof(buf) + 63) // 64 * 64
+    two, none = (vp * 2)(p, p), (vp * 2)()
+    with_db = (vp * 2)(p, None)
+    a = lambda t: C.addressof(t)
+
+    def call(njobs, Ns, dbias, fin_job, fw=p, fb=p, fl=p, fd=p):
+        n = (C.c_int * 2)(*Ns)
+        return fn(None, njobs, a(two), a(two), a(n), a(two), a(dbias), fin_job, fw, fb, fl, fd, 1, p, 1 << 40, 0, None, None, None, 0, None, None)
+
+    assert call(2, (128, 384), none, 0) is False                              # the defect: brow and db of the fin job were NULL and W was not
+    assert call(1, (128, 384), with_db, 1) is False and call(2, (128, 384), with_db, 2) is False
+    for k in range(4):
+        assert call(2, (128, 384), with_db, 0, *[None if q == k else p for q in range(4)]) is False
+    assert call(2, (256, 384), with_db, 0) is False
+    assert call(2, (128, 384), (vp * 2)(None, p), -1) is False                # (as before: a bias gradient on a job that is not the fin job)
+
+
+def test_jobs_tables_meet_the_conditions():
+    """the token counts of tests/test_gpu_dense.py::test_wgrad_jobs against the launcher's arithmetic as dense_ref.jobs_splits restates it: every mix meets one token,
+    a last split of one row, a split with a register tail and one without, 1 / 2 / 7 / 8 k / 8 k + r splits (the remainder branch of the XCD order), 1 / 16 / 17 /
+    32 / 33 / >= 49 tiles in the finish loop, and splits of three or more 64-row ring tiles (a two-stage ring takes a stage again)"""
+    assert R.jobs_splits(1, (128,)) == (1, 128) and R.jobs_splits(31744, (128,)) == (248, 128) and R.jobs_splits(31745, (128,)) == (125, 256)
+    assert R.jobs_splits(24577, (128, 384)) == (49, 512) and R.jobs_splits(7937, (128, 128, 256)) == (32, 256) and R.jobs_splits(10625, (384,)) == (42, 256)
+    assert R.jobs_splits(40000, (128, 384)) == (53, 768) and R.jobs_splits(7936, (512,)) == (62, 128)
+    assert R.jobs_partial_floats(129, (128, 384), 0) == 2 * 512 * 128 + 2 * 128 and R.jobs_partial_floats(129, (384,), -1) == 2 * 384 * 128
+    for mix, (Ns, fin_job, reds, ext) in R.JOBS_MIXES.items():
+        cases = R.jobs_cases(mix)
+        Ms = [M for M, _ in cases]
+        assert Ms[0] == 1 and max(Ms) <= 32000, mix
+        sp = {M: R.jobs_splits(M, Ns) for M in Ms}
+        last = {M: M - (s - 1) * sl for M, (s, sl) in sp.items()}            # rows of the last split
+        assert any(s > 1 and last[M] == 1 for M, (s, _) in sp.items()), mix
+        assert any(last[M] % 64 != 0 for M in Ms) and any(last[M] % 64 == 0 for M in Ms), mix            # a last split with a register tail, and one without
+        assert any(s > 1 and last[M] > 64 and last[M] % 64 != 0 for M, (s, _) in sp.items()), mix          # ring tiles AND a tail in one split
+        counts = {s for s, _ in sp.values()}
+        assert {1, 2, 7, 16, 17, 32, 33} <= counts and max(counts) >= 49, (mix, counts)
+        assert any(s % 8 == 0 for s in counts) and any(s > 8 and s % 8 != 0 for s in counts) and any(s < 8 for s in counts)
+        assert any(sl >= 192 for _, sl in sp.values()), mix
+        parts = {p for _, p in cases}
+        assert parts == set(R.JOBS_PARTS[mix]), mix            # every listed number of parts is used by some case
+        if ext:
+            assert {1, 16, 17, 33} <= parts and max(parts) >= 49, mix
+    assert {1, 17, 256} <= set(R.JOBS_PARTS["att1_red"]) and {2, 32, 49} <= set(R.JOBS_PARTS["one_red2"])
+    # the isolation case's redraw changes job 1 and nothing else
+    a, b = R.jobs_inputs("att2", 2049, 0), R.jobs_inputs("att2", 2049, 0, 1)
+    assert torch.equal(a["G"][0], b["G"][0]) and torch.equal(a["X"][0], b["X"][0]) and torch.equal(a["W"], b["W"]) and not torch.equal(a["G"][1], b["G"][1])
+
+
+def test_wgrad_jobs_reference_is_autograd_of_the_projection():
+    """the fin job's and the ext job's algebra: out = ls (x W^T + bias) with upstream gradient g"""
+    i = R.jobs_inputs("att2", 129, 0)
+    G, X, fin_job, W, bias, ls, red, ep, eb = R.jobs_sel(i, torch.float64)
+    Wl, bl, lsl = (t.clone().requires_grad_(True) for t in (W, bias, ls))
+    ((lsl * (X[0] @ Wl.T + bl)) * G[0]).sum().backward()
+    r = R.wgrad_jobs_ref(G, X, fin_job, W, bias, ls, red, ep, eb)
+    assert R.rel_err(r["dw0"], Wl.grad) < 1e-12 and R.rel_err(r["db"], bl.grad) < 1e-12 and R.rel_err(r["dls"], lsl.grad) < 1e-12
+    assert R.rel_err(r["dw1"], G[1].T @ X[1]) == 0
+    i = R.jobs_inputs("ext_bone", 129, 17)
+    G, X, fin_job, W, bias, ls, red, ep, eb = R.jobs_sel(i, torch.float64)
+    r = R.wgrad_jobs_ref(G, X, fin_job, W, bias, ls, red, ep, eb)
+    want = R.ls_algebra(ep.sum(0), eb.sum(0), W, bias, ls)
+    assert all(torch.equal(r[n], w) for n, w in zip(("ext_dw", "ext_db", "dls"), want)) and set(r) == {"dw0", "dw1", "ext_dw", "ext_db", "dls"}
+    assert R.jobs_no16("dls", i) and not R.jobs_no16("dls", R.jobs_inputs("att2", 129, 0)) and R.jobs_no16("red1", i) and not R.jobs_no16("dw0", i)
 
 
 def test_launcher_arithmetic_restated_by_the_reference():

@@ -24,6 +24,9 @@ Instantiations by test id (attn_ref.core_kernel, fused_do_grid and block_grid re
   test_block         flat / rp / rp3 -> k_attn_blk_fwd_flat / _rp / _rp3 <BONE = false / true>
   test_handover      rp3 -> kt, rp -> pers<16>, flat -> pers<9>: the forward's own q | k | v (o, lse) into the backward
   test_isolation     one case per kernel above: the groups kept must not see the groups redrawn
+  test_block_bwd     (kasf_op_attn_block_bwd) spatial and t9 -> k_attn_blk_bwd_h<BONE, 9>;  t16 -> <BONE, 16>;  then k_wgrad_ring_jobs + k_wgrad_finish_jobs
+                     (ext job) and k_col_finish.  Stage by stage as test_block: LN(x) from x; dq | dk | dv and the proj gradients on the stored LN(x); out, out_limb, the
+                     LayerNorm parameter gradients and dw on the stored dq | dk | dv.  test_block_bwd_short_sink: error 6;  test_block_bwd_isolation: three shapes per form
 """
 import pytest
 import torch
@@ -431,3 +434,130 @@ def test_isolation(lib, case):
         assert torch.equal(first[n][rows], second[n][rows]), f"{case}: {n} of a kept group changed when other groups were redrawn"
         changed += int((first[n][~rows] != second[n][~rows]).sum())
     assert changed > 0, f"{case}: the redrawn groups' outputs did not change"
+
+
+# ================================================================================================ F. block backward
+WPROJ_BYTES = 256 * 128 * 128 * 2 + 256 * 128 * 4
+BWD_ACC = ("dgamma", "dbeta", "dgamma_l", "dbeta_l", "dw_mix", "dw_kv", "dproj_w", "dproj_b", "dls1")
+
+
+def run_block_bwd(lib, bone, geom, i, sink_rows=None, expect=0):
+    """-> every output as fp64 CPU tensors (the accumulated fp32 ones with their start value 1 taken off); sink_rows: the rows of the column sink (default: the active
+    workgroups).  Token-major operands carry 64 rows of NaN behind row M, written token-major outputs the sentinel; out_limb starts from random bf16 values; partial,
+    proj_part and the sink start at NaN with a NaN guard behind the size the entry is told."""
+    from tests.dense_ref import jobs_splits
+    mode, B, T = geom
+    bf = torch.bfloat16
+    M = B * T * 17
+    x, g_mid = _in([i["x"]], 128, bf), _in([i["g_mid"]], 128, bf)
+    xl = _in([i["xl"]], 128, bf) if bone else None
+    f = lambda n: _dev(i[n]).data_ptr() if i.get(n) is not None else None
+    w = lambda n, t=None: _dev(i[n] if t is None else t, bf).data_ptr() if i.get(n) is not None else None
+    out, dq, xn_a = _out(M, 128, bf), _out(M, 128 if bone else 384, bf), _out(M, 128, bf)
+    out_limb = dkv = xn_b = None
+    if bone:
+        dkv, xn_b = _out(M, 256, bf), _out(M, 128, bf)
+        out_limb = _in([i["outl0"]], 128, bf)
+        out_limb[M:] = SENTINEL
+    acc = {n: torch.ones(s, device="cuda") for n, s in (("dgamma", 128), ("dbeta", 128), ("dw_mix", (128 if bone else 384, 128)), ("dproj_w", (128, 128)), ("dproj_b", 128),
+                                                        ("dls1", 128))}
+    if bone:
+        acc.update({n: torch.ones(s, device="cuda") for n, s in (("dgamma_l", 128), ("dbeta_l", 128), ("dw_kv", (256, 128)))})
+    need = jobs_splits(M, (128, 256) if bone else (384,))[0] * 384 * 128
+    active = R.block_bwd_grid(B, T, mode)[2]
+    sink = ((active if sink_rows is None else sink_rows) * (512 if bone else 256) + 63) // 64 * 64
+    nan = lambda n, dt=torch.float32: torch.full((n + 64,), NAN, device="cuda", dtype=dt)
+    partial, ppart, scratch = nan(need), nan(WPROJ_BYTES // 2, bf), nan(sink)
+    _KEEP.extend([acc, partial, ppart, scratch])
+    p = lambda t: t.data_ptr() if t is not None else None
+    a = lambda n: acc[n].data_ptr() if n in acc else None
+    rc = lib.kasf_op_attn_block_bwd(bone, p(x), p(xl), p(g_mid), f("ln_g"), f("ln_b"), f("lnl_g"), f("lnl_b"), w("wq"), w("wkv"), w("wq", i["wq"].T.contiguous()) if bone else None,
+                                    w("wts"), f("proj_w"), f("proj_b"), f("ls1"), p(out), p(out_limb), p(dq), p(dkv), p(xn_a), p(xn_b), a("dgamma"), a("dbeta"),
+                                    a("dgamma_l"), a("dbeta_l"), a("dw_mix"), a("dw_kv"), a("dproj_w"), a("dproj_b"), a("dls1"), p(partial), need, p(ppart), WPROJ_BYTES,
+                                    p(scratch), sink, B, T, mode, stream())
+    torch.cuda.synchronize()
+    assert rc == expect, (rc, lib.kasf_last_error())
+    for n, b in (("partial", partial[need:]), ("proj_part", ppart[WPROJ_BYTES // 2:]), ("scratch", scratch[sink:])):
+        assert bool(torch.isnan(b).all()), f"the guard behind {n} was written"
+    toks = dict(out=out, dq=dq, xn=xn_a, **(dict(out_limb=out_limb, dkv=dkv, xnl=xn_b) if bone else {}))
+    if expect != 0:                                            # refused or declined: nothing was launched, every buffer keeps its start value
+        assert all(bool((t == SENTINEL).all()) for n, t in toks.items() if n != "out_limb") and all(bool((t == 1).all()) for t in acc.values())
+        assert bool(torch.isnan(partial).all()) and bool(torch.isnan(ppart).all()) and bool(torch.isnan(scratch).all())
+        return None
+    for n, t in toks.items():
+        _kept(t, M, t.shape[1], n)
+    res = {n: t[:M].double().cpu() for n, t in toks.items() if n not in ("dq", "dkv")}
+    d = torch.cat((dq[:M], dkv[:M]), dim=1).double().cpu() if bone else dq[:M].double().cpu()
+    res.update(dq=d[:, :128], dk=d[:, 128:256], dv=d[:, 256:])
+    res.update({n: t.double().cpu() - 1 for n, t in acc.items()})
+    return res
+
+
+def _bwd_params():
+    return [(name, m, B, T, bone) for name, cases in R.BLOCK_BWD.items() for m, B, T in cases for bone in (0, 1)]
+
+
+def _bwd_judge(log, got, ref, geom, names):
+    """one stage's outputs in their measures: dq | dk | dv per (token, head), the token-major ones per row over their own bf16 ulp, the reductions per tensor (+ one
+    fp32 addition into the buffer that held 1)"""
+    from tests.dense_ref import rel_err
+    zero = R.handover_zero(geom[1], geom[2], geom[0])
+    for stage, outs in R.BWD_STAGES.items():
+        for n in outs:
+            if n not in names or n not in ref:
+                continue
+            key = f"bwd.{stage}"
+            if n in ("dq", "dk", "dv"):
+                log.heads(key, n, got[n], ref[n], geom, 8, zero.get(n))
+            elif n in ("xn", "xnl", "out", "out_limb"):
+                e, row = R.row_excess(got[n], ref[n])
+                log.add(f"{n} excess", e, R.bar(key, "bf16"), f"row {row}")
+            else:
+                mx = max(float(ref[n].abs().max()), 1e-300)
+                log.add(n, rel_err(got[n], ref[n]), R.bar(key, "bf16") + 2.0 ** -24 * (1 + mx) / mx)
+
+
+@pytest.mark.parametrize("name,mode,B,T,bone", _bwd_params(), ids=lambda v: str(v))
+def test_block_bwd(lib, name, mode, B, T, bone):
+    """kasf_launch_attn_block_bwd + the streaming weight gradient with its ext job + the sink's flush, stage by stage against attn_ref.block_bwd_ref: LN(x) from x;
+    dq | dk | dv on the LN(x) the device stored; out, out_limb, the LayerNorm parameter gradients and dw_mix / dw_kv on the dq | dk | dv (and LN(x)) it stored; the
+    proj gradients from the stored LN(x) (o is never stored)"""
+    geom = (mode, B, T)
+    i = R.stored(R.block_bwd_inputs(bone, mode, B, T), "bf16")
+    grid, per, active = R.block_bwd_grid(B, T, mode)
+    log = Log(f"block_bwd {name} mode={mode} B={B} T={T} bone={bone} [k_attn_blk_bwd_h<{bool(bone)}, {9 if R.group_len(T, mode) <= 17 else 16}>, per {per}, active {active}]", "bf16")
+    got = _twice(lambda: run_block_bwd(lib, bone, geom, i), log.tag)
+    _bwd_judge(log, got, R.block_bwd_ref(i, B, T, mode), geom, ("xn", "xnl"))
+    want = i["ln_b"].to(torch.bfloat16).double()
+    for r in i["where"]["const"] + i["where"]["zero"]:
+        assert torch.equal(got["xn"][r], want), f"{log.tag}: LN of the planted constant row {r} is not beta exactly"
+    st = {n: got[n] for n in ("xn", "xnl") if n in got}
+    _bwd_judge(log, got, R.block_bwd_ref(i, B, T, mode, given=st), geom, ("dq", "dk", "dv", "dproj_w", "dls1", "dproj_b"))
+    st.update({n: got[n] for n in ("dq", "dk", "dv")})
+    _bwd_judge(log, got, R.block_bwd_ref(i, B, T, mode, given=st), geom, ("out", "out_limb", "dgamma", "dbeta", "dgamma_l", "dbeta_l", "dw_mix", "dw_kv"))
+    log.done()
+
+
+@pytest.mark.parametrize("bone", [0, 1])
+def test_block_bwd_short_sink(lib, bone):
+    """the column sink one row short of the active workgroups: error 6, nothing launched, every buffer untouched; with the full sink the same call runs"""
+    geom = (1, 16, 17)
+    i = R.stored(R.block_bwd_inputs(bone, *geom), "bf16")
+    active = R.block_bwd_grid(16, 17, 1)[2]
+    assert run_block_bwd(lib, bone, geom, i, sink_rows=active - 1, expect=6) is None
+    assert run_block_bwd(lib, bone, geom, i) is not None
+
+
+@pytest.mark.parametrize("mode,B,T,bone", [(m, B, T, bone) for m, B, T in ((0, 513, 1), (1, 31, 32), (1, 16, 17)) for bone in (0, 1)], ids=lambda v: str(v))
+def test_block_bwd_isolation(lib, mode, B, T, bone):
+    """the groups with index not divisible by 3 redrawn (x, x_limb, g_mid): the token-major outputs of the other groups keep their bits"""
+    geom = (mode, B, T)
+    i = R.stored(R.block_bwd_inputs(bone, mode, B, T), "bf16")
+    j, rows = _redraw(i, ("x", "xl", "g_mid"), geom, 2)
+    first, second = run_block_bwd(lib, bone, geom, i), run_block_bwd(lib, bone, geom, j)
+    changed = 0
+    for n in ("xn", "xnl", "dq", "dk", "dv", "out", "out_limb"):
+        if n in first:
+            assert torch.equal(first[n][rows], second[n][rows]), f"block_bwd {geom} bone={bone}: {n} of a kept group changed when other groups were redrawn"
+            changed += int((first[n][~rows] != second[n][~rows]).sum())
+    assert changed > 0

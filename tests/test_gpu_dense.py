@@ -1,5 +1,5 @@
 """The linear, data-gradient, weight-gradient and MLP kernels on their own (include/kasf.h: kasf_op_linear, kasf_op_linear_res, kasf_op_dgrad_lnbwd, kasf_op_dgrad_wg,
-kasf_op_wgrad, kasf_op_mlp_fwd, kasf_op_mlp_bwd, kasf_op_mlp_bwd_fused, kasf_op_cast) against fp64 torch math of the same operation on the dtype-rounded operands
+kasf_op_wgrad, kasf_op_wgrad_jobs, kasf_op_mlp_fwd, kasf_op_mlp_bwd, kasf_op_mlp_bwd_fused, kasf_op_cast) against fp64 torch math of the same operation on the dtype-rounded operands
 (tests/dense_ref.py).  tests/test_gpu_ops.py keeps its own, older checks of the same entries.
 
 How every comparison is set up:
@@ -26,7 +26,12 @@ Instantiations by test id (bf16 unless noted; fp32 mode runs the generic k_linea
   test_mlp_fwd          fp32 k_mlp_fwd<float>;  bf16 k_mlp_fwd_s with xn_out and with NULL (evaluation mode)
   test_mlp_bwd_wgrad    k_mlp_bwd<float> / k_mlp_bwd<bf16> + the two kasf_op_wgrad launches of the fp32 mode's path
   test_mlp_bwd_fused    k_mlp_bwd_s<false> + k_lnbwd_sum4_fin<2> (fin blocks: mlp_wfinish_body)
+  test_wgrad_jobs       k_wgrad_ring_jobs (wgrad_ring_body<bf16, BF16P>) + k_wgrad_finish_jobs:  att2 / bone3 -> two / three streaming jobs, job 0 finished with the
+                        layer-scale algebra;  att1_red / one_red2 -> the reduction role beside the jobs;  ext_self / ext_bone -> the ext job (tiles and rows from
+                        another kernel) beside one / two streaming jobs.  M 769 / 2049 / 4097 / 6209: the remainder branch of the XCD order (splits % 8 != 0)
 """
+import ctypes as C
+
 import pytest
 import torch
 
@@ -390,6 +395,117 @@ def test_wgrad(lib, cd, N, K, use_ln, M):
         if form == "exact":
             _same_bits(got, run(form), log.tag)
     log.done()
+
+
+# ================================================================================================ several weight gradients in one launch (bf16)
+def _parr(ts):
+    """a host array of device pointers (NULL for None); the tensors stay alive in _KEEP"""
+    a = (C.c_void_p * max(len(ts), 1))(*[t.data_ptr() if t is not None else None for t in ts])
+    _KEEP.append(a)
+    return C.c_void_p(C.addressof(a))
+
+
+def _parts_in(t):
+    """bf16 partial tiles [parts, ...] (a reduction's, the ext job's) with one part of NaN behind them: a loop that runs one part too far sums it"""
+    d = torch.full((t.shape[0] + 1, *t.shape[1:]), float("nan"), dtype=torch.bfloat16)
+    d[:t.shape[0]] = t.to(torch.bfloat16)
+    return _dev(d, torch.bfloat16)
+
+
+def _jobs_operands(i):
+    bf = torch.bfloat16
+    d = dict(G=[_rows_in(t, bf) for t in i["G"]], X=[_rows_in(t, bf) for t in i["X"]], W=_dev(i["W"]), bias=_dev(i["bias"]), ls=_dev(i["ls"]),
+             red=[_parts_in(t) for t in i["red"]], ext_part=None, ext_brow=None)
+    if i["ext_part"] is not None:
+        d["ext_part"] = _parts_in(i["ext_part"])
+        d["ext_brow"] = _dev(torch.cat([i["ext_brow"], torch.full((1, 128), float("nan"))]))
+    return d
+
+
+def _run_jobs(lib, i, d, M, floats=None):
+    """-> (return code, {output: the accumulated buffer (started at 1)}, partial, the floats the launcher needs)"""
+    Ns, fin_job = i["Ns"], i["fin_job"]
+    one = lambda *s: _new(tuple(s), fill=1.0)
+    r = {f"dw{j}": one(N, 128) for j, N in enumerate(Ns)}
+    r.update({f"red{k}": one(t.shape[1]) for k, t in enumerate(i["red"])})
+    ext = d["ext_part"] is not None
+    if fin_job >= 0 or ext:
+        r.update(db=one(128), dls=one(128))
+    if ext:
+        r["ext_dw"] = one(128, 128)
+    need = R.jobs_partial_floats(M, Ns, fin_job)
+    part = _new(need + 64, fill=float("nan"))
+    dbias = [r["db"] if j == fin_job else None for j in range(len(Ns))]
+    fin = (lambda t: ptr(t)) if fin_job >= 0 or ext else (lambda t: None)
+    nparts = (C.c_int32 * 2)(*[t.shape[0] for t in i["red"]])
+    elems = (C.c_int32 * 2)(*[t.shape[1] for t in i["red"]])
+    _KEEP.extend([nparts, elems])
+    nred = len(i["red"])
+    rc = lib.kasf_op_wgrad_jobs(len(Ns), _parr(d["G"]), _parr(d["X"]), _parr_i32(Ns), _parr([r[f"dw{j}"] for j in range(len(Ns))]), _parr(dbias), fin_job, fin(d["W"]),
+                                fin(d["bias"]), fin(d["ls"]), fin(r.get("dls")), M, ptr(part), need if floats is None else floats, nred,
+                                _parr(d["red"]) if nred else None, _parr([r[f"red{k}"] for k in range(nred)]) if nred else None,
+                                C.c_void_p(C.addressof(nparts)) if nred else None, C.c_void_p(C.addressof(elems)) if nred else None, ptr(d["ext_part"]),
+                                ptr(d["ext_brow"]), i["ext_part"].shape[0] if ext else 0, ptr(r.get("ext_dw")), ptr(r["db"]) if ext else None, stream())
+    if ext:
+        r["ext_db"] = r.pop("db")
+    return rc, r, part, need
+
+
+def _parr_i32(v):
+    a = (C.c_int32 * len(v))(*v)
+    _KEEP.append(a)
+    return C.c_void_p(C.addressof(a))
+
+
+JOBS_CASES = [(mix, M, parts) for mix in R.JOBS_MIXES for M, parts in R.jobs_cases(mix)]
+
+
+@pytest.mark.parametrize("mix,M,parts", JOBS_CASES, ids=[f"{c[0]}-M{c[1]}-parts{c[2]}" for c in JOBS_CASES])
+def test_wgrad_jobs(lib, mix, M, parts):
+    """kasf_launch_wgrad_jobs as block_backward launches it: every job's dW, the fin job's layer-scale algebra, the reductions riding in the finish launch and the ext
+    job, each per tensor against fp64 on the bf16 operands; one bf16 partial tile per job and split is the 16-bit point (dense_ref.wgrad_jobs_ref)"""
+    i = R.jobs_inputs(mix, M, parts)
+    ref = R.wgrad_jobs_ref(*R.jobs_sel(i, F64))
+    d = _jobs_operands(i)
+    splits, sl = R.jobs_splits(M, i["Ns"])
+    log = Log(f"wgrad_jobs {mix} M={M} parts={parts} splits={splits} slice={sl}", "bf16", "wgrad_jobs")
+    rc, got, part, need = _run_jobs(lib, i, d, M)
+    _ok(rc, lib)
+    _all_nan(part[need:], log.tag + " partial")
+    assert set(got) == set(ref), (sorted(got), sorted(ref))
+    for n in sorted(ref):
+        log.red(n, _back(got[n]) - 1, ref[n], 1, no16=R.jobs_no16(n, i))
+    rc, again, part, _ = _run_jobs(lib, i, d, M)
+    _ok(rc, lib)
+    _same_bits(got, again, log.tag)
+    log.done()
+
+
+def test_wgrad_jobs_refuses_short_scratch(lib):
+    """one float below what the launcher asks is error 2 before a launch: every buffer keeps its start value"""
+    mix, M = "att2", 2049
+    i = R.jobs_inputs(mix, M, 0)
+    d = _jobs_operands(i)
+    need = R.jobs_partial_floats(M, i["Ns"], i["fin_job"])
+    rc, got, part, _ = _run_jobs(lib, i, d, M, floats=need - 1)
+    assert rc == 2 and b"partial_floats" in lib.kasf_last_error()
+    torch.cuda.synchronize()
+    assert all(bool((t == 1).all()) for t in got.values()) and bool(torch.isnan(part).all())
+    rc, got, part, _ = _run_jobs(lib, i, d, M, floats=need)
+    _ok(rc, lib)
+    assert not any(bool((t == 1).all()) for t in got.values())
+
+
+def test_wgrad_jobs_isolation(lib):
+    """job 1's operands redrawn: job 0's dW, db and dls keep their bits (a job reads and writes its own tiles and rows only)"""
+    mix, M = "att2", 2049
+    a, b = R.jobs_inputs(mix, M, 0), R.jobs_inputs(mix, M, 0, 1)
+    rc, ga, _, _ = _run_jobs(lib, a, _jobs_operands(a), M)
+    _ok(rc, lib)
+    rc, gb, _, _ = _run_jobs(lib, b, _jobs_operands(b), M)
+    _ok(rc, lib)
+    _same_bits({n: ga[n] for n in ("dw0", "db", "dls")}, gb, "wgrad_jobs isolation")
+    assert not torch.equal(ga["dw1"], gb["dw1"])
 
 
 # ================================================================================================ MLP
