@@ -67,6 +67,8 @@
  *                             quantity held constant is what loss_limb_var_calc penalises in training: one length per bone per player, re-imposed on every frame
  *   kasf_pose_place        <- nothing in the reference (its demo plots one person at the origin): the root translation that re-projects a root-relative pose
  *                             onto its keypoints through the camera's intrinsics, so that several players stand where they stood
+ *   kasf_keypoints_triangulate, kasf_keypoints_undistort <- nothing in the reference (it is monocular): the keypoints of one player in several calibrated cameras
+ *                             to joints in the world frame, and the Brown-Conrady undistortion that this and kasf_pose_place need in front of them
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
  *   kasf_op_gcn_fwd, kasf_op_gcn_bwd <- GCN.forward between its U | V Linear and the residual, and autograd of it   model/modules/graph.py:19-134, KASportsFormer.py:109
  */
@@ -1014,8 +1016,8 @@ int kasf_bone_tracked(const float* poses, const int32_t* ids, const int32_t* slo
  * root-relative, joint 0 at the origin, so every player stands on the same spot.  With the 2-D keypoints the pose came from and the camera's intrinsics, the
  * root translation T that makes the pose re-project onto its keypoints is a 3 x 3 linear least-squares problem per frame; this stage solves it on the device.
  * Frames are independent of one another: a recorded track and one live tick are the same call.  Nothing is read back, nothing is allocated, no atomics: the
- * same bits from run to run.  The camera is a pinhole, (fx, fy, cx, cy) in pixels: THERE IS NO DISTORTION MODEL; undistort the keypoints first where the lens
- * needs it.
+ * same bits from run to run.  The camera is a pinhole, (fx, fy, cx, cy) in pixels: THERE IS NO DISTORTION MODEL HERE; undistort the keypoints first where the lens
+ * needs it (kasf_keypoints_undistort below).
  *
  * Per frame: the pose P [17][3] fp32, root-relative, in any one unit; the keypoints k [17][3] fp32, pixel x, pixel y, score, in the Human3.6M-17 layout; the
  * camera (fx, fy, cx, cy) fp32.  ALL ARITHMETIC BELOW IS IN FP64 (on players at 4 - 40 m with f = 1500 px the system's condition number reaches 4e4), joints
@@ -1071,6 +1073,87 @@ typedef struct kasf_place_params {
 int kasf_pose_place(const float* poses, const float* keypoints, int64_t frames, const float* camera, int32_t camera_per_frame, const float* lengths,
                     int32_t lengths_per_frame, const kasf_place_params* params, float* out, float* root, float* residual, float* scale, uint8_t* state,
                     void* stream);
+
+/* ---- keypoints of several calibrated cameras -> joints in the world frame, and the lens undistortion (ADDED under ABI 12: additive, kasf_version() stays 12;
+ * look the symbols up by name).  A player tracked in C synchronised, calibrated cameras has C keypoint tracks; this stage triangulates them, point by point --
+ * one joint of one frame --, on the device.  Points are independent of one another: a recorded track and one live tick are the same call.  Nothing is read
+ * back, nothing is allocated, no atomics: the same bits from run to run.  Calibration, synchronisation and matching players across cameras are the caller's.
+ *
+ * THE CAMERA MODEL, stated once (csrc/camera_model.h).  A camera is 21 fp32 values: fx, fy, cx, cy in pixels; k1, k2, p1, p2, k3, the Brown-Conrady
+ * coefficients in OpenCV's order; R [9] row-major and t [3] with X_cam = R X_world + t.  ALL ARITHMETIC BELOW IS IN FP64, views in ascending order, every line
+ * one rounded operation (a line with several: by its parentheses, then left to right); the library is built with -ffp-contract=off and a correctly rounded
+ * divide and square root.  An fp32 input enters by an exact conversion; results are rounded to fp32 once, at the store.
+ *   Normalise:  xd = (u - cx) / fx;  yd = (v - cy) / fy.
+ *   Undistort:  x = xd, y = yd, then n times (n = undistort_iterations in [0, 20]; a fixed count with no convergence test, so that the bits do not depend on
+ *               the data's path; 0 is a pinhole):
+ *                 r2 = x * x + y * y
+ *                 rad = 1 + r2 * (k1 + r2 * (k2 + r2 * k3))
+ *                 dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+ *                 dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+ *                 x = (xd - dx) / rad;  y = (yd - dy) / rad
+ *               With k1 = -0.12, k2 = 0.05, |x| <= 0.6 and f = 1500 px five rounds come within 2e-4 px of the true point and three within 3e-2 px.
+ *
+ * THE TRIANGULATION RULE, per point seen by C views, 2 <= C <= 16; view c gives the keypoint k = (u, v, score) fp32 and a camera row.
+ *   1. View c is USABLE when its keypoint passes step 1 of the One-Euro rule above with C = 2 and a score, the same code (|u|, |v| <= 1e12f and score >=
+ *      min_score; a NaN fails) and the 21 values of its camera are finite.  used = the number of usable views, stored whatever the state.  (x, y) of a usable
+ *      view is its undistorted point.
+ *   2. The fit.  w0 = score when weighted, else 1.  A usable view gives two rows in X, the world point:
+ *        a1 = (x * R20 - R00, x * R21 - R01, x * R22 - R02),  r1 = t0 - x * t2        a2 = (y * R20 - R10, y * R21 - R11, y * R22 - R12),  r2 = t1 - y * t2
+ *      Pass 0 weights row 1 by wu = w0 * (fx * fx) and row 2 by wv = w0 * (fy * fy): an algebraic error in pixels at unit depth.  The nine sums start at 0 and
+ *      take, for each usable view ascending, row 1 and then row 2, with (w, a, r) the row's weight, vector and right-hand side:
+ *        A00 = A00 + w * (a0 * a0);  A01 = A01 + w * (a0 * a1);  A02 = A02 + w * (a0 * a2);  A11 = A11 + w * (a1 * a1);  A12 = A12 + w * (a1 * a2)
+ *        A22 = A22 + w * (a2 * a2);  b0 = b0 + w * (a0 * r);  b1 = b1 + w * (a1 * r);  b2 = b2 + w * (a2 * r)
+ *      The symmetric system A X = b is solved as L D L^T in the order 0, 1, 2 without exchanges:
+ *        d0 = A00;  l10 = A01 / d0;  l20 = A02 / d0;  d1 = A11 - l10 * A01;  m12 = A12 - l10 * A02;  l21 = m12 / d1;  d2 = A22 - l20 * A02 - l21 * m12
+ *        c1 = b1 - l10 * b0;  c2 = b2 - l20 * b0 - l21 * c1
+ *        X2 = c2 / d2;  X1 = c1 / d1 - l21 * X2;  X0 = b0 / d0 - l10 * X1 - l20 * X2
+ *      THE PIVOT TEST: d0, d1 and d2 must each be > 1e-9 * (A00 + A11 + A22) (a NaN fails).  Two rays at the angle theta give a least pivot of about
+ *      theta^2 / 8 of the trace, so the test fails below 9e-5 rad: a parallax of an eighth of a pixel at f = 1500 px, cameras a millimetre apart at 12 m --
+ *      as with kasf_pose_place's 1e-9, the geometry is then below what a keypoint can carry, and fp64 keeps seven digits at that pivot.  It is a floor for the
+ *      arithmetic, not a verdict on accuracy: rays a few milliradians apart pass it and fix a depth to metres; `residual` and the rig are the caller's judges.
+ *   3. Re-weighting, `iterations` times (in [0, 8]), at the X of the pass before, for each usable view:
+ *        Xc = R00 * X0 + R01 * X1 + R02 * X2 + t0;  Yc and Zc with rows 1 and 2 of R and t1, t2;  a usable view with !(Zc > 0) marks the point BEHIND
+ *        du = fx * (Xc / Zc - x);  dv = fy * (Yc / Zc - y);  rho = du * du + dv * dv          (pixels of the undistorted image, squared)
+ *        g = w0 / (1 + rho / (delta * delta));  wu = g * (fx * fx) / (Zc * Zc);  wv = g * (fy * fy) / (Zc * Zc)
+ *      then step 2's sums and solve with these weights: Hartley and Zisserman's iteratively re-weighted linear triangulation -- dividing by the depth turns
+ *      the algebraic error into pixels -- with kasf_pose_place's Cauchy weight, which takes a view that does not fit, a swapped joint for instance, out.
+ *      delta is in pixels; delta * delta is the product of the two fp32 values in fp64.  With two views nothing tells which of them is wrong: the re-weighting
+ *      cannot help there, only the residual shows it.  The sums run in view order, so permuting the views may change the last bits.
+ *   4. One more pass only measures, at the final X: rho per usable view as in step 3 (its Zc is tested as well); num = num + w0 * rho and den = den + w0;
+ *        residual = fp32(sqrt(num / den)) in pixels;  view_residual[c] = fp32(sqrt(rho)), NaN for a view that is not usable;  points = fp32(X).
+ *   5. state, uint8, the first that applies:
+ *        1  used < min_views (min_views in [2, 16])
+ *        2  degenerate: in any pass a pivot fails the test (rays that do not spread) or X0, X1 or X2 is not finite
+ *        3  behind: a usable view has !(Zc > 0) at the X of any pass
+ *        0  triangulated
+ *      A point whose state is not 0 gets NaN (0x7fc00000) in points, in residual and in every view_residual: kasf_tracks_refine over the points (has_score = 0)
+ *      then interpolates it from its neighbours on a recorded track.
+ *
+ * kasf_keypoints_triangulate: keypoints [views][M][3], M = frames * points_per_frame points in frame-major order; cameras [views][21] for a static rig, or with
+ * cameras_per_frame != 0 [views][M / points_per_frame][21] for moving cameras; points [M][3]; residual [M], used [M], state [M] and view_residual [views][M]
+ * may each be NULL.  All device pointers.  One launch: one lane per point, a workgroup stages the 128 records of a tile view by view in LDS (float4 where the
+ * view's tile is 16-byte aligned), undistorts them once and walks the views out of LDS with its sums in fp64 registers; the points leave as whole rows.  The
+ * inputs are only read; points is an array of its own.
+ * kasf_keypoints_undistort: keypoints, out [M][3], pixels in, undistorted pixels out: u' = fp32(fx * x + cx), v' = fp32(fy * y + cy) with `iterations` rounds;
+ * the score is copied.  camera is the first nine values of a row, [9], or with camera_per_frame != 0 [M / points_per_frame][9].  A point that is not usable
+ * -- |u| or |v| not <= 1e12f (one_euro.h's test without a score), or a camera value that is not finite -- is copied as it came.  out is an array of its own.
+ *
+ * M = 0 does nothing.  Error 2, before a device or a device pointer is touched: views outside [2, 16]; M negative or not a multiple of points_per_frame;
+ * points_per_frame < 1; a non-finite min_score; weighted neither 0 nor 1; iterations outside [0, 8]; delta not finite or not > 0; min_views outside [2, 16];
+ * undistort_iterations (iterations of the undistortion) outside [0, 20]; points == keypoints, out == keypoints; a null pointer (params included; residual,
+ * used, state and view_residual may be NULL).  The defaults of kasportsformer_amd/triangulate.py (min_score 0.3, weighted, 4 iterations, delta 3 px, 2 views,
+ * 5 rounds) are a starting point, not tuned on footage. */
+typedef struct kasf_triangulate_params {
+    float min_score;
+    int32_t weighted, iterations;
+    float delta;
+    int32_t min_views, undistort_iterations;
+} kasf_triangulate_params;
+int kasf_keypoints_triangulate(const float* keypoints, int32_t views, int64_t M, int32_t points_per_frame, const float* cameras, int32_t cameras_per_frame,
+                               const kasf_triangulate_params* params, float* points, float* residual, uint8_t* used, uint8_t* state, float* view_residual,
+                               void* stream);
+int kasf_keypoints_undistort(const float* keypoints, int64_t M, int32_t points_per_frame, const float* camera, int32_t camera_per_frame, int32_t iterations,
+                             float* out, void* stream);
 
 /* debugging / tests: locate a named activation inside the workspace (see kasf_ws_name()) */
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags);

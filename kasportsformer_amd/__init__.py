@@ -67,6 +67,11 @@ Public surface mirrors the reference's interface for this path:
                                         its keypoints through the camera's intrinsics, a 3 x 3 least-squares fit per frame in fp64 with Cauchy re-weighting and an
                                         optional metric scale from a bone table, so that several players stand where they stood; one launch, live and recorded
                                         (`python -m kasportsformer_amd.lift --place --camera FX,FY,CX,CY`)
+  triangulate_keypoints,                not in the reference (it is monocular): one player's keypoint tracks in 2 to 16 calibrated cameras -> joints in the world
+  undistort_keypoints, camera_row,      frame, per joint a 3 x 3 least-squares fit of the undistorted rays in fp64, re-weighted to pixels with the placement's Cauchy
+  TriangulateResult                     weight, with the re-projection error per point and per view (a check on a lifted pose, labels for new footage); and the
+                                        Brown-Conrady undistortion on its own, in front of `place_poses`; one launch each, one lane per joint
+                                        (`python -m kasportsformer_amd.lift --place --camera-distortion K1,K2,P1,P2,K3`)
   poses_to_world, DEMO_CAMERA_ROTATION  demo/lib/utils.py:55-73, demo/demo.py:242-248 (camera space -> world space, floor, unit scale; `--world`)
   draw_poses, bgr_to_nv12,              demo/demo.py:91-105,159-191,307-323, demo/lib/hrnet/lib/utils/utilitys.py:24-58 (`plot_on_frame`'s lines and dots over the frame, the
   poses_to_panel, DrawResult            score threshold, the 3-D plot's projection, and the frame as the NV12 surface an encoder takes, on the device: exact
@@ -99,6 +104,7 @@ from .smooth import OneEuroFilter, smooth_tracks
 from .refine import refine_tracks
 from .bones import fix_bone_lengths, bone_lengths, BoneLengthFilter
 from .place import place_poses, PlaceResult
+from .triangulate import triangulate_keypoints, undistort_keypoints, camera_row, TriangulateResult
 
 __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_stream", "set_deterministic", "is_deterministic", "set_fused_attention_backward", "is_fused_attention_backward", "loss3", "loss7", "LOSS7_NAMES", "FusedAdamW", "AdamW", "plan_chunks", "DataParallel", "joint_flip", "predict_flip_tta", "clip_metrics", "Evaluator",
            "evaluate_one_epoch", "PackedClips", "DeviceClipLoader", "pack_clip_directory", "read_clip_file", "shard_indices",
@@ -106,4 +112,4 @@ __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_strea
            "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample",
            "lift_track", "lift_tracks", "window_plan", "StreamLifter", "coco_to_h36m", "poses_to_world", "DEMO_CAMERA_ROTATION", "heatmaps_to_keypoints", "gaussian_weights",
            "detections_to_boxes", "yolo_heads_to_boxes", "DetectResult", "YOLOV3_ANCHORS", "YOLOV3_MASKS", "crop_persons", "CropResult", "letterbox_frames", "LetterboxResult", "yuv_to_bgr", "nv12_to_bgr", "i420_to_bgr", "SortTracker", "TrackResult", "TrackState",
-           "TrackedLifter", "TrackedTick", "OneEuroFilter", "smooth_tracks", "refine_tracks", "fix_bone_lengths", "bone_lengths", "BoneLengthFilter", "place_poses", "PlaceResult", "draw_poses", "bgr_to_nv12", "poses_to_panel", "DrawResult"]
+           "TrackedLifter", "TrackedTick", "OneEuroFilter", "smooth_tracks", "refine_tracks", "fix_bone_lengths", "bone_lengths", "BoneLengthFilter", "place_poses", "PlaceResult", "triangulate_keypoints", "undistort_keypoints", "camera_row", "TriangulateResult", "draw_poses", "bgr_to_nv12", "poses_to_panel", "DrawResult"]

@@ -86,6 +86,15 @@ def index_in(v, who: str, name: str, lo=None, hi=None, any_index: bool = False) 
     return v
 
 
+def number(v, who: str, name: str) -> float:
+    """A Python or numpy real number that is not a bool and is finite as the float32 an entry point takes."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{who}: {name} must be a number, got {type(v).__name__}")
+    if not np.isfinite(np.float32(v)):
+        raise ValueError(f"{who}: {name} must be finite, got {v}")
+    return float(v)
+
+
 def step(p: torch.Tensor, dim: int, least: int) -> int:
     """The stride of dimension dim in bytes; a dimension of one element has no stride to speak of, so the least legal one stands in for it."""
     return int(p.stride(dim)) if p.shape[dim] > 1 else max(int(p.stride(dim)), least)

@@ -59,6 +59,11 @@ class KasfPlaceParams(C.Structure):       # kasf_place_params: host values, pass
     _fields_ = [("min_score", C.c_float), ("weighted", C.c_int32), ("iterations", C.c_int32), ("delta", C.c_float), ("min_joints", C.c_int32)]
 
 
+class KasfTriangulateParams(C.Structure):  # kasf_triangulate_params: host values, passed by value into the launch
+    _fields_ = [("min_score", C.c_float), ("weighted", C.c_int32), ("iterations", C.c_int32), ("delta", C.c_float), ("min_views", C.c_int32),
+                ("undistort_iterations", C.c_int32)]
+
+
 class KasfRefineParams(C.Structure):      # kasf_refine_params: host values, passed by value into the launch; weights[k] = the weight at distance k frames
     _fields_ = [("min_score", C.c_float), ("max_gap", C.c_int32), ("radius", C.c_int32), ("weights", C.c_float * 33)]
 
@@ -130,6 +135,8 @@ SIGNATURES = {
     "kasf_bone_push": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "kasf_bone_tracked": (_i32, [_vp] * 5 + [_i32] * 6 + [_vp] * 6),
     "kasf_pose_place": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i32, C.POINTER(KasfPlaceParams)] + [_vp] * 6),
+    "kasf_keypoints_triangulate": (_i32, [_vp, _i32, _i64, _i32, _vp, _i32, C.POINTER(KasfTriangulateParams)] + [_vp] * 6),
+    "kasf_keypoints_undistort": (_i32, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp]),
     "kasf_coco_h36m": (_i32, [_vp, _i64, _vp, _vp]),
     "kasf_pose_world": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "kasf_heatmap_keypoints": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i32, C.c_double, _i32, _i32, _vp, _vp, _vp]),

@@ -261,6 +261,20 @@ void kasf_launch_pose_place(hipStream_t s, const float* poses, const float* keyp
                             const float* lengths, int lengths_per_frame, const KasfPlace& p, float* out, float* root, float* residual, float* scale,
                             unsigned char* state);
 
+// ---- k_triangulate.hip: keypoints of several calibrated cameras -> world-space points (kasf.h, kasf_keypoints_triangulate / kasf_keypoints_undistort);
+// keypoints [C][M][3] fp32, cameras [C][21] or [C][M / ppf][21] (camera_model.h), points [M][3] a distinct array; residual [M], used [M] bytes, state [M] bytes
+// and view_residual [C][M] may be null; the parameters as the entry point checked them, passed by value into the launch ----
+struct KasfTriangulate {
+    float min_score, delta;
+    int weighted, iterations, min_views, undistort_iterations;
+};
+void kasf_launch_keypoints_triangulate(hipStream_t s, const float* keypoints, int C, int64_t M, int ppf, const float* cameras, int cameras_per_frame,
+                                       const KasfTriangulate& p, float* points, float* residual, unsigned char* used, unsigned char* state,
+                                       float* view_residual);
+// keypoints, out [M][3], distinct arrays; camera [9] (fx, fy, cx, cy, k1, k2, p1, p2, k3) or [M / ppf][9]
+void kasf_launch_keypoints_undistort(hipStream_t s, const float* keypoints, int64_t M, int ppf, const float* camera, int camera_per_frame, int rounds,
+                                     float* out);
+
 // ---- k_heatmap.hip: pose-network heatmaps hm [n,17,H,W] (dtype KASF_F32 / KASF_F16 / KASF_BF16) -> out [n,17,3] fp32 image x, y, score in COCO order (kasf.h,
 // kasf_heatmap_keypoints); geom [n,4] fp32: kind 0 = center x, y, scale x, y; kind 1 = box x1, y1, x2, y2 widened to `aspect`; H * W <= 2^24 ----
 void kasf_launch_heatmap_keypoints(hipStream_t s, const void* hm, int dtype, int64_t n, int H, int W, const float* geom, int geom_kind, double aspect,

@@ -26,7 +26,8 @@ track (``kasportsformer_amd.refine.refine_tracks``: occlusion gaps filled from b
 and ``--refine-poses`` runs the same over the lifted poses, before ``--fix-bones``; ``--fix-bones [--fix-bones-symmetric]`` gives every bone of a track one length
 (``kasportsformer_amd.bones.fix_bone_lengths`` over the final poses, before ``--world``); ``--place --camera FX,FY,CX,CY [--place-lengths table.npy]
 [--place-iterations] [--place-delta]`` then puts every pose where its player stood in front of the camera (``kasportsformer_amd.place.place_poses``, after
-``--fix-bones`` and ``--refine-poses``, before ``--world``; not with ``--world-unit``; an ``.npz`` output also gets ``root_i`` and ``place_state_i`` per track); ``--world [--world-floor] [--world-unit]`` sends the poses through ``poses_to_world`` before they are written.
+``--fix-bones`` and ``--refine-poses``, before ``--world``; not with ``--world-unit``; an ``.npz`` output also gets ``root_i`` and ``place_state_i`` per track;
+``--camera-distortion K1,K2,P1,P2,K3`` sends the keypoints it is given through ``kasportsformer_amd.triangulate.undistort_keypoints`` first); ``--world [--world-floor] [--world-unit]`` sends the poses through ``poses_to_world`` before they are written.
 """
 from __future__ import annotations
 
@@ -332,7 +333,9 @@ def _parse(argv=None):
     ap.add_argument("--fix-bones-symmetric", action="store_true", help="--fix-bones: left / right partner bones get their mean")
     ap.add_argument("--place", action="store_true", help="place every pose in camera space from its keypoints and --camera (kasportsformer_amd.place_poses), "
                                                          "after --refine-poses and --fix-bones, before --world; an .npz output also gets root_i and place_state_i")
-    ap.add_argument("--camera", default=None, help="--place: the pinhole intrinsics FX,FY,CX,CY in pixels (no lens distortion is modelled)")
+    ap.add_argument("--camera", default=None, help="--place: the pinhole intrinsics FX,FY,CX,CY in pixels (a lens with distortion: --camera-distortion)")
+    ap.add_argument("--camera-distortion", default=None, help="--place: the lens' Brown-Conrady coefficients K1,K2,P1,P2,K3 (OpenCV's order): the keypoints "
+                                                              "given to the placement are undistorted first (kasportsformer_amd.undistort_keypoints)")
     ap.add_argument("--place-lengths", default=None, help="--place: an .npy of the sixteen bone lengths in metres (0 skips a bone): the roots come out in metres")
     ap.add_argument("--place-iterations", type=int, default=None, help="--place: rounds of Cauchy re-weighting, in [0, 8] (default 4)")
     ap.add_argument("--place-delta", type=float, default=None, help="--place: the re-weighting's scale in pixels (default 3.0; a starting point, not tuned on footage)")
@@ -366,6 +369,8 @@ def _parse(argv=None):
     place_defaults = dict(place_iterations=4, place_delta=3.0)
     if not args.place and (args.camera is not None or args.place_lengths is not None or any(getattr(args, k) is not None for k in place_defaults)):
         ap.error("--camera, --place-lengths, --place-iterations and --place-delta belong to --place")
+    if not args.place and args.camera_distortion is not None:
+        ap.error("--camera-distortion belongs to --place")
     for k, v in place_defaults.items():
         if getattr(args, k) is None:
             setattr(args, k, v)
@@ -381,6 +386,14 @@ def _parse(argv=None):
         if len(camera) != 4 or not all(np.isfinite(np.float32(v)) for v in camera) or not (camera[0] > 0 and camera[1] > 0):
             ap.error(f"--camera must be four finite numbers FX,FY,CX,CY with FX, FY > 0, got {args.camera!r}")
         args.camera = np.array(camera, np.float32)
+        if args.camera_distortion is not None:
+            try:
+                lens = [float(v) for v in args.camera_distortion.split(",")]
+            except ValueError:
+                lens = []
+            if len(lens) != 5 or not all(abs(v) <= float(np.finfo(np.float32).max) for v in lens):         # false for a NaN: finite as the device's fp32
+                ap.error(f"--camera-distortion must be five finite numbers K1,K2,P1,P2,K3, got {args.camera_distortion!r}")
+            args.camera_distortion = np.array(lens, np.float32)
         if not 0 <= args.place_iterations <= 8:
             ap.error("--place-iterations must be in [0, 8]")
         if not (np.isfinite(args.place_delta) and args.place_delta > 0):
@@ -427,7 +440,11 @@ def main(argv=None):
         if args.place:                                 # the keypoints in the layout the model saw; frames that cannot be placed come out NaN
             from .place import place_poses
             from .pose import coco_to_h36m
-            placed = place_poses(poses, coco_to_h36m(kp, device=poses.device) if args.layout == "coco" else kp, args.camera, metric_lengths=place_table,
+            kp = coco_to_h36m(kp, device=poses.device) if args.layout == "coco" else kp
+            if args.camera_distortion is not None:     # the placement's camera is a pinhole: it gets the keypoints that one would have seen
+                from .triangulate import undistort_keypoints
+                kp = undistort_keypoints(kp, args.camera, args.camera_distortion, device=poses.device)
+            placed = place_poses(poses, kp, args.camera, metric_lengths=place_table,
                                  iterations=args.place_iterations, delta=args.place_delta, device=poses.device)
             poses = placed.poses
             if i is not None:

@@ -11,7 +11,7 @@ that makes a pose re-project onto the keypoints it was lifted from is a 3 x 3 we
 states the rule in full: a joint is usable by the One-Euro filter's test (finite keypoint, score at least ``min_score``) when its pose values are finite;
 the fit is accumulated and solved in fp64 (the system's condition number reaches 4e4 for players at 40 m); ``iterations`` rounds of Cauchy re-weighting with
 ``delta`` pixels take the weight off a keypoint that does not fit, a swapped wrist for instance; results are rounded to fp32 once.  The camera is a pinhole:
-there is no lens-distortion model.
+for a lens with distortion, send the keypoints through ``undistort_keypoints`` (triangulate.py) first.
 
 Metres come one of two ways.  ``metric_lengths``: a table of the sixteen bone lengths in metres (``bones.BONE_PARENTS``' bones, 0 skips a bone); every frame's
 pose is multiplied by (the table's sum) / (the frame's sum over the same bones) before the fit -- per frame, because the model's unit is image pixels and a
@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _args, _lib
-from ._args import index_in
+from ._args import index_in, number as _number
 
 MAX_ITERATIONS, MIN_JOINTS, JOINTS, BONES = 8, 2, 17, 16       # iterations in [0, 8] and min_joints in [2, 17] of kasf_pose_place
 
@@ -45,14 +45,6 @@ class PlaceResult(NamedTuple):
     residual: torch.Tensor
     scale: torch.Tensor
     state: torch.Tensor
-
-
-def _number(v, who: str, name: str) -> float:
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise TypeError(f"{who}: {name} must be a number, got {type(v).__name__}")
-    if not np.isfinite(np.float32(v)):
-        raise ValueError(f"{who}: {name} must be finite, got {v}")
-    return float(v)
 
 
 def place_params(min_score=0.3, weighted=True, iterations=4, delta=3.0, min_joints=4, who: str = "place_poses") -> _lib.KasfPlaceParams:
@@ -92,7 +84,7 @@ def place_poses(poses, keypoints, camera, *, metric_lengths=None, min_score: flo
                 min_joints: int = 4, device=None) -> PlaceResult:
     """Root-relative poses placed in front of the camera; see the module docstring.  ``poses`` [...,17,3] (any one unit) and ``keypoints`` of the same shape
     (pixel x, pixel y, score in the H36M-17 layout): float32, numpy or torch, on the host or the GPU, never modified.  ``camera``: float32 [4] = fx, fy, cx, cy
-    in pixels (a pinhole: no distortion), or ``poses.shape[:-2] + (4,)``, a row per frame.  ``metric_lengths``: None, or float32 [16] metres (0 skips a bone), or
+    in pixels (a pinhole: ``undistort_keypoints`` goes in front for a lens), or ``poses.shape[:-2] + (4,)``, a row per frame.  ``metric_lengths``: None, or float32 [16] metres (0 skips a bone), or
     ``poses.shape[:-2] + (16,)``.  ``min_score``: a keypoint scored below it is not used; ``weighted``: weigh a keypoint by its score; ``iterations`` in [0, 8]
     rounds of Cauchy re-weighting with ``delta`` pixels; ``min_joints`` in [2, 17].  -> ``PlaceResult`` on the device; a frame whose ``state`` is not 0 is NaN in
     ``poses``, ``root`` and ``residual`` (``refine_tracks(r.root.unsqueeze(-2), score=False)`` fills it on a recorded track).  One launch.  The defaults are a
