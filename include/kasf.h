@@ -69,6 +69,8 @@
  *                             onto its keypoints through the camera's intrinsics, so that several players stand where they stood
  *   kasf_keypoints_triangulate, kasf_keypoints_undistort <- nothing in the reference (it is monocular): the keypoints of one player in several calibrated cameras
  *                             to joints in the world frame, and the Brown-Conrady undistortion that this and kasf_pose_place need in front of them
+ *   kasf_match_pair_costs, kasf_match_groups <- nothing in the reference: which of the rows that several cameras' trackers emit are the same player, from the
+ *                             gaps between their keypoints' rays; what puts kasf_keypoints_triangulate behind kasf_sort_update without a host round trip
  *   kasf_op_*              <- the individual nn.Modules under model/modules/ (unit-test entry points)
  *   kasf_op_gcn_fwd, kasf_op_gcn_bwd <- GCN.forward between its U | V Linear and the residual, and autograd of it   model/modules/graph.py:19-134, KASportsFormer.py:109
  */
@@ -1077,7 +1079,7 @@ int kasf_pose_place(const float* poses, const float* keypoints, int64_t frames, 
 /* ---- keypoints of several calibrated cameras -> joints in the world frame, and the lens undistortion (ADDED under ABI 12: additive, kasf_version() stays 12;
  * look the symbols up by name).  A player tracked in C synchronised, calibrated cameras has C keypoint tracks; this stage triangulates them, point by point --
  * one joint of one frame --, on the device.  Points are independent of one another: a recorded track and one live tick are the same call.  Nothing is read
- * back, nothing is allocated, no atomics: the same bits from run to run.  Calibration, synchronisation and matching players across cameras are the caller's.
+ * back, nothing is allocated, no atomics: the same bits from run to run.  Calibration and synchronisation are the caller's; which tracks are one player: kasf_match_* below.
  *
  * THE CAMERA MODEL, stated once (csrc/camera_model.h).  A camera is 21 fp32 values: fx, fy, cx, cy in pixels; k1, k2, p1, p2, k3, the Brown-Conrady
  * coefficients in OpenCV's order; R [9] row-major and t [3] with X_cam = R X_world + t.  ALL ARITHMETIC BELOW IS IN FP64, views in ascending order, every line
@@ -1154,6 +1156,82 @@ int kasf_keypoints_triangulate(const float* keypoints, int32_t views, int64_t M,
                                void* stream);
 int kasf_keypoints_undistort(const float* keypoints, int64_t M, int32_t points_per_frame, const float* camera, int32_t camera_per_frame, int32_t iterations,
                              float* out, void* stream);
+
+/* ---- matching players across calibrated cameras (no counterpart in the reference, which is monocular): each camera's tracker emits P rows of keypoint tracks,
+ * in its own order and with its own ids; these two entries say which row of which camera is the same player, so that kasf_keypoints_triangulate can be fed
+ * without the tracks leaving the device.  Cameras are rows of 21 values as above, a static rig only.
+ *
+ * THE PAIR RULE (kasf_match_pair_costs), in fp64 with the arithmetic of the triangulation rule above: every operation rounded, in the order the parentheses
+ * give and then left to right, no fused multiply-add, a correctly rounded divide and square root; fp32 inputs enter by an exact conversion, the cost is rounded
+ * to fp32 once.  keypoints [C][P][N][J][3]: C cameras (2 <= C <= 16), P rows per camera (1 <= P <= 64, padded), N synchronised frames, J joints, (u, v, score).
+ *   1. A SAMPLE is one joint of one frame of one row.  It is USABLE by step 1 of the triangulation rule, the same code: |u|, |v| <= 1e12f, score >= min_score
+ *      (a NaN fails) and the 21 values of its camera finite.  (x, y) = its undistorted point (`undistort_iterations` rounds).  Its ray, in the world frame:
+ *        o = 0 - (R0k * t0 + R1k * t1 + R2k * t2), k = 0, 1, 2   (the camera's centre -R^T t)
+ *        d = R0k * x + R1k * y + R2k, k = 0, 1, 2                  (R^T (x, y, 1): the parameter along the ray is the depth in the ray's camera)
+ *        f = 0.5 * (fx + fy)
+ *   2. For cameras a < b, row p of a and row q of b, and a sample index (frame n, joint j) at which both samples are usable, with (o, d, f) of a written
+ *      (oa, a, fa) and of b (ob, b, fb):
+ *        w = oa - ob (three components);  aa = a0 * a0 + a1 * a1 + a2 * a2;  bb likewise of b;  ab = a0 * b0 + a1 * b1 + a2 * b2
+ *        da = a0 * w0 + a1 * w1 + a2 * w2;  db = b0 * w0 + b1 * w1 + b2 * w2;  det = aa * bb - ab * ab
+ *        THE PARALLEL TEST: det > 1e-10 * (aa * bb) (a NaN fails) -- det / (aa * bb) is the squared sine of the angle between the rays, so rays closer than
+ *        1e-5 rad are not compared; two cameras with one centre give w = 0, s = t = 0, which the next test refuses.
+ *        s = (ab * db - bb * da) / det;  t = (aa * db - ab * da) / det     (the depths of closest approach)
+ *        s > 0 and t > 0 and both finite, else the sample is NOT COMPARABLE (a closest approach behind a camera)
+ *        g_k = (oa_k + s * a_k) - (ob_k + t * b_k);  g = sqrt(g0 * g0 + g1 * g1 + g2 * g2)        (the gap between the rays, in world units)
+ *        e = 0.5 * g * (fa / s + fb / t)                                                          (the gap in pixels at the two depths, averaged)
+ *        e finite, else not comparable.
+ *   3. The sums of a pair (a, p, b, q) over its comparable samples, wt = score_a * score_b (the fp32 scores' product in fp64) when weighted, else 1:
+ *        num = num + wt * min(e, cap);  den = den + wt;  count = count + 1           (cap: the fp32 value in fp64; min(e, cap) is e when e < cap)
+ *      THE ORDER: the frames are cut into tiles of 256; a tile's sums start at 0 and take its samples frame by frame, joints ascending within a frame; the
+ *      pair's sums start at 0 and take the tiles' sums in ascending order.  The order depends on the sample index alone: not on the grid, not on the other rows
+ *      or cameras -- a pair has the same bits when only its two cameras are given -- and the same bits come out run after run (no atomics).
+ *   4. samples[a][b][p][q] = count.  cost[a][b][p][q] = fp32(num / den) when count >= min_samples, else +inf.  cost[b][a][q][p] and samples[b][a][q][p] are
+ *      the same values with the same bits.  The diagonal blocks a == a are +inf with 0 samples.  A weighted pair whose comparable samples all score 0 is 0 / 0.
+ *
+ * THE GROUPING RULE (kasf_match_groups) over any cost and samples [C][C][P][P], in one launch of one wavefront; cameras are taken in ascending order, so the
+ * result depends on the order of the cameras: the first camera's rows seed the groups, and a player it did not see is only grouped from the camera that first
+ * did.  That is a property of the rule, not of the kernel.
+ *   A group holds at most one row per camera.  There are none at the start.  For camera c = 0, 1, ...:
+ *   1. Row q of c is NON-EMPTY when samples[c][m][q][r] > 0 for some other camera m and some row r: a row that was never comparable with anything -- a padded
+ *      row, or a player at whom, over the whole track, no other camera looked at anybody -- stays out, group -1.
+ *   2. The cost of non-empty row q to group g, over g's members (m, r), cameras m ascending, that are COMPARABLE with it -- cost[m][c][r][q] finite and
+ *      samples[m][c][r][q] > 0:  num = num + samples * cost;  den = den + samples (both fp64, starting at 0);  the cost is num / den, or BIG = 1e9 when g
+ *      has no comparable member.
+ *   3. The assignment of non-empty rows to groups that makes min(rows, groups) pairs with the least total cost, by the shortest-augmenting-path method of
+ *      kasf_sort_update (csrc/assignment.h: rows of the walk = the smaller side, the non-empty rows in ascending order and the groups in ascending order, ties
+ *      by the totally ordered key (cost, column already assigned, column)).
+ *   4. As in SORT's rule 4 a pair made by the assignment is REJECTED when its cost is >= BIG or > max_cost; an accepted row joins its group.
+ *   5. The non-empty rows without a group, in ascending row order, open new groups while fewer than max_groups exist; the rest count in `dropped`, group -1.
+ *   group [C][P]: the row's group or -1;  members [max_groups][C]: the group's row in each camera or -1;  views [max_groups]: its number of members (0 for
+ *   a group that was never opened);  group_cost [max_groups]: fp32 of the mean, in fp64 in camera order, of the costs at which its rows were accepted, NaN
+ *   (0x7fc00000) for a group of one view or none;  count [1]: the groups opened;  dropped [1].
+ *
+ * kasf_match_workspace_bytes: the bytes kasf_match_pair_costs needs at `workspace` (8-byte aligned; the tiles' sums): 20 * ceil(frames / 256) * C (C - 1) / 2
+ * * P * P.  -2 on a refusal.
+ * kasf_match_pair_costs: two launches -- the pairs, then the sum over tiles (see csrc/k_match.hip for the kernel's shape: a workgroup stages 16 samples of
+ * every row of a camera pair through LDS, undistorts them once and walks up to 256 pairs; no ray is written to global memory).  frames = 0 does nothing and
+ * leaves cost and samples as they were.  All device pointers; the inputs are only read.
+ * kasf_match_groups: one launch.  Nothing is read back by either.
+ *
+ * Error 2, before a device or a device pointer is touched: cameras outside [2, 16]; rows outside [1, 64]; frames outside [0, 2^31 - 1]; joints < 1; frames *
+ * joints >= 2^31; a non-finite min_score; weighted neither 0 nor 1; cap or max_cost not finite or not > 0; min_samples < 1; undistort_iterations outside
+ * [0, 20]; max_groups outside [1, 64]; a workspace that is too small or not 8-byte aligned; a null pointer (params included).  The defaults of
+ * kasportsformer_amd/match.py (min_score 0.3, weighted, cap 50 px, min_samples 2 * J, 5 rounds, max_cost 15 px) are a starting point, not tuned: nothing was
+ * run on footage.  Not here: synchronising the cameras in time, moving cameras, a stateful live matcher that keeps group ids from tick to tick, and
+ * cycle-consistent multi-way matching (this rule is greedy in the camera order). */
+#define KASF_MATCH_MAX_CAMERAS 16
+#define KASF_MATCH_MAX_ROWS 64
+typedef struct kasf_match_params {
+    float min_score;
+    int32_t weighted;
+    float cap;
+    int32_t min_samples, undistort_iterations;
+} kasf_match_params;
+int64_t kasf_match_workspace_bytes(int32_t cameras, int32_t rows, int64_t frames);
+int kasf_match_pair_costs(const float* keypoints, int32_t cameras, int32_t rows, int64_t frames, int32_t joints, const float* camera_rows,
+                          const kasf_match_params* params, float* cost, int32_t* samples, void* workspace, int64_t workspace_bytes, void* stream);
+int kasf_match_groups(const float* cost, const int32_t* samples, int32_t cameras, int32_t rows, float max_cost, int32_t max_groups, int32_t* group,
+                      int32_t* members, int32_t* views, float* group_cost, int32_t* count, int32_t* dropped, void* stream);
 
 /* debugging / tests: locate a named activation inside the workspace (see kasf_ws_name()) */
 int32_t kasf_ws_entries(const kasf_model* m, int32_t batch, int32_t flags);

@@ -72,6 +72,10 @@ Public surface mirrors the reference's interface for this path:
   TriangulateResult                     weight, with the re-projection error per point and per view (a check on a lifted pose, labels for new footage); and the
                                         Brown-Conrady undistortion on its own, in front of `place_poses`; one launch each, one lane per joint
                                         (`python -m kasportsformer_amd.lift --place --camera-distortion K1,K2,P1,P2,K3`)
+  match_players, match_costs,           not in the reference: which of the rows that several cameras' trackers emit are the same player -- the cost of a pair of
+  match_groups, gather_matched,         rows is the mean gap between their keypoints' undistorted rays in pixels, in fp64 with every sum in a fixed order; the
+  MatchResult                           cameras are then taken in turn, each one's rows assigned to the groups so far by the tracker's optimal assignment --
+                                        and the tracks in group order, which is what `triangulate_keypoints` takes; three launches, nothing read back
   poses_to_world, DEMO_CAMERA_ROTATION  demo/lib/utils.py:55-73, demo/demo.py:242-248 (camera space -> world space, floor, unit scale; `--world`)
   draw_poses, bgr_to_nv12,              demo/demo.py:91-105,159-191,307-323, demo/lib/hrnet/lib/utils/utilitys.py:24-58 (`plot_on_frame`'s lines and dots over the frame, the
   poses_to_panel, DrawResult            score threshold, the 3-D plot's projection, and the frame as the NV12 surface an encoder takes, on the device: exact
@@ -105,6 +109,7 @@ from .refine import refine_tracks
 from .bones import fix_bone_lengths, bone_lengths, BoneLengthFilter
 from .place import place_poses, PlaceResult
 from .triangulate import triangulate_keypoints, undistort_keypoints, camera_row, TriangulateResult
+from .match import match_players, match_costs, match_groups, gather_matched, MatchResult, MatchCosts, MatchGroups
 
 __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_stream", "set_deterministic", "is_deterministic", "set_fused_attention_backward", "is_fused_attention_backward", "loss3", "loss7", "LOSS7_NAMES", "FusedAdamW", "AdamW", "plan_chunks", "DataParallel", "joint_flip", "predict_flip_tta", "clip_metrics", "Evaluator",
            "evaluate_one_epoch", "PackedClips", "DeviceClipLoader", "pack_clip_directory", "read_clip_file", "shard_indices",
@@ -112,4 +117,4 @@ __all__ = ["KASportsFormer", "load_model", "set_single_stream", "is_single_strea
            "synthetic_clips", "synthetic_test_extras", "teacher_labels", "teacher_clips", "slice_source", "split_clips", "mysplit_clips", "resample",
            "lift_track", "lift_tracks", "window_plan", "StreamLifter", "coco_to_h36m", "poses_to_world", "DEMO_CAMERA_ROTATION", "heatmaps_to_keypoints", "gaussian_weights",
            "detections_to_boxes", "yolo_heads_to_boxes", "DetectResult", "YOLOV3_ANCHORS", "YOLOV3_MASKS", "crop_persons", "CropResult", "letterbox_frames", "LetterboxResult", "yuv_to_bgr", "nv12_to_bgr", "i420_to_bgr", "SortTracker", "TrackResult", "TrackState",
-           "TrackedLifter", "TrackedTick", "OneEuroFilter", "smooth_tracks", "refine_tracks", "fix_bone_lengths", "bone_lengths", "BoneLengthFilter", "place_poses", "PlaceResult", "triangulate_keypoints", "undistort_keypoints", "camera_row", "TriangulateResult", "draw_poses", "bgr_to_nv12", "poses_to_panel", "DrawResult"]
+           "TrackedLifter", "TrackedTick", "OneEuroFilter", "smooth_tracks", "refine_tracks", "fix_bone_lengths", "bone_lengths", "BoneLengthFilter", "place_poses", "PlaceResult", "triangulate_keypoints", "undistort_keypoints", "camera_row", "TriangulateResult", "match_players", "match_costs", "match_groups", "gather_matched", "MatchResult", "MatchCosts", "MatchGroups", "draw_poses", "bgr_to_nv12", "poses_to_panel", "DrawResult"]

@@ -27,6 +27,7 @@ DRAW_MAX_JOINTS, DRAW_MAX_SEGMENTS, DRAW_MAX_FILLS = 32, 32, 8      # kasf_draw_
 DRAW_MAX_THICKNESS, DRAW_MAX_RADIUS = 64, 32
 SORT_MAX = 64                          # KASF_SORT_MAX: slots and max_dets of kasf_sort_update
 SORT_HEADER_BYTES = 64                 # KASF_SORT_HEADER_BYTES
+MATCH_MAX_CAMERAS, MATCH_MAX_ROWS = 16, 64     # KASF_MATCH_MAX_CAMERAS, KASF_MATCH_MAX_ROWS: cameras, rows and max_groups of kasf_match_*
 FLAG_TRAIN, FLAG_RETURN_REP, FLAG_KEEP = 1, 2, 4
 FLAG_INPUT_GRAD = 8                    # KASF_FLAG_INPUT_GRAD: kasf_backward also leaves d/dx in the workspace entry "dx_input"
 EVAL_COLS = 22
@@ -62,6 +63,10 @@ class KasfPlaceParams(C.Structure):       # kasf_place_params: host values, pass
 class KasfTriangulateParams(C.Structure):  # kasf_triangulate_params: host values, passed by value into the launch
     _fields_ = [("min_score", C.c_float), ("weighted", C.c_int32), ("iterations", C.c_int32), ("delta", C.c_float), ("min_views", C.c_int32),
                 ("undistort_iterations", C.c_int32)]
+
+
+class KasfMatchParams(C.Structure):        # kasf_match_params: host values, passed by value into the launch
+    _fields_ = [("min_score", C.c_float), ("weighted", C.c_int32), ("cap", C.c_float), ("min_samples", C.c_int32), ("undistort_iterations", C.c_int32)]
 
 
 class KasfRefineParams(C.Structure):      # kasf_refine_params: host values, passed by value into the launch; weights[k] = the weight at distance k frames
@@ -137,6 +142,9 @@ SIGNATURES = {
     "kasf_pose_place": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i32, C.POINTER(KasfPlaceParams)] + [_vp] * 6),
     "kasf_keypoints_triangulate": (_i32, [_vp, _i32, _i64, _i32, _vp, _i32, C.POINTER(KasfTriangulateParams)] + [_vp] * 6),
     "kasf_keypoints_undistort": (_i32, [_vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "kasf_match_workspace_bytes": (_i64, [_i32, _i32, _i64]),
+    "kasf_match_pair_costs": (_i32, [_vp, _i32, _i32, _i64, _i32, _vp, C.POINTER(KasfMatchParams), _vp, _vp, _vp, _i64, _vp]),
+    "kasf_match_groups": (_i32, [_vp, _vp, _i32, _i32, _f32, _i32] + [_vp] * 7),
     "kasf_coco_h36m": (_i32, [_vp, _i64, _vp, _vp]),
     "kasf_pose_world": (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "kasf_heatmap_keypoints": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _i32, C.c_double, _i32, _i32, _vp, _vp, _vp]),

@@ -275,6 +275,20 @@ void kasf_launch_keypoints_triangulate(hipStream_t s, const float* keypoints, in
 void kasf_launch_keypoints_undistort(hipStream_t s, const float* keypoints, int64_t M, int ppf, const float* camera, int camera_per_frame, int rounds,
                                      float* out);
 
+// ---- k_match.hip: the keypoint tracks of P rows in each of C calibrated cameras -> pair costs and groups (kasf.h, kasf_match_pair_costs / kasf_match_groups);
+// keypoints [C][P][N][J][3] fp32, cameras [C][21] (camera_model.h), cost and samples [C][C][P][P], workspace kasf_match_workspace(C, P, N) bytes, 8-byte
+// aligned; the parameters as the entry point checked them, passed by value into the launch ----
+struct KasfMatch {
+    float min_score, cap;
+    int weighted, min_samples, undistort_iterations;
+};
+int64_t kasf_match_workspace(int C, int P, int64_t N);
+void kasf_launch_match_pair_costs(hipStream_t s, const float* keypoints, int C, int P, int64_t N, int J, const float* cameras, const KasfMatch& p, float* cost,
+                                  int* samples, void* workspace);
+// cost, samples [C][C][P][P] (any source) -> group [C][P], members [G][C], views [G], group_cost [G], count and dropped [1]
+void kasf_launch_match_groups(hipStream_t s, const float* cost, const int* samples, int C, int P, float max_cost, int G, int* group, int* members, int* views,
+                              float* group_cost, int* count, int* dropped);
+
 // ---- k_heatmap.hip: pose-network heatmaps hm [n,17,H,W] (dtype KASF_F32 / KASF_F16 / KASF_BF16) -> out [n,17,3] fp32 image x, y, score in COCO order (kasf.h,
 // kasf_heatmap_keypoints); geom [n,4] fp32: kind 0 = center x, y, scale x, y; kind 1 = box x1, y1, x2, y2 widened to `aspect`; H * W <= 2^24 ----
 void kasf_launch_heatmap_keypoints(hipStream_t s, const void* hm, int dtype, int64_t n, int H, int W, const float* geom, int geom_kind, double aspect,

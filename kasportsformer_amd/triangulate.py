@@ -19,8 +19,9 @@ recorded track fills it.  ``residual``: the weighted RMS re-projection error in 
 to check a lifted and placed pose against, and what tells which camera's calibration has drifted.  Points are independent: a recorded track and one live tick
 are the same call.  One launch, nothing read back, no host path.
 
-Not here: calibration itself (estimating R, t or the coefficients), synchronising the cameras in time, matching players across cameras (the caller gives the C
-tracks of ONE player), rational and fisheye lens models, bundle adjustment.  The defaults are a starting point, not tuned on footage; accuracy has been shown
+Not here: calibration itself (estimating R, t or the coefficients), temporal synchronisation of the cameras, moving cameras for the matching
+in front of this call (``match_players`` says which rows of which cameras are ONE player: a static rig, no stateful live matcher that keeps group ids from tick to
+tick, no cycle-consistent multi-way matching), rational and fisheye lens models, bundle adjustment.  The defaults are a starting point, not tuned on footage; accuracy has been shown
 on synthetic players only.
 """
 from __future__ import annotations
