@@ -1409,6 +1409,44 @@ int kasf_op_gcn_fwd(int32_t dtype, const void* x_in, const void* xn, const void*
  * (0: mean and variance are constants, duv has no batch-mean terms). */
 int kasf_op_gcn_bwd(int32_t dtype, const void* g, const void* xn, const void* y, const float* coef, const uint32_t* mask, const float* ls1, void* r, void* duv,
                     float* dls1, float* d_bn_w, float* d_bn_b, void* bstats, int32_t batch, int32_t n_frames, int32_t mode, int32_t training, void* stream);
+/* ---- the MLP, data-gradient and GCN backward kernels in the form a backward stage runs them (ADDED under ABI 12: additive, kasf_version() stays 12).  Each entry
+ * puts a column sink on the caller's scratch, calls the launcher that kasf_backward calls, and finishes the sink in a fixed order on `stream`: every per-channel
+ * sum (dgamma, dbeta, db1, colsum(g), dls1) leaves its kernel as one row per workgroup and is bit-reproducible.  scratch: device floats, 16-byte aligned,
+ * scratch_floats >= kasf_op_sink_scratch_floats(...).  Error 2: scratch with scratch_floats < 1 or misaligned, and what the entry without scratch refuses.
+ * kasf_op_mlp_bwd_rows, kasf_op_dgrad_lnbwd_rows, kasf_op_gcn_bwd_rows: the parameters and results of kasf_op_mlp_bwd, kasf_op_dgrad_lnbwd and kasf_op_gcn_bwd.  A NULL
+ * scratch is that entry (fp32 atomics); a scratch that is too small falls back to the atomics (results still complete) and returns error 6. */
+#define KASF_SINK_MLP_BWD_FUSED_FC2 0
+#define KASF_SINK_MLP_BWD_ROWS 1
+#define KASF_SINK_DGRAD_LNBWD_ROWS 2
+#define KASF_SINK_GCN_BWD_ROWS 3
+#define KASF_SINK_FORM_RESID 1
+#define KASF_SINK_FORM_DXN_ADD 2
+#define KASF_SINK_FORM_ACCUMULATE 4
+#define KASF_SINK_FORM_XN_OUT 8
+/* floats of scratch the entry asks for at M tokens (gcn_bwd_rows: M = batch * n_frames * 17): the sum over the launch's requests of rows * row length, each rounded up to
+ * 64 floats.  dtype: of the call (ignored by mlp_bwd_fused_fc2).  Kd and form (KASF_SINK_FORM_* of the operands given) are read for dgrad_lnbwd_rows only: they
+ * decide which kernel runs.  -2 with kasf_last_error() set: M < 1, unknown op, bad dtype, Kd not a multiple of 128.  Needs no device. */
+int64_t kasf_op_sink_scratch_floats(int32_t op, int32_t dtype, int64_t M, int32_t Kd, int32_t form);
+int kasf_op_mlp_bwd_rows(int32_t dtype, const void* x, const void* g, const float* ln_g, const float* ln_b, const void* w1, const float* b1,
+                         const void* w2t_scaled, const void* w1t, void* hbuf, void* dzbuf, void* g_in, float* dgamma, float* dbeta, int64_t M, float* scratch,
+                         int64_t scratch_floats, void* stream);
+int kasf_op_dgrad_lnbwd_rows(int32_t dtype, const void* dy, int32_t Kd, const void* wt, const void* dxn_add, const void* x, const float* gamma,
+                             const void* resid, void* out, int32_t accumulate, float* dgamma, float* dbeta, int64_t M, void* xn_out, const float* beta,
+                             float* scratch, int64_t scratch_floats, void* stream);
+int kasf_op_gcn_bwd_rows(int32_t dtype, const void* g, const void* xn, const void* y, const float* coef, const uint32_t* mask, const float* ls1, void* r, void* duv,
+                         float* dls1, float* d_bn_w, float* d_bn_b, void* bstats, int32_t batch, int32_t n_frames, int32_t mode, int32_t training, float* scratch,
+                         int64_t scratch_floats, void* stream);
+/* bf16 only: kasf_op_mlp_bwd_fused with fc2 finished as a backward stage finishes it.  w2 [128,512] is the fp32 master of fc2 (w2t_scaled stays the bf16 copy of
+ * (ls2 . W2)^T), b2 and ls2 [128] fp32.  With G = g^T H and c = colsum(g):
+ *   dw1, db1, dgamma, dbeta are ACCUMULATED into, as there;
+ *   dw2 [128,512] += ls2[n] G[n][:]  (the SCALED gradient);   dls2 [128] += <w2[n], G[n]> + b2 . c;
+ *   the gsum slot is ASSIGNED db2 = ls2 . c  (what was there before is lost: it is the bias gradient's slot, written once per step).
+ * This form has no atomics fallback: without the rows the finish that scales db2 and adds the b2 term never runs.  So a scratch that is NULL or below
+ * kasf_op_sink_scratch_floats(KASF_SINK_MLP_BWD_FUSED_FC2, ...) is error 2 before any launch, never error 6 after one.  M <= 0: returns 0 after the checks. */
+int kasf_op_mlp_bwd_fused_fc2(const void* x, const void* xn, const void* g, const float* ln_g, const void* w1, const float* b1, const void* w2t_scaled,
+                              const void* w1t, void* dapart, float* partial, float* dw1, float* dw2, float* db1, float* gsum, void* g_in, float* dgamma,
+                              float* dbeta, int64_t M, const float* w2, const float* b2, const float* ls2, float* dls2, float* scratch, int64_t scratch_floats,
+                              void* stream);
 /* ---- the prologue, gate, head and embedding kernels on their own (ADDED under ABI 12: additive, kasf_version() stays 12; a library without them fails to load on
  * the missing symbol).  Thin entries over the launches kasf_forward / kasf_backward make (k_misc.hip, k_reduce.hip), for unit tests against fp64 math.
  * Tensors of the model dtype are void*, everything else fp32.  frames = clips * n_frames, M = frames * 17 tokens in [clip][frame][joint] order.

@@ -33,7 +33,9 @@ FLAG_INPUT_GRAD = 8                    # KASF_FLAG_INPUT_GRAD: kasf_backward als
 EVAL_COLS = 22
 LOSS7_MAX_FRAMES = 360               # KASF_LOSS7_MAX_FRAMES: n_frames of kasf_loss7
 MISC_EMBED_BWD, MISC_REFUSION_BWD, MISC_GATE_BWD, MISC_HEAD_BWD = 0, 1, 2, 3      # KASF_MISC_*: ops of kasf_op_misc_scratch_floats
-GCN_STAT_WORDS = 4 * 512 * 5     # KASF_GCN_STAT_WORDS: int64 words of one BatchNorm statistics buffer of kasf_op_gcn_fwd / kasf_op_gcn_bwd
+SINK_MLP_BWD_FUSED_FC2, SINK_MLP_BWD_ROWS, SINK_DGRAD_LNBWD_ROWS, SINK_GCN_BWD_ROWS = 0, 1, 2, 3      # KASF_SINK_*: ops of kasf_op_sink_scratch_floats
+SINK_FORM_RESID, SINK_FORM_DXN_ADD, SINK_FORM_ACCUMULATE, SINK_FORM_XN_OUT = 1, 2, 4, 8               # KASF_SINK_FORM_*
+GCN_STAT_WORDS = 4 * 512 * 5    # KASF_GCN_STAT_WORDS: int64 words of one BatchNorm statistics buffer of kasf_op_gcn_fwd / kasf_op_gcn_bwd
 OPT_CHUNK_MAX, OPT_MAX_CLASSES = 4096, 32      # KASF_OPT_CHUNK_MAX, KASF_OPT_MAX_CLASSES: kasf_adamw_segments / kasf_grad_norm
 ABI_VERSION = 12        # kasf_version() of the library these prototypes describe (a stale in-tree .so is refused)
 
@@ -183,6 +185,11 @@ SIGNATURES = {
     "kasf_op_attn_block_bwd": (_i32, [_i32] + [_vp] * 30 + [_i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp]),
     "kasf_op_gcn_fwd": (_i32, [_i32] + [_vp] * 13 + [_i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "kasf_op_gcn_bwd": (_i32, [_i32] + [_vp] * 12 + [_i32, _i32, _i32, _i32, _vp]),
+    "kasf_op_sink_scratch_floats": (_i64, [_i32, _i32, _i64, _i32, _i32]),
+    "kasf_op_mlp_bwd_rows": (_i32, [_i32] + [_vp] * 13 + [_i64, _vp, _i64, _vp]),
+    "kasf_op_mlp_bwd_fused_fc2": (_i32, [_vp] * 17 + [_i64] + [_vp] * 5 + [_i64, _vp]),
+    "kasf_op_dgrad_lnbwd_rows": (_i32, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "kasf_op_gcn_bwd_rows": (_i32, [_i32] + [_vp] * 12 + [_i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "kasf_op_misc_scratch_floats": (_i64, [_i32, _i64]),
     "kasf_op_prologue_fwd": (_i32, [_vp] * 8 + [_i64, _vp]),
     "kasf_op_embed_bwd": (_i32, [_i32] + [_vp] * 7 + [_i64, _vp, _i64, _vp]),

@@ -120,9 +120,7 @@ int kasf_op_mlp_fwd(int32_t dtype, const void* x, const float* ln_g, const float
 }
 int kasf_op_mlp_bwd(int32_t dtype, const void* x, const void* g, const float* ln_g, const float* ln_b, const void* w1, const float* b1,
                     const void* w2t_scaled, const void* w1t, void* hbuf, void* dzbuf, void* g_in, float* dgamma, float* dbeta, int64_t M, void* stream) {
-    OP_DT_CHECK(dtype);
-    kasf_launch_mlp_bwd(dtype, (hipStream_t)stream, x, g, ln_g, ln_b, w1, b1, w2t_scaled, w1t, hbuf, dzbuf, nullptr, g_in, dgamma, dbeta, M);
-    return api_done();
+    return kasf_op_mlp_bwd_rows(dtype, x, g, ln_g, ln_b, w1, b1, w2t_scaled, w1t, hbuf, dzbuf, g_in, dgamma, dbeta, M, nullptr, 0, stream);
 }
 int kasf_op_mlp_bwd_fused(const void* x, const void* xn, const void* g, const float* ln_g, const void* w1, const float* b1, const void* w2t_scaled,
                           const void* w1t, void* dapart, float* partial, float* dw1, float* dw2_unscaled, float* db1, float* gsum, void* g_in,
@@ -131,6 +129,48 @@ int kasf_op_mlp_bwd_fused(const void* x, const void* xn, const void* g, const fl
     kasf_launch_mlp_bwd_q((hipStream_t)stream, x, xn, g, ln_g, w1, b1, w2t_scaled, w1t, dapart, partial, dw1, dw2_unscaled, db1, gsum, g_in, dgamma,
                           dbeta, M);
     return api_done();
+}
+// ---- the same launches with a column sink of their own, finished on the same stream: the form a backward stage runs (kasf.h, kasf_op_sink_scratch_floats ...) ----
+// what KasfColSink::take hands out for one request
+static int64_t sink_take_floats(int64_t rows, int64_t ld) { return (rows * ld + 63) / 64 * 64; }
+int64_t kasf_op_sink_scratch_floats(int32_t op, int32_t dtype, int64_t M, int32_t Kd, int32_t form) {
+    if (M < 1) { kasf_set_error(2, "sink_scratch_floats: M must be >= 1"); return -2; }
+    if (op < KASF_SINK_MLP_BWD_FUSED_FC2 || op > KASF_SINK_GCN_BWD_ROWS) { kasf_set_error(2, "sink_scratch_floats: unknown op"); return -2; }
+    if (op != KASF_SINK_MLP_BWD_FUSED_FC2 && dtype != KASF_F32 && dtype != KASF_BF16) { kasf_set_error(2, "sink_scratch_floats: bad dtype"); return -2; }
+    if (op == KASF_SINK_MLP_BWD_FUSED_FC2) {
+        int range_rows = 0;
+        const int rows = kasf_mlp_bwd_q_rows(M, &range_rows);
+        return sink_take_floats(range_rows, 512) + sink_take_floats(rows, 384);
+    }
+    if (op == KASF_SINK_MLP_BWD_ROWS) return sink_take_floats(kasf_mlp_bwd_rows(dtype, M), 256);
+    if (op == KASF_SINK_GCN_BWD_ROWS) return sink_take_floats(kasf_gcn_bwd1_rows(M), 128);
+    if (Kd < 128 || Kd % 128 != 0) { kasf_set_error(2, "sink_scratch_floats: Kd must be a positive multiple of 128"); return -2; }
+    return sink_take_floats(kasf_dgrad_lnbwd_rows(dtype, Kd, (form & KASF_SINK_FORM_RESID) != 0, (form & KASF_SINK_FORM_DXN_ADD) != 0,
+                                                  (form & KASF_SINK_FORM_ACCUMULATE) != 0, (form & KASF_SINK_FORM_XN_OUT) != 0, M), 256);
+}
+int kasf_op_mlp_bwd_rows(int32_t dtype, const void* x, const void* g, const float* ln_g, const float* ln_b, const void* w1, const float* b1,
+                         const void* w2t_scaled, const void* w1t, void* hbuf, void* dzbuf, void* g_in, float* dgamma, float* dbeta, int64_t M, float* scratch,
+                         int64_t scratch_floats, void* stream) {
+    OP_DT_CHECK(dtype);
+    if (int rc = misc_scratch_check(scratch, scratch_floats)) return rc;
+    MiscSink ms(scratch, scratch_floats);
+    kasf_launch_mlp_bwd(dtype, (hipStream_t)stream, x, g, ln_g, ln_b, w1, b1, w2t_scaled, w1t, hbuf, dzbuf, nullptr, g_in, dgamma, dbeta, M, ms.p);
+    return api_done(ms.finish((hipStream_t)stream));
+}
+int kasf_op_mlp_bwd_fused_fc2(const void* x, const void* xn, const void* g, const float* ln_g, const void* w1, const float* b1, const void* w2t_scaled,
+                              const void* w1t, void* dapart, float* partial, float* dw1, float* dw2, float* db1, float* gsum, void* g_in, float* dgamma,
+                              float* dbeta, int64_t M, const float* w2, const float* b2, const float* ls2, float* dls2, float* scratch, int64_t scratch_floats,
+                              void* stream) {
+    if (!x || !xn || !g || !dapart || !partial || !dw1 || !dw2 || !db1 || !gsum || !g_in || !w2 || !b2 || !ls2 || !dls2 || !scratch) return refuse_null();
+    if (int rc = misc_scratch_check(scratch, scratch_floats)) return rc;
+    if (M <= 0) return 0;
+    // no atomics fallback here: without its rows the launch would leave db2 unscaled and dls2 without its b2 term, so a short scratch is refused, not reported behind
+    if (scratch_floats < kasf_op_sink_scratch_floats(KASF_SINK_MLP_BWD_FUSED_FC2, KASF_BF16, M, 0, 0))
+        return refuse("mlp_bwd_fused_fc2", "scratch_floats is below kasf_op_sink_scratch_floats(KASF_SINK_MLP_BWD_FUSED_FC2): this form has no atomics fallback");
+    MiscSink ms(scratch, scratch_floats);
+    kasf_launch_mlp_bwd_q((hipStream_t)stream, x, xn, g, ln_g, w1, b1, w2t_scaled, w1t, dapart, partial, dw1, dw2, db1, gsum, g_in, dgamma, dbeta, M, w2, b2, ls2,
+                          dls2, ms.p);
+    return api_done(ms.finish((hipStream_t)stream));
 }
 int kasf_op_wgrad(int32_t dtype, const void* g, int32_t N, const void* x, int32_t K, const float* ln_g, const float* ln_b, float* dw, float* dbias,
                   int64_t M, float* partial, int64_t partial_floats, void* stream) {
@@ -143,11 +183,18 @@ int kasf_op_wgrad(int32_t dtype, const void* g, int32_t N, const void* x, int32_
 int kasf_op_dgrad_lnbwd(int32_t dtype, const void* dy, int32_t Kd, const void* wt, const void* dxn_add, const void* x, const float* gamma,
                         const void* resid, void* out, int32_t accumulate, float* dgamma, float* dbeta, int64_t M, void* xn_out, const float* beta,
                         void* stream) {
+    return kasf_op_dgrad_lnbwd_rows(dtype, dy, Kd, wt, dxn_add, x, gamma, resid, out, accumulate, dgamma, dbeta, M, xn_out, beta, nullptr, 0, stream);
+}
+int kasf_op_dgrad_lnbwd_rows(int32_t dtype, const void* dy, int32_t Kd, const void* wt, const void* dxn_add, const void* x, const float* gamma,
+                             const void* resid, void* out, int32_t accumulate, float* dgamma, float* dbeta, int64_t M, void* xn_out, const float* beta,
+                             float* scratch, int64_t scratch_floats, void* stream) {
     OP_DT_CHECK(dtype);
     if (Kd % 128 != 0) return kasf_set_error(2, "Kd must be a multiple of 128");
     if (xn_out != nullptr && beta == nullptr) return kasf_set_error(2, "xn_out needs beta");
-    kasf_launch_dgrad_lnbwd(dtype, (hipStream_t)stream, dy, Kd, wt, dxn_add, x, gamma, resid, out, accumulate, dgamma, dbeta, M, xn_out, beta);
-    return api_done();
+    if (int rc = misc_scratch_check(scratch, scratch_floats)) return rc;
+    MiscSink ms(scratch, scratch_floats);
+    kasf_launch_dgrad_lnbwd(dtype, (hipStream_t)stream, dy, Kd, wt, dxn_add, x, gamma, resid, out, accumulate, dgamma, dbeta, M, xn_out, beta, ms.p);
+    return api_done(ms.finish((hipStream_t)stream));
 }
 // the fused data + weight gradient launch with a column sink of its own and the finish launches of a backward stage (engine.hip: kasf_launch_bf16_reduce, or
 // kasf_launch_proj_finish for the PROJ form, then the sink's flush on the same stream)
@@ -408,17 +455,24 @@ int kasf_op_gcn_fwd(int32_t dtype, const void* x_in, const void* xn, const void*
 }
 int kasf_op_gcn_bwd(int32_t dtype, const void* g, const void* xn, const void* y, const float* coef, const uint32_t* mask, const float* ls1, void* r, void* duv,
                     float* dls1, float* d_bn_w, float* d_bn_b, void* bstats, int32_t batch, int32_t n_frames, int32_t mode, int32_t training, void* stream) {
+    return kasf_op_gcn_bwd_rows(dtype, g, xn, y, coef, mask, ls1, r, duv, dls1, d_bn_w, d_bn_b, bstats, batch, n_frames, mode, training, nullptr, 0, stream);
+}
+int kasf_op_gcn_bwd_rows(int32_t dtype, const void* g, const void* xn, const void* y, const float* coef, const uint32_t* mask, const float* ls1, void* r, void* duv,
+                         float* dls1, float* d_bn_w, float* d_bn_b, void* bstats, int32_t batch, int32_t n_frames, int32_t mode, int32_t training, float* scratch,
+                         int64_t scratch_floats, void* stream) {
     OP_DT_CHECK(dtype);
     if (gcn_shape_check(batch, n_frames, mode) != 0) return 2;
     if (!g || !xn || !y || !coef || !ls1 || !r || !duv || !dls1 || !d_bn_w || !d_bn_b || !bstats || (mode == 1 && !mask))
         return refuse_null();
+    if (int rc = misc_scratch_check(scratch, scratch_floats)) return rc;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(bstats, 0, (size_t)KASF_GCN_STAT_WORDS * sizeof(int64_t), s));
-    kasf_launch_gcn_bwd1(dtype, s, g, xn, y, coef, ls1, r, dls1, (double*)bstats, batch, n_frames, mode);
+    MiscSink ms(scratch, scratch_floats);
+    kasf_launch_gcn_bwd1(dtype, s, g, xn, y, coef, ls1, r, dls1, (double*)bstats, batch, n_frames, mode, ms.p);
     const double count = mode == 0 ? (double)batch * n_frames * 128 : (double)batch * 17 * 128;
     kasf_launch_gcn_bwd2(dtype, s, r, y, coef, mode == 1 ? mask : nullptr, duv, batch, n_frames, mode, (const double*)bstats, d_bn_w, d_bn_b, count,
                          training ? 1 : 0);
-    return api_done();
+    return api_done(ms.finish(s));
 }
 // ---- the gate, head and embedding kernels on their own (kasf.h, kasf_op_embed_bwd ... kasf_op_add): the engine's own launchers; the scratch of api_check.h's MiscSink ----
 #define MISC_TOKENS_CHECK(M, what) \

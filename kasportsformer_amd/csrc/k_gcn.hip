@@ -973,12 +973,15 @@ void kasf_launch_gcn_apply(int dt, hipStream_t s, const void* x_in, const void* 
     if (dt == KASF_F32) hipLaunchKernelGGL(k_gcn_apply<float>, dim3(ew_grid(M)), dim3(256), 0, s, (const float*)x_in, (const float*)xn, (const float*)y, stats, bn_w, bn_b, run_mean, run_var, coef, ls1, (float*)out, M, T, mode, nodes, count, training, momentum);
     else hipLaunchKernelGGL(k_gcn_apply<bf16>, dim3(ew_grid(M)), dim3(256), 0, s, (const bf16*)x_in, (const bf16*)xn, (const bf16*)y, stats, bn_w, bn_b, run_mean, run_var, coef, ls1, (bf16*)out, M, T, mode, nodes, count, training, momentum);
 }
+int kasf_gcn_bwd1_rows(int64_t M) {
+    const unsigned grid = ew_grid(M);
+    return (int)(grid > 512 ? 512 : grid);               // block-end atomics on the BN sums are same-address
+}
 void kasf_launch_gcn_bwd1(int dt, hipStream_t s, const void* g, const void* xn, const void* y, const float* coef, const float* ls1, void* r,
                           float* dls1, double* bstats, int B, int T, int mode, KasfColSink* sink) {
     const int64_t M = (int64_t)B * T * KASF_J;
     const int nodes = mode == 0 ? KASF_J : T;
-    unsigned grid = ew_grid(M);
-    if (grid > 512) grid = 512;                          // block-end atomics on the BN sums are same-address
+    const unsigned grid = (unsigned)kasf_gcn_bwd1_rows(M);
     const size_t sh = (size_t)16 * 2 * nodes * sizeof(float);
     float* rows = sink != nullptr ? sink->take((int)grid, 128) : nullptr;
     if (dt == KASF_F32) hipLaunchKernelGGL(k_gcn_bwd1<float>, dim3(grid), dim3(256), sh, s, (const float*)g, (const float*)xn, (const float*)y, coef, ls1, (float*)r, dls1, bstats, M, T, mode, nodes, rows);

@@ -740,6 +740,11 @@ void kasf_launch_linear_res(int dt, hipStream_t s, const void* A, const void* W,
     DT_DISPATCH(dt, (linear_res_T<float>(s, A, W, bias, ls, resid, C, M)), (linear_res_T<bf16>(s, A, W, bias, ls, resid, C, M)));
 }
 
+template <typename T> static int dgrad_lnbwd_grid(int64_t M) { return (int)((M + GemmCfg<T>::BM - 1) / GemmCfg<T>::BM); }
+int kasf_dgrad_lnbwd_rows(int dt, int Kd, bool resid, bool dxn_add, bool accumulate, bool xn_out, int64_t M) {
+    if (dt == KASF_BF16 && kasf_dgrad_r_has(Kd, resid, dxn_add, accumulate, xn_out)) return kasf_dgrad_r_rows(M);
+    return dt == KASF_F32 ? dgrad_lnbwd_grid<float>(M) : dgrad_lnbwd_grid<bf16>(M);
+}
 template <typename T>
 static void dgrad_lnbwd_T(hipStream_t s, const void* dY, int Kd, const void* Wt, const void* dxn_add, const void* X, const float* gamma,
                           const void* resid, void* out, int accumulate, float* dgamma, float* dbeta, int64_t M, void* xn_out, const float* beta,
@@ -747,7 +752,7 @@ static void dgrad_lnbwd_T(hipStream_t s, const void* dY, int Kd, const void* Wt,
     constexpr int BM = GemmCfg<T>::BM, NBUF = GemmCfg<T>::NBUF;
     const size_t sh = (size_t)NBUF * (BM * 128 + 128 * 128) * sizeof(T);
     set_smem(k_dgrad_lnbwd<T, BM, NBUF>, sh);
-    const int grid = (int)((M + BM - 1) / BM);
+    const int grid = dgrad_lnbwd_grid<T>(M);
     float* part = sink != nullptr ? sink->take(grid, 256) : nullptr;
     hipLaunchKernelGGL((k_dgrad_lnbwd<T, BM, NBUF>), dim3((unsigned)grid), dim3(256), sh, s, (const T*)dY, Kd, (const T*)Wt,
                        (const T*)dxn_add, (const T*)X, gamma, (const T*)resid, (T*)out, accumulate, dgamma, dbeta, M, (T*)xn_out, beta, part);

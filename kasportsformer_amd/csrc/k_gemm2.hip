@@ -503,10 +503,14 @@ void launch_linear_r(hipStream_t s, const void* A, const void* W, const float* b
 
 }  // namespace
 
+bool kasf_dgrad_r_has(int Kd, bool R, bool A, bool C, bool XN) {
+    return (Kd == 384 && R && !A && !C && XN) || (Kd == 128 && R && !A && !C && XN) || (Kd == 256 && !R && !A && C && XN) || (Kd == 256 && R && A && !C && !XN);
+}
 // Returns false when the combination is not one of the instantiated ones (the caller then uses k_dgrad_lnbwd).
 bool kasf_launch_dgrad_r(hipStream_t s, const void* dY, int Kd, const void* Wt, const void* dxn_add, const void* X, const float* gamma, const void* resid,
                          void* out, int accumulate, float* dgamma, float* dbeta, int64_t M, void* xn_out, const float* beta, KasfColSink* sink) {
     const bool R = resid != nullptr, A = dxn_add != nullptr, C = accumulate != 0, XN = xn_out != nullptr;
+    if (!kasf_dgrad_r_has(Kd, R, A, C, XN)) return false;
     if (M <= 0) return true;
     if (Kd == 384 && R && !A && !C && XN) launch_dgrad_r<3, true, false, false, true>(s, dY, Wt, dxn_add, X, gamma, beta, resid, out, dgamma, dbeta, xn_out, M, sink);
     else if (Kd == 128 && R && !A && !C && XN) launch_dgrad_r<1, true, false, false, true>(s, dY, Wt, dxn_add, X, gamma, beta, resid, out, dgamma, dbeta, xn_out, M, sink);

@@ -206,7 +206,7 @@ void mlp_bwd_T(hipStream_t s, const void* x, const void* g, const float* ln_g, c
     constexpr int BM = MlpCfg<T>::BM_B, NBUF = MlpCfg<T>::NBUF, NTHR = MlpCfg<T>::NTHR;
     const size_t sh = (size_t)(4 * BM * 128 + NBUF * 128 * 128) * sizeof(T);
     set_smem(k_mlp_bwd<T, BM, NBUF, NTHR>, sh);
-    const int grid = (int)((M + BM - 1) / BM);
+    const int grid = kasf_mlp_bwd_rows(sizeof(T) == 4 ? KASF_F32 : KASF_BF16, M);
     float* part = sink != nullptr ? sink->take(grid, 256) : nullptr;          // one [dgamma | dbeta] row per workgroup
     hipLaunchKernelGGL((k_mlp_bwd<T, BM, NBUF, NTHR>), dim3((unsigned)grid), dim3(NTHR), sh, s, (const T*)x, (const T*)g, ln_g, ln_b,
                        (const T*)W1, b1, (const T*)W2ts, (const T*)W1t, (T*)Hbuf, (T*)dZbuf, (T*)xn_buf, (T*)g_in, dgamma, dbeta, M, part);
@@ -222,6 +222,10 @@ void kasf_launch_mlp_fwd(int dt, hipStream_t s, const void* x, const float* ln_g
     const int64_t tiles = (M + 31) / 32;                 // bf16: persistent producer / consumer kernel (k_mlp3.hip), one workgroup per CU
     const int64_t cap = kasf_narrow_grid(KASF_NG_MLP_FWD, 256, M);
     kasf_launch_mlp_fwd_s(s, x, ln_g, ln_b, W1, b1, W2, b2, ls2, out, M, xn_out, (unsigned)(tiles < cap ? tiles : cap));
+}
+int kasf_mlp_bwd_rows(int dt, int64_t M) {
+    const int BM = dt == KASF_F32 ? MlpCfg<float>::BM_B : MlpCfg<bf16>::BM_B;
+    return (int)((M + BM - 1) / BM);
 }
 void kasf_launch_mlp_bwd(int dt, hipStream_t s, const void* x, const void* g, const float* ln_g, const float* ln_b, const void* W1, const float* b1,
                          const void* W2ts, const void* W1t, void* Hbuf, void* dZbuf, void* xn_buf, void* g_in, float* dgamma, float* dbeta,

@@ -111,15 +111,28 @@ int kasf_mlp_bwd_q_ranges(int64_t M) {
     const int64_t tiles = (M + Q_BM - 1) / Q_BM;
     return (int)(tiles < 64 ? tiles : 64);
 }
+static bool mlp_bwd_dz_form() {
+    static const bool dz_form = [] { const char* e = getenv("KASF_MLP_BWD_DZ"); return e != nullptr && *e == '1'; }();
+    return dz_form;
+}
+static int mlp_bwd_q_tpr(int64_t M, int ranges) { return (int)(((M + Q_BM - 1) / Q_BM + ranges - 1) / ranges); }      // tiles per token range
+static int mlp_bwd_q_used(int64_t M, int tpr) { return (int)(((M + Q_BM - 1) / Q_BM + tpr - 1) / tpr); }              // ranges that own at least one tile
+static int mlp_bwd_q_blocks(int64_t M) {                // streaming workgroups of k_lnbwd_sum4_fin: two rows of 16 lanes per thread
+    const int64_t blocks = (M + 31) / 32;
+    return (int)(blocks > 512 ? 512 : blocks);
+}
+int kasf_mlp_bwd_q_rows(int64_t M, int* range_rows) {
+    *range_rows = mlp_bwd_q_used(M, mlp_bwd_q_tpr(M, kasf_mlp_bwd_q_ranges(M)));
+    return mlp_bwd_dz_form() ? kasf_dgrad_r_rows(M) : mlp_bwd_q_blocks(M);
+}
 void kasf_launch_mlp_bwd_q(hipStream_t s, const void* x, const void* xn, const void* g, const float* ln_g, const void* W1, const float* b1,
                            const void* W2ts, const void* W1t, void* dApart, float* partial, float* dW1, float* dW2, float* db1, float* gsum, void* g_in,
                            float* dgamma, float* dbeta, int64_t M, const float* W2, const float* b2, const float* ls2, float* dls2, KasfColSink* sink) {
     if (M <= 0) return;                                  // (no tile, no range: tpr below would divide by zero)
     int ranges = kasf_mlp_bwd_q_ranges(M);
-    const int64_t tiles = (M + Q_BM - 1) / Q_BM;
     { const int nr = kasf_narrow_grid(KASF_NG_MLP_BWD, 64, M); if (ranges > nr) ranges = nr; }
-    const int tpr = (int)((tiles + ranges - 1) / ranges);
-    const int used = (int)((tiles + tpr - 1) / tpr);             // ranges that own at least one tile
+    const int tpr = mlp_bwd_q_tpr(M, ranges);
+    const int used = mlp_bwd_q_used(M, tpr);
     bf16* p1 = reinterpret_cast<bf16*>(partial);          // (the scratch is sized in floats for the round-3 fp32 tiles: half of it is used)
     bf16* p2 = p1 + (int64_t)used * 512 * 128;
     float* db1_rows = sink != nullptr ? sink->take(used, 512) : nullptr;          // one row of db1 per token range
@@ -127,7 +140,7 @@ void kasf_launch_mlp_bwd_q(hipStream_t s, const void* x, const void* xn, const v
     // (k_dgrad_r<4, ..., MLPFIN>, k_gemm2.hip) forms dA = dZ W1 on its own matrix pipe in front of the LayerNorm backward.  Same bytes, one GEMM moved out of the
     // issue-bound kernel into the HBM-bound one: k_mlp_bwd_s -10 us, the second launch +9..+28 us, step +0.4 % (inside box noise) -- so the partial-sum form of
     // rounds 2-5 (k_lnbwd_sum4_fin) stays the default.  profiles/r6_mlp_bwd_dz_form_ab.md
-    static const bool dz_form = [] { const char* e = getenv("KASF_MLP_BWD_DZ"); return e != nullptr && *e == '1'; }();
+    const bool dz_form = mlp_bwd_dz_form();
     kasf_launch_mlp_bwd_s(s, xn, g, W1, b1, W2ts, W1t, dApart, p1, p2, db1, db1_rows, M, tpr, used, dz_form);
     if (db1_rows != nullptr) sink->add(db1_rows, 512, used, 512, db1);
     if (dz_form) {
@@ -135,8 +148,7 @@ void kasf_launch_mlp_bwd_q(hipStream_t s, const void* x, const void* xn, const v
         kasf_launch_mlp_dgrad_fin(s, dApart, W1t, x, ln_g, g, g_in, dgamma, dbeta, gsum, M, sink, &fa, b2, ls2, dls2, W2 != nullptr);
         return;
     }
-    int64_t blocks = (M + 31) / 32;                     // two rows of 16 lanes per thread
-    if (blocks > 512) blocks = 512;
+    const int blocks = mlp_bwd_q_blocks(M);
     float* rows = sink != nullptr ? sink->take((int)blocks, 384) : nullptr;       // dgamma | dbeta | colsum(g) per streaming workgroup
     const MlpFinArgs fa{p1, p2, dW1, dW2, used, W2, b2, ls2, dls2};
     hipLaunchKernelGGL(k_lnbwd_sum4_fin<2>, dim3((unsigned)blocks + 256), dim3(256), 0, s, (const bf16*)dApart, (const bf16*)x, (const bf16*)g, ln_g,

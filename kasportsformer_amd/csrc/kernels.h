@@ -60,6 +60,8 @@ void kasf_launch_linear_res(int dt, hipStream_t s, const void* A, const void* W,
 void kasf_launch_dgrad_lnbwd(int dt, hipStream_t s, const void* dY, int Kd, const void* Wt, const void* dxn_add, const void* X, const float* gamma,
                              const void* resid, void* out, int accumulate, float* dgamma, float* dbeta, int64_t M, void* xn_out = nullptr,
                              const float* beta = nullptr, KasfColSink* sink = nullptr);   // xn_out: also write LN(x) (operand of the matching weight gradient)
+// the 256-float rows [dgamma | dbeta] that launch asks of the column sink at the full grid (M >= 1): k_dgrad_r's where kasf_dgrad_r_has the form, else k_dgrad_lnbwd's
+int kasf_dgrad_lnbwd_rows(int dt, int Kd, bool resid, bool dxn_add, bool accumulate, bool xn_out, int64_t M);
 void kasf_launch_wgrad(int dt, hipStream_t s, const void* G, int64_t ldg, int N, const void* X, int64_t ldx, int K, const float* ln_g,
                        const float* ln_b, float* out, int64_t ldo, float* dbias, int64_t M, float* partial = nullptr, int64_t partial_floats = 0);
 // partial: optional fp32 scratch (>= splits*N*K floats): per-split tiles are stored there and summed by a second kernel
@@ -76,6 +78,7 @@ void kasf_launch_mlp_fwd(int dt, hipStream_t s, const void* x, const float* ln_g
 void kasf_launch_mlp_bwd(int dt, hipStream_t s, const void* x, const void* g, const float* ln_g, const float* ln_b, const void* W1, const float* b1,
                          const void* W2t_scaled, const void* W1t, void* Hbuf, void* dZbuf, void* xn_buf, void* g_in, float* dgamma, float* dbeta,
                          int64_t M, KasfColSink* sink = nullptr);
+int kasf_mlp_bwd_rows(int dt, int64_t M);      // workgroups of k_mlp_bwd = the 256-float rows [dgamma | dbeta] it asks of the column sink (M >= 1)
 
 // ---- k_mlp2.hip / k_mlp3.hip (bf16): hidden-quarter MLP backward with fused weight gradients ----
 // dApart: 4*M*128 bf16 scratch; partial: >= KASF_MLP_PARTIAL_FLOATS floats; xn = LN(x) as stored by the forward pass.
@@ -87,6 +90,9 @@ void kasf_launch_mlp_bwd_q(hipStream_t s, const void* x, const void* xn, const v
                            const void* W2ts, const void* W1t, void* dApart, float* partial, float* dW1, float* dW2, float* db1, float* gsum, void* g_in,
                            float* dgamma, float* dbeta, int64_t M, const float* W2 = nullptr, const float* b2 = nullptr, const float* ls2 = nullptr,
                            float* dls2 = nullptr, KasfColSink* sink = nullptr);
+// the two takes of kasf_launch_mlp_bwd_q at the full grid (M >= 1): *range_rows rows of 512 floats (db1 per token range that owns a tile), then the returned number
+// of rows of 384 floats (dgamma | dbeta | colsum(g) per streaming workgroup)
+int kasf_mlp_bwd_q_rows(int64_t M, int* range_rows);
 // BatchNorm batch-statistics buffers: KASF_STAT_SLOTS copies of [KASF_MAX_NODES][2] statistics of KASF_STAT_WORDS 64-bit words each (k_gcn.hip: an exact
 // fixed-point accumulator fed by integer atomics; producers pick a copy by workgroup index)
 #define KASF_STAT_SLOTS 4
@@ -126,6 +132,7 @@ void kasf_launch_gcn_apply(int dt, hipStream_t s, const void* x_in, const void* 
                            float momentum);
 void kasf_launch_gcn_bwd1(int dt, hipStream_t s, const void* g, const void* xn, const void* y, const float* coef, const float* ls1, void* r,
                           float* dls1, double* bstats, int B, int T, int mode, KasfColSink* sink = nullptr);
+int kasf_gcn_bwd1_rows(int64_t M);             // workgroups of k_gcn_bwd1 = the 128-float rows of dls1 it asks of the column sink (M = B * T * 17 tokens)
 // BatchNorm-backward finalisation (means of the backward sums, d(bn weight / bias)) is part of bwd2
 void kasf_launch_gcn_bwd2(int dt, hipStream_t s, const void* r, const void* y, const float* coef, const uint32_t* mask, void* duv, int B, int T,
                           int mode, const double* bstats, float* d_bn_w, float* d_bn_b, double count, int training = 1);
@@ -406,6 +413,7 @@ int kasf_launch_dgrad_wg(hipStream_t s, const void* dY, int Kd, const void* Wt, 
 void kasf_launch_proj_finish(hipStream_t s, const void* proj_part, const float* proj_brow, int nparts, float* dW, const float* W, const float* bias, const float* ls,
                              float* db, float* dls, int nred, const KasfBf16Reduce* red);
 void kasf_launch_bf16_reduce(hipStream_t s, int nred, const KasfBf16Reduce* red);      // the fixed-order sum of such partial tiles on its own (no streaming jobs in the block)
+bool kasf_dgrad_r_has(int Kd, bool resid, bool dxn_add, bool accumulate, bool xn_out);      // the forms kasf_launch_dgrad_r has an instantiation for
 bool kasf_launch_dgrad_r(hipStream_t s, const void* dY, int Kd, const void* Wt, const void* dxn_add, const void* X, const float* gamma, const void* resid,
                          void* out, int accumulate, float* dgamma, float* dbeta, int64_t M, void* xn_out, const float* beta, KasfColSink* sink = nullptr);
 bool kasf_launch_linear_r(hipStream_t s, const void* A, const void* W, const float* bias, void* C, int64_t M, int N, const float* ln_g, const float* ln_b,

@@ -45,6 +45,9 @@ JOBS_PARTS = {"att2": (0,), "bone3": (0,), "att1_red": (1, 17, 256), "ext_self":
 MLP_FWD_M = {"fp32": (1, 63, 64, 65, 459), "bf16": (1, 31, 32, 33, 8192, 8193, 32769)}
 MLP_BWD_M = (1, 31, 32, 33, 64, 65, 4099)
 MLP_FUSED_M = (1, 31, 32, 33, 2048, 2049, 10273)
+# kasf_op_mlp_bwd_fused_fc2 (tests/test_gpu_sink_forms.py): 16,417 tokens are 514 tiles of 32, so k_lnbwd_sum4_fin's streaming grid reaches its cap of 512 and
+# workgroups 0 and 1 walk a second time (tiles 512 and 513: the last, ragged tile with its planted rows lies in that walk)
+MLP_FC2_M = MLP_FUSED_M + (16417,)
 CAST_N = (1, 7, 128, 128 * 65539 + 3)
 
 # ---- the fp32 bars: 8 x the measured sensitivity (the worst output of the op, in the measure the GPU test applies to it: per row for token-major outputs, per tensor
@@ -61,6 +64,7 @@ BAR32 = {
     "mlp_fwd": 3e-5,
     "mlp_bwd": 2e-5,
     "mlp_fused": 9e-6,
+    "mlp_fc2": 9e-6,
 }
 # ---- bf16 mode: the measured distance between the fp64 reference and the same reference with the 16-bit roundings in (`Rounded`), same measure, same shape, rounded
 # UP (one digit; mlp_bwd two, since 2e-2 would lift its bar past 3e-2); c[op] = max(BAR32[op], 2 x DIST16[op]) is the term beside the output's own bf16 ulp.  No c
@@ -76,6 +80,7 @@ DIST16 = {
     "mlp_fwd": 5e-3,
     "mlp_bwd": 1.3e-2,
     "mlp_fused": 9e-3,
+    "mlp_fc2": 9e-3,
 }
 
 
@@ -480,6 +485,51 @@ def mlp_bwd_ref(x, gout, gm, bt, W1, b1, W2s, R=Exact, xn_op=None, fused_M_grid=
     return out
 
 
+def mlp_fc2_inputs(M):
+    """the operands of kasf_op_mlp_bwd_fused_fc2 as bf16 mode holds them: those of the fused backward, with W2 the fp32 MASTER of fc2 (the layer-scale algebra reads
+    it; W2s stays the bf16 copy of ls W2 that the data path multiplies by)"""
+    i = stored(mlp_inputs(M, 64), "bf16")
+    i["W2"] = mlp_inputs(M, 64)["W2"]
+    return i
+
+
+def mlp_fc2_ref(x, gout, gm, bt, W1, b1, W2s, W2, b2, ls, R=Exact, xn_op=None):
+    """the fused backward (mlp_bwd_ref, fused_M_grid = 64) with fc2 finished as a backward stage finishes it: dW2 = ls dW2u (SCALED), db2 = ls gsum,
+    dls2 = <W2, dW2u> + b2 gsum.  No 16-bit point beyond mlp_bwd_ref's (the algebra runs in fp32 on the summed tiles); db2 has none at all."""
+    out = mlp_bwd_ref(x, gout, gm, bt, W1, b1, W2s, R, xn_op, 64)
+    out["dW2"], out["db2"], out["dls2"] = ls_algebra(out["dW2u"], out["gsum"], W2, b2, ls)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ scratch of the column sink (kasf_op_sink_scratch_floats, restated)
+def sink_floats(*takes):
+    """KasfColSink::take: (rows, row length) per request, each rounded up to 64 floats"""
+    return sum((rows * ld + 63) // 64 * 64 for rows, ld in takes)
+
+
+def fc2_scratch_floats(M):
+    """kasf_launch_mlp_bwd_q: one row of db1 [512] per token range that owns a tile, one row of dgamma | dbeta | colsum(g) [384] per streaming workgroup (<= 512)"""
+    return sink_floats((len(wg_ranges(M, 32, 64)), 512), (min((M + 31) // 32, 512), 384))
+
+
+def mlp_bwd_rows(cd, M):
+    """k_mlp_bwd's grid: tiles of 32 (fp32) / 64 (bf16) tokens, one row of dgamma | dbeta each"""
+    return (M + 31) // 32 if cd == "fp32" else (M + 63) // 64
+
+
+def dgrad_rows(cd, case, M):
+    """the rows of dgamma | dbeta of kasf_op_dgrad_lnbwd_rows: bf16, the four persistent instantiations of k_dgrad_r: the workgroups that own a tile; otherwise
+    k_dgrad_lnbwd's grid of 64-row tiles"""
+    persistent = cd == "bf16" and tuple(case) in ((384, False, True, False, True), (128, False, True, False, True), (256, False, False, True, True),
+                                                  (256, True, True, False, False))
+    return len(wg_ranges(M)) if persistent else (M + 63) // 64
+
+
+def gcn_bwd_rows(M):
+    """k_gcn_bwd1's grid: 16 tokens per workgroup, capped at 512; one row of dls1 [128] each"""
+    return min(512, max(1, (M * 16 + 255) // 256))
+
+
 # ------------------------------------------------------------------------------------------------ cast
 @functools.lru_cache(maxsize=2)
 def cast_inputs(n):
@@ -550,4 +600,14 @@ def measure(which):
     worst("mlp_bwd", _split(("g_in", "H", "dZ"), mlp_bwd_ref(*_f(i, lo, n), R), mlp_bwd_ref(*_f(i, torch.float64, n))))
     i = stored(mlp_inputs(max(MLP_FUSED_M), 64), cd)
     worst("mlp_fused", _split(("g_in",), mlp_bwd_ref(*_f(i, lo, n), R, None, 64), mlp_bwd_ref(*_f(i, torch.float64, n), Exact, None, 64), skip=("H", "dZ")))
+    out["mlp_fc2"] = measure_fc2(which)
     return out
+
+
+def measure_fc2(which):
+    """measure()'s entry of the fc2 form, at its largest listed shape; dW2u and gsum are not outputs of that entry (dW2 and db2 take their slots)"""
+    f32 = which == "fp32"
+    i = mlp_fc2_inputs(max(MLP_FC2_M)) if not f32 else dict(mlp_inputs(max(MLP_FC2_M), 64))
+    n = ("x", "gout", "gm", "bt", "W1", "b1", "W2s", "W2", "b2", "ls")
+    return _split(("g_in",), mlp_fc2_ref(*_f(i, torch.float32 if f32 else torch.float64, n), Exact if f32 else Rounded),
+                  mlp_fc2_ref(*_f(i, torch.float64, n)), skip=("H", "dZ", "dW2u", "gsum"))

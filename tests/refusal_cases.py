@@ -251,8 +251,15 @@ ENTRIES = [
     ("kasf_op_mlp_fwd", dict(dtype=0, M=1), _DT, ALL),
     ("kasf_op_mlp_bwd", dict(dtype=0, M=1), _DT, ALL),
     ("kasf_op_mlp_bwd_fused", dict(M=1), [], ("ln_g", "w1", "b1", "w2t_scaled", "w1t", "dgamma", "dbeta")),
+    ("kasf_op_sink_scratch_floats", dict(op=0, dtype=0, M=1, Kd=128),
+     [("M", dict(M=0)), ("op", dict(op=4)), ("dtype", dict(op=1, dtype=2)), ("Kd", dict(op=2, Kd=100)), ("Kd_0", dict(op=2, Kd=0), "Kd")], ()),
+    ("kasf_op_mlp_bwd_rows", dict(dtype=0, M=1, scratch_floats=256), _DT + _SCRATCH, ALL),
+    # (M = 1: one token range of 512 floats and one streaming row of 384)
+    ("kasf_op_mlp_bwd_fused_fc2", dict(M=1, scratch_floats=896), _SCRATCH + [("scratch_small", dict(scratch_floats=895))],
+     ("ln_g", "w1", "b1", "w2t_scaled", "w1t", "dgamma", "dbeta")),
     ("kasf_op_wgrad", dict(dtype=0, N=128, K=128, M=1), _DT + [("N", dict(N=100)), ("K", dict(K=100)), ("ln_K", dict(K=256))], ALL),
     ("kasf_op_dgrad_lnbwd", dict(dtype=0, Kd=128, M=1), _DT + [("Kd", dict(Kd=100)), ("beta", dict(beta=None))], ALL),
+    ("kasf_op_dgrad_lnbwd_rows", dict(dtype=0, Kd=128, M=1, scratch_floats=256), _DT + [("Kd", dict(Kd=100)), ("beta", dict(beta=None))] + _SCRATCH, ALL),
     ("kasf_op_dgrad_wg", dict(Kd=128, M=1, wpart_bytes=_WG_TILES, scratch_floats=256, dxn_add=None, dbias=None, **_NO_PROJ),
      [("proj_together", dict(proj_o=BUF)), ("form", dict(Kd=512)), ("form_resid", dict(resid=None), "form"), ("form_acc", dict(accumulate=1), "form"),
       ("form_uv", dict(Kd=256, dxn_add=BUF), "form"), ("form_proj", dict(Kd=384, **_PROJ), "form"), ("wpart_bytes", dict(wpart_bytes=_WG_TILES - 1)),
@@ -294,6 +301,7 @@ ENTRIES = [
     ("kasf_op_gcn_fwd", dict(dtype=0, batch=1, n_frames=4, mode=1, neighbour_num=4),
      _GCN + [("neighbour_num", dict(neighbour_num=0)), ("neighbour_num_big", dict(neighbour_num=5))], ()),
     ("kasf_op_gcn_bwd", dict(dtype=0, batch=1, n_frames=4, mode=1), _GCN, ()),
+    ("kasf_op_gcn_bwd_rows", dict(dtype=0, batch=1, n_frames=4, mode=1, scratch_floats=128), _GCN + _SCRATCH, ("scratch",)),
     ("kasf_op_embed_bwd", dict(dtype=0, frames=1, scratch_floats=16), _DT + [("frames", dict(frames=0)), ("frames_big", dict(frames=2 ** 19))] + _SCRATCH,
      ("din3", "scratch")),
     ("kasf_op_gate_fwd", dict(dtype=0, M=1), _DT + [("tokens", dict(M=0)), ("tokens_big", dict(M=2 ** 23))], ("alpha",)),

@@ -192,6 +192,52 @@ def test_mlp_backward_formulas_are_autograd_of_the_forward():
             assert R.rel_err(got, want) < 1e-9
 
 
+def test_fc2_finish_is_autograd_of_the_forward():
+    """dW2 (SCALED), db2 and dls2 of mlp_fc2_ref -- dense_ref.ls_algebra on the unscaled dW2u and gsum of the fused backward -- against fp64 autograd of mlp_fwd_ref
+    with respect to W2, b2 and ls"""
+    i = R.to(R.mlp_inputs(459, 64), torch.float64)
+    leaf = {k: i[k].clone().requires_grad_(True) for k in ("W2", "b2", "ls")}
+    R.mlp_fwd_ref(i["x"], i["gm"], i["bt"], i["W1"], i["b1"], leaf["W2"], leaf["b2"], leaf["ls"])["out"].backward(i["gout"])
+    r = R.mlp_fc2_ref(i["x"], i["gout"], i["gm"], i["bt"], i["W1"], i["b1"], i["ls"][:, None] * i["W2"], i["W2"], i["b2"], i["ls"])
+    for got, want in ((r["dW2"], leaf["W2"].grad), (r["db2"], leaf["b2"].grad), (r["dls2"], leaf["ls"].grad)):
+        assert R.rel_err(got, want) < 1e-9
+    # the operands of the entry: W2 is the fp32 master, W2s the bf16 copy of ls W2
+    j, raw = R.mlp_fc2_inputs(33), R.mlp_inputs(33, 64)
+    assert torch.equal(j["W2"], raw["W2"]) and torch.equal(j["W2s"], (raw["ls"][:, None] * raw["W2"]).to(torch.bfloat16).float())
+    assert not torch.equal(j["W2"], j["W2"].to(torch.bfloat16).float())
+
+
+def test_sink_scratch_query_is_the_launchers_arithmetic(lib):
+    """kasf_op_sink_scratch_floats (computed by the helpers the launchers call) against dense_ref's restatement of each launch's requests of the column sink, at the
+    listed shapes and around every edge of the grids: needs no device"""
+    from kasportsformer_amd import _lib
+    for n, count in (("kasf_op_sink_scratch_floats", 5), ("kasf_op_mlp_bwd_rows", 18), ("kasf_op_mlp_bwd_fused_fc2", 25), ("kasf_op_dgrad_lnbwd_rows", 18),
+                     ("kasf_op_gcn_bwd_rows", 20)):
+        assert n in _lib.SIGNATURES and hasattr(lib, n) and getattr(lib, n).argtypes == _lib.SIGNATURES[n][1] and len(_lib.SIGNATURES[n][1]) == count, n
+    q = lib.kasf_op_sink_scratch_floats
+    edges = (1, 31, 32, 33, 63, 64, 65, 2047, 2048, 2049, 8191, 8192, 8193, 16383, 16384, 16385, 16417, 24577, 40003, 65637, 176256)
+    for M in sorted(set(edges + R.MLP_FC2_M + R.MLP_BWD_M + R.DGRAD_M)):
+        assert q(_lib.SINK_MLP_BWD_FUSED_FC2, 1, M, 0, 0) == R.fc2_scratch_floats(M), M
+        assert q(_lib.SINK_GCN_BWD_ROWS, 0, M, 0, 0) == q(_lib.SINK_GCN_BWD_ROWS, 1, M, 0, 0) == R.sink_floats((R.gcn_bwd_rows(M), 128)), M
+        for code, cd in ((0, "fp32"), (1, "bf16")):
+            assert q(_lib.SINK_MLP_BWD_ROWS, code, M, 0, 0) == R.sink_floats((R.mlp_bwd_rows(cd, M), 256)), (cd, M)
+            for case in R.DGRAD_CASES:
+                Kd, add, resid, acc, xn = case
+                form = _lib.SINK_FORM_RESID * resid + _lib.SINK_FORM_DXN_ADD * add + _lib.SINK_FORM_ACCUMULATE * acc + _lib.SINK_FORM_XN_OUT * xn
+                assert q(_lib.SINK_DGRAD_LNBWD_ROWS, code, M, Kd, form) == R.sink_floats((R.dgrad_rows(cd, case, M), 256)), (cd, case, M)
+    assert R.fc2_scratch_floats(1) == 512 + 384 and R.fc2_scratch_floats(16417) == 58 * 512 + 512 * 384 and R.sink_floats((1, 100), (3, 50)) == 128 + 192
+    assert R.gcn_bwd_rows(68) == 5 and R.gcn_bwd_rows(8192) == 512 and R.gcn_bwd_rows(65637) == 512
+    assert min((16417 + 31) // 32, 512) == 512 < (16417 + 31) // 32                  # the shape at which k_lnbwd_sum4_fin's streaming workgroups walk twice
+    # the fc2 form: M = 0 returns 0 before any device call; a missing or short scratch is refused (error 2), never fallen back from
+    import ctypes as C
+    buf = C.create_string_buffer(4096 + 64)
+    p = (C.addressof(buf) + 63) // 64 * 64
+    assert lib.kasf_op_mlp_bwd_fused_fc2(*[p] * 17, 0, *[p] * 5, 16, None) == 0
+    assert lib.kasf_op_mlp_bwd_fused_fc2(*[p] * 17, 33, p, p, p, p, None, 0, None) == 2
+    assert lib.kasf_op_mlp_bwd_fused_fc2(*[p] * 17, 33, *[p] * 5, R.fc2_scratch_floats(33) - 1, None) == 2 and b"no atomics fallback" in lib.kasf_last_error()
+    assert not any(buf.raw)
+
+
 def test_sensitivities_are_within_the_bars():
     """BAR32 is 8 x what a plain fp32 evaluation of the reference loses against the fp64 one, DIST16 what the reference moves by when the 16-bit storage points of
     the bf16 kernels are rounded, each at the op's largest listed shape with the plants in.  Re-measured here: both evaluations must stay within
