@@ -182,6 +182,16 @@ def test_bgr_to_nv12_equals_the_restatement(Hf, Wf):
         assert np.array_equal(y.cpu().numpy(), wy) and np.array_equal(uv.cpu().numpy(), wuv)
 
 
+def round_trip_limit(matrix, full_range):
+    """The round trip's bound per channel, {"B", "G", "R"} -> grey levels, from the two stated accuracies (the derivation is in the test below; the composed
+    tick tests import it from here)."""
+    from tests.test_draw_cpu import nv12_bound
+    bY, bU, bV = nv12_bound(matrix, full_range)
+    _, (iB, iG, iR) = yuv_bounds(matrix, full_range)
+    cy, cvr, cvg, cug, cub = yuv_exact(matrix, full_range)
+    return {"B": iB + cy * bY + abs(cub) * bU, "G": iG + cy * bY + abs(cug) * bU + abs(cvg) * bV, "R": iR + cy * bY + abs(cvr) * bV}
+
+
 @pytest.mark.parametrize("matrix,full_range", [("bt601", False), ("bt601", True), ("bt709", False), ("bt709", True)])
 def test_a_flat_colour_survives_the_round_trip_within_the_two_bounds(matrix, full_range):
     """yuv_to_bgr(bgr_to_nv12(frame)) on flat-colour frames.  Each of Y, U, V is within its stated bound b_f (tests/test_draw_cpu.py, nv12_bound: 0.5 + ...) of
@@ -189,11 +199,7 @@ def test_a_flat_colour_survives_the_round_trip_within_the_two_bounds(matrix, ful
     1-Lipschitz), and yuv_to_bgr's own stated bound b_i (tests/test_yuv_cpu.py, bounds) comes on top: |error| <= b_i + |cy| bY + sum |c| b_chroma, an integer, so
     at most its floor.  That is 2 grey levels for every table; it is computed here, not assumed."""
     import kasportsformer_amd as K
-    from tests.test_draw_cpu import nv12_bound
-    bY, bU, bV = nv12_bound(matrix, full_range)
-    _, (iB, iG, iR) = yuv_bounds(matrix, full_range)
-    cy, cvr, cvg, cug, cub = yuv_exact(matrix, full_range)
-    limit = {"B": iB + cy * bY + abs(cub) * bU, "G": iG + cy * bY + abs(cug) * bU + abs(cvg) * bV, "R": iR + cy * bY + abs(cvr) * bV}
+    limit = round_trip_limit(matrix, full_range)
     print(matrix, full_range, limit)
     assert max(int(v) for v in limit.values()) <= 2, "the two grey levels the round trip is stated to keep"
     g = np.random.default_rng(1)
